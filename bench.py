@@ -12,6 +12,10 @@ Prints ONE JSON line (rank 0).  N > 1: one process per GPU -- either launched by
 form: WORLD_SIZE / RANK / LOCAL_RANK in the environment, `--gpus` must equal WORLD_SIZE), or `python bench.py --gpus N` alone:
 with WORLD_SIZE unset this process starts the N ranks itself (torch.distributed.run as a child, before anything here touches
 the GPU) and exits with their status -- what `pl.Trainer(gpus=N)` does for the reference (pmgt/base_trainer.py:309-322).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the side measurements after the timed steps (host
+sampler rate, per-phase pass with rooflines, batch sweep, live pipeline, child workloads, CPU baseline, all-reduce timing); none of
+them changes `value` or `ms_per_step`.  --dump-outputs DIR writes what the last timed step computed as .npy files, for comparing builds.
 """
 import argparse
 import json
@@ -80,7 +84,17 @@ def parse():
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher check that needs no GPU: the ranks rendezvous over gloo, all-reduce their ranks and rank 0 prints "
                          "a line with n_gpus = world and value = null")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed steps: host sampler rate, phase pass + rooflines, batch sweep, live "
+                         "pipeline, child workloads, CPU baseline, all-reduce timing (each still switched off by its --no-* option).  Without "
+                         "it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (losses, logits, masked-row count, pre-clip "
+                         "gradient norm, gradients, updated parameters) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -236,6 +250,38 @@ def time_steps(trainer, staged, steps, warmup):
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_BUDGET = 60_000_000     # bytes of .npy payload per --dump-outputs directory (64 MB with room for the file headers)
+DUMP_WHOLE = 1 << 20         # arrays up to this size are always written whole
+
+
+def last_step_outputs(trainer, eng):
+    """What the last train_step handed its caller (the engine's output set of that step) and left in the engine (gradients, parameters
+    after clip + AdamW), as host arrays.  Call before any further step: the output set is recycled."""
+    o = trainer.last_outputs
+    return {"losses": o["losses"].float().cpu().numpy(),                     # [loss, GSR loss, NFR loss]
+            "logits": o["logits"].float().cpu().numpy(),
+            "nfr_count": o["nfr_count"].cpu().numpy().astype(np.float64),
+            "grad_norm": eng.grad_norm().reshape(1).float().cpu().numpy(),
+            "grads": eng.grads.float().cpu().numpy(),
+            "params": eng.params.float().cpu().numpy()}
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """arrays -> dirname/<name>.npy (1-D, float32 / float64).  Arrays above DUMP_WHOLE share what the small ones leave of `budget`; one
+    that does not fit its share is written as a fixed sample: the elements at a sorted draw without replacement from a generator
+    seeded with 0, so two runs of the same configuration write the same positions."""
+    os.makedirs(dirname, exist_ok=True)
+    flat = {k: np.ascontiguousarray(v).reshape(-1) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in flat.values() if a.nbytes <= DUMP_WHOLE)
+    n_big = sum(1 for a in flat.values() if a.nbytes > DUMP_WHOLE)
+    share = (budget - small) // max(n_big, 1)
+    for k, a in flat.items():
+        if a.nbytes > DUMP_WHOLE and a.nbytes > share:
+            keep = share // a.itemsize
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -344,16 +390,18 @@ def main():
 
     n_stage = min(args.steps + args.warmup, 8)
     staged = stage(B, n_stage)
-    # sustained rate of the host sampler alone, as the live pipeline uses it: one warm call (worker pool and staging buffers
-    # exist, pages touched), then back-to-back calls into one buffer
-    slot = sampler.alloc(B, MODE_TRAIN)
-    sampler.batch(np.resize(shard, B), MODE_TRAIN, out=slot, threads=threads, base_seed=rank, counter=n_stage * B)
-    t0 = time.perf_counter()
-    for i in range(4):
-        sampler.batch(np.resize(shard[(i * B) % max(len(shard) - B, 1):], B), MODE_TRAIN, out=slot, threads=threads,
-                      base_seed=rank, counter=(n_stage + 1 + i) * B)
-    sampler_nodes_per_s = 4 * B / max(time.perf_counter() - t0, 1e-9)
-    del slot
+    sampler_nodes_per_s = None
+    if args.full:
+        # sustained rate of the host sampler alone, as the live pipeline uses it: one warm call (worker pool and staging buffers
+        # exist, pages touched), then back-to-back calls into one buffer
+        slot = sampler.alloc(B, MODE_TRAIN)
+        sampler.batch(np.resize(shard, B), MODE_TRAIN, out=slot, threads=threads, base_seed=rank, counter=n_stage * B)
+        t0 = time.perf_counter()
+        for i in range(4):
+            sampler.batch(np.resize(shard[(i * B) % max(len(shard) - B, 1):], B), MODE_TRAIN, out=slot, threads=threads,
+                          base_seed=rank, counter=(n_stage + 1 + i) * B)
+        sampler_nodes_per_s = 4 * B / max(time.perf_counter() - t0, 1e-9)
+        del slot
 
     def barrier():
         if exchange:
@@ -387,6 +435,9 @@ def main():
         # a step whose loss or pre-clip gradient norm is not finite does no learning (clip coefficient 0 / NaN parameters):
         # its time is not a measurement of the training step
         raise RuntimeError(f"bench: non-finite training state after the timed steps (loss {loss_last}, grad norm {grad_norm_last})")
+    # (before any side measurement: those run more steps on the same engine)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(trainer, eng))
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
 
@@ -416,15 +467,17 @@ def main():
         "setup_s": round(setup_s, 1),
         "side_stream_reductions": bool(args.overlap),
         "engine_options": list(args.engine_option),
-        # (per rank; vs_gpu_consumption < 1 means a run fed by the live sampler -- --end-to-end -- is bound by the host on this CPU share, not
-        #  by the GPU: `value` is the pre-staged rate and does not depend on it)
-        "host_sampler": {"nodes_per_s": round(sampler_nodes_per_s, 1), "threads": threads, "cpus": os.cpu_count(),
-                         "cpu_share": round(share, 1), "ranks_on_host": local_world,
-                         "vs_gpu_consumption": round(sampler_nodes_per_s / max(value / world, 1e-9), 3)},
         "allreduce": None,
     }
+    if sampler_nodes_per_s is not None:
+        # (per rank; vs_gpu_consumption < 1 means a run fed by the live sampler -- --end-to-end -- is bound by the host on this CPU share, not
+        #  by the GPU: `value` is the pre-staged rate and does not depend on it)
+        out["host_sampler"] = {"nodes_per_s": round(sampler_nodes_per_s, 1), "threads": threads, "cpus": os.cpu_count(),
+                               "cpu_share": round(share, 1), "ranks_on_host": local_world,
+                               "vs_gpu_consumption": round(sampler_nodes_per_s / max(value / world, 1e-9), 3)}
     if exchange:
         out["exchange_backend"] = dist.get_backend()
+    if exchange and args.full:
         # (a side measurement: every rank enters it, and a failure inside it must not cost the line its headline numbers; a collective that
         #  raises does so on every rank at the same call, so the ranks stay in step)
         try:
@@ -461,7 +514,7 @@ def main():
     # ---- per-phase HIP-event timers (separate pass, not part of `value`).  EVERY rank runs it, collectives included: the
     # control flow of all ranks is identical from init to destroy (only rank 0 prints), so no rank can be left alone in a
     # collective or tear the process group down while a peer still uses it.
-    if not args.no_phase_profile:
+    if args.full and not args.no_phase_profile:
         nprof = 5
         eng.profile_begin()
         for i in range(nprof):
@@ -552,7 +605,7 @@ def main():
 
     # ---- batch sizes of the reference's own entry points (N = 1): B=32 = scripts/run_pmgt.sh:11, B=256 = the CLI default
     # (train.py:33-38); eager launches and, where capture works, the whole step replayed as ONE hipGraph
-    if world == 1 and not args.no_batch_sweep:
+    if world == 1 and args.full and not args.no_batch_sweep:
         sweep = {}
         for Bx in (32, 256):
             if Bx == B:
@@ -595,7 +648,7 @@ def main():
     # training job sees; `value` above is the pre-staged rate the metric is defined on.  Every rank runs it (symmetric).
     # (at N > 1 only on request: the data-parallel numbers the driver collects are the pre-staged `value`; the multi-rank live pipeline
     # has only been rehearsed over gloo on one GPU)
-    if not args.no_end_to_end and (world == 1 or args.end_to_end):
+    if args.full and not args.no_end_to_end and (world == 1 or args.end_to_end):
         # untimed pass first: pinned slots, device slots and the worker pool exist, pages touched, and (N = 1) the step is captured once
         # per slot -- the timed pass replays it with one launch per step (a launch thread that loses its CPU mid-step on a shared
         # host otherwise shows up as GPU idle time inside the step)
@@ -613,11 +666,11 @@ def main():
     # ---- the other single-GPU configurations of BASELINE.json that are quoted anywhere: c4 shapes (10^6 nodes, L6 d512 S64) in bf16 and
     # in the fp8 mode (config 5), B = 256, ten steps each, in a child process of their own (a fresh engine and workspace; this
     # process only waits).  A child that does not deliver within the budget is reported as skipped with the reason.
-    if rank == 0 and world == 1 and args.workload == "c2" and not args.no_extra_workloads:
+    if rank == 0 and world == 1 and args.full and args.workload == "c2" and not args.no_extra_workloads:
         out["workloads"] = extra_workloads()
 
     # ---- CPU baseline: the oracle (CPU restatement pinned to the reference) on a bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, graph, S, args.dropout)
 
     if rank == 0:
@@ -654,7 +707,7 @@ def extra_workloads():
         # (the child's stdout is its own compact line; the parent reads the child's full record from a file of its own)
         tmp = tempfile.NamedTemporaryFile(prefix=f"pmgt_bench_{name}_", suffix=".json", delete=False)
         tmp.close()
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-end-to-end",
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-end-to-end",
                "--no-batch-sweep", "--no-extra-workloads", "--detail-out", tmp.name] + extra
         t0 = time.perf_counter()
         try:

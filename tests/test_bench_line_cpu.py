@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,3 +157,46 @@ def test_committed_traffic_files_were_measured_on_these_kernels():
         arg = lambda flag, dflt: extra[extra.index(flag) + 1] if flag in extra else dflt
         key = bench.traffic_key(arg("--workload", "c2"), int(arg("--intermediate", 0)), float(arg("--beta", 0.5)), int(arg("--batch", 1024)))
         assert key in want, (name, key)
+
+
+def test_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: small arrays are written whole; large ones share the rest of the budget, and one that does not fit its share is a
+    seeded sample -- the same positions on every run, so two builds compare element for element."""
+    rs = np.random.RandomState(0)
+    pos = np.arange(3_000_000, dtype=np.float32)          # each element names its own position (exact in float32 below 2^24)
+    arrays = {"losses": rs.rand(3).astype(np.float32), "nfr_count": np.array([17.0]), "params": pos, "grads": pos * 2}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == v.dtype and np.array_equal(got, v), k
+    budget = 8 * 10 ** 6
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    sizes = sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) - 128 for k in arrays)
+    assert sizes <= budget
+    a, b = (np.load(tmp_path / "a" / "params.npy")), np.load(tmp_path / "b" / "params.npy")
+    assert np.array_equal(a, b) and 0 < a.size < pos.size and (np.diff(a) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "losses.npy"), arrays["losses"])
+    # the same positions in every array of the same length: a parameter's sample lines up with its gradient's
+    assert np.array_equal(np.load(tmp_path / "a" / "grads.npy"), a * 2)
+
+
+def test_plain_run_does_only_the_timed_steps():
+    """Without --full, main() runs no side measurement: every call that measures something besides the timed steps sits under a test on
+    args.full."""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    side = ("profile_begin", "time_steps", "run_live", "capture_step", "extra_workloads", "cpu_baseline", "measure_allreduce", "sampler.alloc")
+    gated = set()
+    for node in ast.walk(main):
+        if isinstance(node, ast.If) and "args.full" in ast.unparse(node.test):
+            gated.update(id(n) for b in node.body for n in ast.walk(b))
+    for node in ast.walk(main):
+        if isinstance(node, ast.Call) and any(s in ast.unparse(node.func) for s in side):
+            assert id(node) in gated, ast.unparse(node)[:200]
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()

@@ -172,7 +172,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(tmp_path, launch):
         env.pop(k, None)
     detail = str(tmp_path / "detail.json")
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--sampler-threads", "2",
-            "--detail-out", detail]
+            "--full", "--detail-out", detail]
     if launch == "driver":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + tail
@@ -220,7 +220,7 @@ def test_bench_force_exchange_prints_exactly_one_json_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-exchange", "--steps", "3", "--warmup", "1", "--batch", "64", "--sampler-threads", "2",
-           "--no-cpu-baseline", "--no-end-to-end", "--no-batch-sweep", "--no-extra-workloads"]
+           "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-batch-sweep", "--no-extra-workloads"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -231,7 +231,7 @@ def test_bench_force_exchange_prints_exactly_one_json_line():
 
 
 def test_bench_with_the_drivers_exact_command_prints_one_parsable_line_under_4_kb():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the command BENCH_rNN.json records, every default side measurement on (phase pass,
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the command BENCH_rNN.json records plus --full: every side measurement on (phase pass,
     batch sweep, live pipeline, six child workloads, CPU baseline).  Round 5's line was 20 KB and the driver's record lost its head; the line is now
     bounded, starts with the contract's keys, carries `roofline` and `cpu_baseline`, and the full record sits in bench_detail.json."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -240,7 +240,7 @@ def test_bench_with_the_drivers_exact_command_prints_one_parsable_line_under_4_k
     detail = os.path.join(ROOT, "bench_detail.json")
     if os.path.exists(detail):
         os.unlink(detail)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], env=env, cwd=ROOT, capture_output=True,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -259,3 +259,38 @@ def test_bench_with_the_drivers_exact_command_prints_one_parsable_line_under_4_k
         assert "skipped" in w or (w["nodes_per_s"] > 0 and w["roofline_kernel"]), (name, w)
     full = json.load(open(detail))
     assert full["value"] == out["value"] and "phases" in full and "roofline_top3" in full and "batch_sweep" in full
+
+
+def test_plain_bench_times_only_the_steps_and_dumps_the_same_outputs_run_to_run(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` without --full: the line carries the contract's keys and none of the side measurements,
+    and --dump-outputs writes what the last timed step computed.  The inputs are seeded and the engine is bit-reproducible, so two runs with the
+    same arguments dump the same arrays."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        dump, detail = tmp_path / run, tmp_path / f"detail_{run}.json"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(dump),
+                            "--detail-out", str(detail)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{\"metric\""), r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["metric"] == "PMGT pre-train nodes/sec" and out["unit"] == "target nodes/s" and out["higher_is_better"] is True
+        assert out["steps"] == 20 and out["warmup"] == 5 and out["dtype"] == "bf16" and out["n_gpus"] == 1
+        assert abs(out["value"] - 1024 / out["ms_per_step"] * 1e3) / out["value"] < 1e-3
+        for k in ("roofline", "roofline_top3", "cpu_baseline", "end_to_end", "workloads", "batch_sweep", "host_sampler"):
+            assert k not in out, k
+        assert "phases" not in json.load(open(detail))
+        files = sorted(os.listdir(dump))
+        assert files == sorted(n + ".npy" for n in ("losses", "logits", "nfr_count", "grad_norm", "grads", "params")), files
+        arrs = {f[:-4]: np.load(dump / f) for f in files}
+        assert sum(os.path.getsize(dump / f) for f in files) <= 64 * 10 ** 6
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrs.values())
+        assert abs(arrs["losses"][0] - out["loss_last"]) <= 1e-4 * abs(out["loss_last"]) + 1e-5
+        assert abs(arrs["grad_norm"][0] - out["grad_norm_last"]) <= 1e-4 * abs(out["grad_norm_last"]) + 1e-5
+        assert arrs["params"].size == arrs["grads"].size and arrs["nfr_count"][0] > 0
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

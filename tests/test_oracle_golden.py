@@ -89,9 +89,14 @@ def test_oracle_train_loss_and_grads(name):
 
 @pytest.mark.parametrize("name", ["m1", "m1_pad", "m4"])
 def test_oracle_optimizer_curve(name):
+    """Several clip + AdamW steps.  The oracle runs in float64 from the fp32 parameters and tables the reference was loaded with: AdamW
+    divides by sqrt(v), so a parameter whose gradient is the small remainder of terms that nearly cancel (a key bias) carries the rounding
+    of that remainder into its value at ~lr per step.  In fp32 that rounding follows the summation order of the host's CPU kernels (thread
+    count, vector width); in float64 it is negligible, and what is left to compare is the reference's own fp32 rounding in the fixture."""
     c = gu.model_case(name)
-    gold, cfg, tabs = c["gold"], c["cfg"], c["tables"]
-    p = {k: v.clone() for k, v in c["params"].items()}
+    gold, cfg = c["gold"], c["cfg"]
+    tabs = [t.double() for t in c["tables"]]
+    p = {k: v.double() for k, v in c["params"].items()}
     state = {}
     nsteps = len(gold["opt_losses"])
     for s in range(nsteps):

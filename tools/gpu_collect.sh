@@ -8,11 +8,11 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/set_$TAG
 mkdir -p $OUT
 cd $REPO
-Q="--no-cpu-baseline --no-extra-workloads"
+Q="--full --no-cpu-baseline --no-extra-workloads"
 QQ="$Q --no-end-to-end --no-batch-sweep"
 if [ "$PART" = "lines" ]; then
   # stdout = the ONE compact line the driver records (<name>.line.json), --detail-out = the full record (<name>.json)
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail-out $OUT/bench_B1024.json > $OUT/bench_B1024.line.json 2> /dev/null || exit 1
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-out $OUT/bench_B1024.json > $OUT/bench_B1024.line.json 2> /dev/null || exit 1
   echo "default line done: $(wc -c < $OUT/bench_B1024.line.json) bytes"
   python3 bench.py --workload c3 $Q --detail-out $OUT/bench_c3_B1024.json > $OUT/bench_c3_B1024.line.json 2>> $OUT/err.log || exit 1
   python3 bench.py --dtype fp8 $QQ --detail-out $OUT/bench_fp8_B1024.json > /dev/null 2>> $OUT/err.log || exit 1
