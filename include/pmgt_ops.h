@@ -135,6 +135,82 @@ int pmgt_op_attention_bwd_wgrad(const void* qkvc, const float* mask, const void*
                                 float* bias_slab, int n_seq, int H, float beta, float drop_p, uint32_t site1, uint32_t site2,
                                 const uint64_t* rng, int head_major, void* stream);
 
+/* ---- row kernels of the embedding, the loss heads and the optimizer: each entry calls the host function the engine calls, with
+ * the engine's dispatch (template instance by dtype / hidden size / modality count; the embed_tok8 kernel for bf16, phase 2, d = 256
+ * with e_rows set, counted in the launch trace).  dtype: PMGT_DTYPE_F32 or PMGT_DTYPE_BF16 (activations); fp32 parameters. */
+
+/* Modality mix + position + role + LayerNorm + dropout of PMGTEmbeddings from the projected feature rows on, and its backward.
+ * phase 0: per token, E [M, nf d] (row e_rows[m] when e_rows != NULL);  table mode: phase 1 (rows = nodes) fwd writes a [M, nf] and
+ * pre = F [M, d] = sum_k a_k e_k; bwd reads dF [M, d] (fp32 when dF_f32) and writes dE [M, nf d] + dWa / dba partials;  phase 2
+ * (rows = tokens) fwd: x = E[e_rows[m]] (row stride d) + pos + role -> LayerNorm -> dropout, bwd: LayerNorm backward only (dF, dgamma /
+ * dbeta partials).  pre == NULL in phase 2 (bf16, d = 256): the backward recomputes the pre-LayerNorm sum from E, pos and role.
+ * part: [pmgt_op_embed_bwd_parts(M)][pmgt_op_embed_part_elems(d, nf)] = dgamma | dbeta | dWa (nf x nf d) | dba (padded to 4) per
+ * workgroup.  Dropout on h0 (forward) and dh0 (backward) with (rng, drop_p, drop_site) as the other entries; rng == NULL: none. */
+typedef struct pmgt_embed_args {
+    int dtype, phase, M, S, d, nf;
+    const void* E;
+    const int64_t* e_rows;
+    const float *Wa, *ba, *pos, *role, *gamma, *beta;
+    float eps;
+    float* a;
+    void* pre;
+    float* stats;
+    void* h0;
+    float drop_p;
+    uint32_t drop_site;
+    const uint64_t* rng;
+    const void* dh0;
+    void* dE;
+    void* dF;
+    int dF_f32;
+    float* part;
+} pmgt_embed_args;
+int pmgt_op_embed_mix_fwd(const pmgt_embed_args* args, void* stream);
+int pmgt_op_embed_mix_bwd(const pmgt_embed_args* args, void* stream);
+int pmgt_op_embed_part_elems(int d, int nf);
+int pmgt_op_embed_bwd_parts(int M);
+/* dpos [max_pos, d] = possum [S, d] (zero rows for s >= S), drole [2, d] = {possum[0], sum_{s >= 1} possum[s]}; accumulate: += */
+int pmgt_op_pos_role_finish(const float* possum, int S, int d, int max_pos, float* dpos, float* drole, int accumulate, void* stream);
+/* out [n_rows, cols] (row stride cols) = per-node sums of src [M, cols] (row stride ld) over the segments of pmgt_op_seg_sort's
+ * skeys / perm / seg_off; zero rows for empty segments.  (in_dtype, out_dtype): (F32, F32), (BF16, BF16) or (BF16, F32).
+ * part: pmgt_op_seg_part_elems(M, cols) floats of scratch. */
+int64_t pmgt_op_seg_part_elems(int M, int cols);
+int pmgt_op_seg_sum(int in_dtype, int out_dtype, const void* src, int64_t ld, const uint32_t* skeys, const uint32_t* perm, const int* seg_off,
+                    int M, int n_rows, int cols, void* out, float* part, void* stream);
+/* off [B + 1] = exclusive prefix sum of num_pairs [B] */
+int pmgt_op_pair_offsets(const int64_t* num_pairs, int B, int* off, void* stream);
+/* row-major compaction of tgt_full [B, S] (-1 = not masked): rows[k] = (seq_off + b) * S + s, tids[k] = tgt_full[b, s], *count */
+int pmgt_op_nfr_compact(const int64_t* tgt_full, int B, int S, int seq_off, int64_t* rows, int64_t* tids, int* count, void* stream);
+/* graph-structure loss: h [(B + P) rows of CLS, cls_stride apart, d], off [B + 1] pair offsets, labels [P] -> logits [P],
+ * loss_part [B] (loss_i / B) and, dh != NULL, the gradient of the mean loss written to the CLS rows of dh (other rows untouched) */
+int pmgt_op_gsr(int dtype, const void* h, void* dh, int B, int S, int d, int64_t cls_stride, const int* off, const float* labels,
+                float* logits, float* loss_part, void* stream);
+/* pred [cap, sum F] in, d loss_nfr / d pred out for rows < *count; tables[m] [N + 2, F[m]] (e4m3 bytes times scales[m] when tables_f8);
+ * sse_part [pmgt_op_nfr_diff_parts(cap)][4] squared-error partials per modality */
+int pmgt_op_nfr_diff_parts(int cap);
+int pmgt_op_nfr_diff(int dtype, void* pred, const int64_t* tids, const int* count, int cap, int nf, const int* F, const void* const* tables,
+                     int tables_f8, const float* scales, float* sse_part, void* stream);
+/* out [3] = {gsr + nfr, gsr, nfr}; nfr = mean over modalities of sse_m / (count F[m]) (NaN for count 0); count_out: copy of *count */
+int pmgt_op_loss_finish(const float* gsr_part, int B, const float* sse_part, int nparts, const int* count, int nf, const int* F, int with_nfr,
+                        float* out, int* count_out, void* stream);
+/* dst[rows[k], :d] = src[k, :d] (add: +=) for k < *count */
+int pmgt_op_scatter_rows(int dtype, const void* src, const int64_t* rows, const int* count, int cap, int d, void* dst, int add, void* stream);
+/* global-norm clip (max_norm <= 0: off) + AdamW over flat fp32 buffers; step: device counter, incremented; scal [4] = clip coefficient,
+ * lr / bc1, 1 / sqrt(bc2), gradient norm; part: 1024 floats of scratch */
+int pmgt_op_adamw(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1, float b2,
+                  float eps, float max_norm, int64_t* step, float* scal, float* part, void* stream);
+/* weight mirror: per descriptor, W = params[src ..] [rows, cols] copied as dtype to mirror[dst ..], transposed to mirror[dst_t ..] and
+ * transposed with head-major columns to mirror[dst_t_hm ..] (offsets in elements, -1 = none); tile_start = first 32 x 32 tile of the
+ * descriptor in the launch, total_tiles = all of them.  desc is a host array, copied to the device by the entry (synchronous). */
+typedef struct pmgt_mirror_desc {
+    int64_t src;
+    int rows, cols;
+    int64_t dst, dst_t, dst_t_hm;
+    int hm_d, hm_dh;
+    int tile_start;
+} pmgt_mirror_desc;
+int pmgt_op_mirror(int dtype, const float* params, void* mirror, const pmgt_mirror_desc* desc, int ndesc, int total_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 OBJ = os.path.join(HERE, "csrc", "_obj")
+# host-only single-kernel entries of the test surface (include/pmgt_ops.h), outside csrc/ (bench.py fingerprints the kernel sources there)
+OPS_SOURCES = [os.path.join(HERE, "ops", "row_ops.hip")]
 HIP_SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_wsr.hip", "gemm_rowln.hip", "fp8.hip", "rowops.hip", "attention.hip", "attention_mfma.hip", "qkvc_attn.hip", "segsum.hip", "loss.hip", "optim.hip", "engine.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in architectural VGPRs (no v_accvgpr_read moves before every VALU
@@ -51,11 +53,10 @@ def build_hip(force=False):
     os.makedirs(LIB, exist_ok=True)
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "pmgt_capi.h"))
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("pmgt_capi.h", "pmgt_ops.h")]
     jobs, objs = [], []
-    for s in HIP_SOURCES:
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(OBJ, s.replace(".hip", ".o"))
+    for src in [os.path.join(CSRC, s) for s in HIP_SOURCES] + OPS_SOURCES:
+        obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
         objs.append(obj)
         if force or _newer(obj, [src] + headers):
             jobs.append([HIPCC] + HIP_FLAGS + ["-c", src, "-o", obj])

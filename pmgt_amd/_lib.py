@@ -38,6 +38,22 @@ class OutputsC(C.Structure):
     _fields_ = [("loss", C.c_void_p), ("logits", C.c_void_p), ("last_hidden", C.c_void_p), ("nfr_count", C.c_void_p)]
 
 
+class EmbedArgsC(C.Structure):
+    """pmgt_embed_args (include/pmgt_ops.h): arguments of pmgt_op_embed_mix_fwd / _bwd."""
+    _fields_ = [("dtype", C.c_int), ("phase", C.c_int), ("M", C.c_int), ("S", C.c_int), ("d", C.c_int), ("nf", C.c_int),
+                ("E", C.c_void_p), ("e_rows", C.c_void_p), ("Wa", C.c_void_p), ("ba", C.c_void_p), ("pos", C.c_void_p),
+                ("role", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float), ("a", C.c_void_p),
+                ("pre", C.c_void_p), ("stats", C.c_void_p), ("h0", C.c_void_p), ("drop_p", C.c_float), ("drop_site", C.c_uint32),
+                ("rng", C.c_void_p), ("dh0", C.c_void_p), ("dE", C.c_void_p), ("dF", C.c_void_p), ("dF_f32", C.c_int),
+                ("part", C.c_void_p)]
+
+
+class MirrorDescC(C.Structure):
+    """pmgt_mirror_desc (include/pmgt_ops.h): one weight of pmgt_op_mirror."""
+    _fields_ = [("src", C.c_int64), ("rows", C.c_int), ("cols", C.c_int), ("dst", C.c_int64), ("dst_t", C.c_int64),
+                ("dst_t_hm", C.c_int64), ("hm_d", C.c_int), ("hm_dh", C.c_int), ("tile_start", C.c_int)]
+
+
 class AdamC(C.Structure):
     _fields_ = [("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("decay", C.c_void_p),
                 ("lr", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
@@ -65,6 +81,9 @@ OPS_SYMBOLS = [
     "pmgt_op_qkvc_attention_fwd", "pmgt_op_attention_bwd_wgrad", "pmgt_op_attention_bwd_wgrad_parts",
     "pmgt_op_quant_rows_e4m3", "pmgt_op_gemm_nt_f8", "pmgt_op_gemm_tn_f8", "pmgt_op_qkvc_attention_fwd_f8",
     "pmgt_launch_trace_reset", "pmgt_launch_trace_count", "pmgt_op_seg_sort", "pmgt_op_seg_sort_temp_bytes", "pmgt_op_clock_probe", "pmgt_op_qkvc_attention_fwd_ex", "pmgt_op_attention_bwd_wgrad_vc2_parts",
+    "pmgt_op_embed_mix_fwd", "pmgt_op_embed_mix_bwd", "pmgt_op_embed_part_elems", "pmgt_op_embed_bwd_parts", "pmgt_op_pos_role_finish",
+    "pmgt_op_seg_part_elems", "pmgt_op_seg_sum", "pmgt_op_pair_offsets", "pmgt_op_nfr_compact", "pmgt_op_gsr", "pmgt_op_nfr_diff_parts",
+    "pmgt_op_nfr_diff", "pmgt_op_loss_finish", "pmgt_op_scatter_rows", "pmgt_op_adamw", "pmgt_op_mirror",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -161,6 +180,23 @@ def hip():
     L.pmgt_op_gemm_nt_f8.argtypes = [vp, i64, vp, vp, f, vp, i64, vp, vp, i64, i, i, i, vp, vp, vp]
     L.pmgt_op_gemm_tn_f8.argtypes = [vp, i64, vp, i64, f, vp, i, i, i, vp, vp, i, vp, vp]
     L.pmgt_op_qkvc_attention_fwd_f8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, u32, u32, vp, vp]
+    L.pmgt_op_embed_mix_fwd.argtypes = [C.POINTER(EmbedArgsC), vp]
+    L.pmgt_op_embed_mix_bwd.argtypes = [C.POINTER(EmbedArgsC), vp]
+    L.pmgt_op_embed_part_elems.argtypes = [i, i]
+    L.pmgt_op_embed_bwd_parts.argtypes = [i]
+    L.pmgt_op_pos_role_finish.argtypes = [vp, i, i, i, vp, vp, i, vp]
+    L.pmgt_op_seg_part_elems.argtypes = [i, i]
+    L.pmgt_op_seg_part_elems.restype = i64
+    L.pmgt_op_seg_sum.argtypes = [i, i, vp, i64, vp, vp, vp, i, i, i, vp, vp, vp]
+    L.pmgt_op_pair_offsets.argtypes = [vp, i, vp, vp]
+    L.pmgt_op_nfr_compact.argtypes = [vp, i, i, i, vp, vp, vp, vp]
+    L.pmgt_op_gsr.argtypes = [i, vp, vp, i, i, i, i64, vp, vp, vp, vp, vp]
+    L.pmgt_op_nfr_diff_parts.argtypes = [i]
+    L.pmgt_op_nfr_diff.argtypes = [i, vp, vp, vp, i, i, C.POINTER(i), C.POINTER(vp), i, c_f32p, vp, vp]
+    L.pmgt_op_loss_finish.argtypes = [vp, i, vp, i, vp, i, C.POINTER(i), i, vp, vp, vp]
+    L.pmgt_op_scatter_rows.argtypes = [i, vp, vp, vp, i, i, vp, i, vp]
+    L.pmgt_op_adamw.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, vp]
+    L.pmgt_op_mirror.argtypes = [i, vp, vp, C.POINTER(MirrorDescC), i, i, vp]
     _hip = L
     return L
 

@@ -8,6 +8,7 @@ _build.build_hip()
 obj = out + ".o"
 subprocess.run([_build.HIPCC] + _build.HIP_FLAGS + flags + ["-c", os.path.join(_build.CSRC, src), "-o", obj], check=True)
 objs = [obj if s == src else os.path.join(_build.OBJ, s.replace(".hip", ".o")) for s in _build.HIP_SOURCES]
+objs += [os.path.join(_build.OBJ, os.path.basename(s).replace(".hip", ".o")) for s in _build.OPS_SOURCES]
 subprocess.run([_build.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs, check=True)
 os.remove(obj)
 print(out)
