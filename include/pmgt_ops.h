@@ -181,6 +181,19 @@ int pmgt_op_seg_sum(int in_dtype, int out_dtype, const void* src, int64_t ld, co
 int pmgt_op_pair_offsets(const int64_t* num_pairs, int B, int* off, void* stream);
 /* row-major compaction of tgt_full [B, S] (-1 = not masked): rows[k] = (seq_off + b) * S + s, tids[k] = tgt_full[b, s], *count */
 int pmgt_op_nfr_compact(const int64_t* tgt_full, int B, int S, int seq_off, int64_t* rows, int64_t* tids, int* count, void* stream);
+/* NFR masking with the device RNG (site ids 5 and 6 of layer -1): ids [B, S] -> masked_ids [B, S], tgt_full [B, S] (-1 = not masked).
+ * Position 0 and padding (id 0) are never touched; replaced ids lie in [2, n_nodes + 2).  Integer work: bit-exact against a restatement. */
+int pmgt_op_nfr_generate(const int64_t* ids, int B, int S, int n_nodes, float random_ratio, float mask_ratio, const uint64_t* rng,
+                         int64_t* masked_ids, int64_t* tgt_full, void* stream);
+/* rows the loss reads from the last layer, in compact order: CLS rows of the B targets (b * S), of the P pairs ((B + p) * S), then
+ * nfr_rows[0 .. *nfr_count); *count = B + P + *nfr_count.  rows: capacity B + P + B * max(S - 1, 1), which *nfr_count must not exceed
+ * (less B + P).  inv (optional, [n_tokens] ints): token row -> compact row, -1 elsewhere; every listed row must be < n_tokens. */
+int pmgt_op_build_need_rows(int B, int P, int S, const int64_t* nfr_rows, const int* nfr_count, int64_t* rows, int* count, int* inv,
+                            int64_t n_tokens, void* stream);
+/* Keep decisions of the dropout RNG, out [rows, cols] bytes (1 = kept): what every dropout-bearing kernel draws for element (row, col) of
+ * site `site` at rng = {seed, step} (csrc/common.h: one hash pair per (row, col / 4), 16-bit lane col % 4 against (uint32)(p 2^32) >> 16);
+ * p <= 0: all kept, rng not read. */
+int pmgt_op_dropout_keep(const uint64_t* rng, float p, uint32_t site, int rows, int cols, uint8_t* out, void* stream);
 /* graph-structure loss: h [(B + P) rows of CLS, cls_stride apart, d], off [B + 1] pair offsets, labels [P] -> logits [P],
  * loss_part [B] (loss_i / B) and, dh != NULL, the gradient of the mean loss written to the CLS rows of dh (other rows untouched) */
 int pmgt_op_gsr(int dtype, const void* h, void* dh, int B, int S, int d, int64_t cls_stride, const int* off, const float* labels,

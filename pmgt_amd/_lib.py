@@ -92,7 +92,7 @@ OPS_SYMBOLS = [
     "pmgt_op_embed_mix_fwd", "pmgt_op_embed_mix_bwd", "pmgt_op_embed_part_elems", "pmgt_op_embed_bwd_parts", "pmgt_op_pos_role_finish",
     "pmgt_op_seg_part_elems", "pmgt_op_seg_sum", "pmgt_op_pair_offsets", "pmgt_op_nfr_compact", "pmgt_op_gsr", "pmgt_op_nfr_diff_parts",
     "pmgt_op_nfr_diff", "pmgt_op_loss_finish", "pmgt_op_scatter_rows", "pmgt_op_adamw", "pmgt_op_mirror",
-    "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule",
+    "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -209,6 +209,9 @@ def hip():
     L.pmgt_op_adamw_scheduled.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), vp]
     L.pmgt_op_lr_schedule.argtypes = [C.POINTER(LrScheduleC), f, i64, i, vp, vp]
     L.pmgt_op_mirror.argtypes = [i, vp, vp, C.POINTER(MirrorDescC), i, i, vp]
+    L.pmgt_op_nfr_generate.argtypes = [vp, i, i, i, f, f, vp, vp, vp, vp]
+    L.pmgt_op_build_need_rows.argtypes = [i, i, i, vp, vp, vp, vp, vp, i64, vp]
+    L.pmgt_op_dropout_keep.argtypes = [vp, f, u32, i, i, vp, vp]
     _hip = L
     return L
 

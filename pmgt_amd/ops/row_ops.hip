@@ -60,6 +60,16 @@ int pmgt_op_pair_offsets(const int64_t* num_pairs, int B, int* off, void* stream
 int pmgt_op_nfr_compact(const int64_t* tgt_full, int B, int S, int seq_off, int64_t* rows, int64_t* tids, int* count, void* stream) {
     return nfr_compact(tgt_full, B, S, seq_off, rows, tids, count, (hipStream_t)stream);
 }
+int pmgt_op_nfr_generate(const int64_t* ids, int B, int S, int n_nodes, float random_ratio, float mask_ratio, const uint64_t* rng,
+                         int64_t* masked_ids, int64_t* tgt_full, void* stream) {
+    PMGT_CHECK(ids && rng && masked_ids && tgt_full && B > 0 && S > 0 && n_nodes > 0, -2, "pmgt_op_nfr_generate: NULL or empty argument");
+    return nfr_generate(ids, B, S, n_nodes, random_ratio, mask_ratio, rng, masked_ids, tgt_full, (hipStream_t)stream);
+}
+int pmgt_op_build_need_rows(int B, int P, int S, const int64_t* nfr_rows, const int* nfr_count, int64_t* rows, int* count, int* inv,
+                            int64_t n_tokens, void* stream) {
+    PMGT_CHECK(nfr_rows && nfr_count && rows && count && B > 0 && P >= 0 && S > 0, -2, "pmgt_op_build_need_rows: NULL or empty argument");
+    return build_need_rows(B, P, S, nfr_rows, nfr_count, rows, count, (hipStream_t)stream, inv, n_tokens);
+}
 int pmgt_op_gsr(int dtype, const void* h, void* dh, int B, int S, int d, int64_t cls_stride, const int* off, const float* labels,
                 float* logits, float* loss_part, void* stream) {
     GsrArgs g;

@@ -1,9 +1,11 @@
 """Per-kernel parity tests: the GEMM, attention, LayerNorm, column-sum, token-sort and fp8 kernels are called through the
 C ABI (pmgt_op_*) and compared with a plain torch fp32/fp64 CPU computation of the same op (for attention: the oracle's
 restatement of pmgt/pmgt/modeling_pmgt.py:420-534 with autograd for the backward).  The embedding, segment-sum, loss-head
-and optimizer kernels have theirs in test_rowops_gpu.py.  Reached only end to end: the NFR masking RNG (nfr_generate,
-checked statistically in test_fullsize_gpu.py), the batch copies (multi_copy), the compacted-row list of the last layer
-(build_need_rows), the RNG step counter (advance_rng) and the dtype casts."""
+and optimizer kernels have theirs in test_rowops_gpu.py; the dropout hash, the NFR masking RNG (nfr_generate) and the
+compacted-row list of the last layer (build_need_rows) are compared bit for bit with a numpy restatement in
+test_dropout_rng_gpu.py, and every kernel here runs with dropout ON against fp64 with restated masks in
+test_dropout_ops_gpu.py.  Reached only end to end: the batch copies (multi_copy), the RNG step counter (advance_rng) and
+the dtype casts."""
 import ctypes as C
 import math
 
