@@ -388,6 +388,70 @@ class Engine:
             return
         _lib.check(self.lib.pmgt_optimizer_step(self.h, C.byref(tc), C.byref(ac), _stream()))
 
+    # ---- everything a training step mutates, as plain data (Trainer.state_dict / pmgt_amd.io carry it to disk) --------------
+    def config_key(self) -> dict:
+        """The configuration fields that decide the parameter layout and the kernels' arithmetic."""
+        c = self.config
+        return dict(hidden_size=int(c.hidden_size), num_hidden_layers=int(c.num_hidden_layers),
+                    num_attention_heads=int(c.num_attention_heads), intermediate_size=int(c.intermediate_size),
+                    feat_hidden_sizes=[int(f) for f in c.feat_hidden_sizes], max_position_embeddings=int(c.max_position_embeddings),
+                    layer_norm_eps=float(c.layer_norm_eps), beta=float(c.beta), hidden_dropout_prob=float(c.hidden_dropout_prob),
+                    attention_probs_dropout_prob=float(c.attention_probs_dropout_prob))
+
+    def options_set(self) -> List[str]:
+        """Names of the path options that are not at their default (every default is off)."""
+        return [k for k in _lib.OPT if self.get_option(k)]
+
+    def training_state(self) -> dict:
+        """Host copies of the flat parameters, both Adam moments, the optimizer-step counter and the dropout / NFR counter, with what
+        a loader needs to refuse a state that does not fit this engine (parameter count, dtype, configuration) and the path options
+        in force.  The .cpu() copies are ordered behind the steps launched so far on the current stream."""
+        self.ensure_optimizer_state()
+        seed, step = (int(x) for x in self.rng_state.cpu())
+        return dict(n_params=self.n_params, dtype=self.dtype_name, config=self.config_key(), params=self.params.cpu(),
+                    exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), opt_step=int(self.opt_step.cpu()),
+                    rng_state={"seed": seed, "step": step}, options=self.options_set())
+
+    def check_training_state(self, state: dict) -> None:
+        """Refuses, with the reason, a state whose shape is not this engine's."""
+        if int(state["n_params"]) != self.n_params:
+            raise ValueError(f"training state holds {int(state['n_params'])} parameters, this engine has {self.n_params}")
+        if state.get("dtype") is not None and state["dtype"] != self.dtype_name:
+            raise ValueError(f"training state was written by a {state['dtype']!r} engine, this engine is {self.dtype_name!r} "
+                             "(the moments of one precision do not continue the curve of another)")
+        mine = self.config_key()
+        for k, v in (state.get("config") or {}).items():
+            if k in mine and mine[k] != v:
+                raise ValueError(f"training state was written with config.{k} = {v!r}, this engine has {mine[k]!r}")
+        for k in ("params", "exp_avg", "exp_avg_sq"):
+            if tuple(state[k].shape) != (self.n_params,):
+                raise ValueError(f"training state: {k} has shape {tuple(state[k].shape)}, expected ({self.n_params},)")
+
+    def load_training_state(self, state: dict) -> None:
+        """Writes `state` (training_state()'s layout) INTO the existing device tensors: nothing is rebound, so a captured step, which
+        addresses these buffers by pointer, stays valid and continues from the loaded state.  Path options are restored before the
+        parameters are written (state["options"] = None leaves them alone); the LayerNorm-carrier check that follows every bulk
+        parameter load then only moves the engine off the recorded options when the loaded parameters themselves demand stored
+        LayerNorm inputs -- with the usual warning.  rng_state = None keeps this engine's."""
+        self.check_training_state(state)
+        self.ensure_optimizer_state()
+        if state.get("options") is not None:
+            want = set(state["options"])
+            unknown = want - set(_lib.OPT)
+            if unknown:
+                raise ValueError(f"training state names path options this library does not have: {sorted(unknown)}")
+            for k in _lib.OPT:
+                if self.get_option(k) != (k in want):
+                    self.set_option(k, k in want)
+        self.params.copy_(state["params"].to(torch.float32))
+        self.exp_avg.copy_(state["exp_avg"].to(torch.float32))
+        self.exp_avg_sq.copy_(state["exp_avg_sq"].to(torch.float32))
+        self.opt_step.fill_(int(state["opt_step"]))
+        rng = state.get("rng_state")
+        if rng is not None:
+            self.rng_state.copy_(torch.tensor([int(rng["seed"]), int(rng["step"])], dtype=torch.int64))
+        self.check_layernorm_carrier()
+
     def set_grad_ready_hook(self, fn=None):
         """fn(offset, numel) is called on the launching thread, in stream order, as soon as grads[offset: offset + numel]
         is final during a backward pass (buckets: NFR head, layers L-1 .. 0, embeddings); None removes the hook.

@@ -153,6 +153,222 @@ def load_checkpoint(model, path_or_dict, prefix: str = "net.", strict: bool = Tr
     return model.load_state_dict(sd, strict=strict)
 
 
+# ---- full training checkpoints (weights + optimizer + counters): a superset of save_checkpoint's file, under a Lightning checkpoint's keys --------
+FORMAT_VERSION = 1
+NO_DECAY = ("bias", "LayerNorm.weight")              # pmgt/base_trainer.py:38
+_EMB_ORDER = ("position_embeddings", "role_embeddings", "feat_linear", "attention", "LayerNorm")
+_LAYER_ORDER = ("attention.self.query", "attention.self.key", "attention.self.value", "attention.self.ctx_attention",
+                "attention.output.dense", "attention.output.LayerNorm", "intermediate.dense", "output.dense", "output.LayerNorm")
+
+
+def _reference_position(name: str):
+    """Sort key of a trainable parameter in the reference's `named_parameters()` order (pmgt/pmgt/models.py:31-47 registers bert, then
+    nfr_loss, then the frozen feat_embeddings; inside a module weight comes before bias).  The engine's flat layout groups a layer's
+    Q|K|V|C weights and the partial-sum neighbours of the LayerNorms, so its entry order is NOT this order."""
+    stem, leaf = name.rsplit(".", 1)
+    wb = ("weight", "bias").index(leaf)
+    if stem.startswith("bert.embeddings."):
+        parts = stem[len("bert.embeddings."):].split(".")
+        return (0, 0, _EMB_ORDER.index(parts[0]), int(parts[1]) if parts[0] == "feat_linear" else 0, wb)
+    if stem.startswith("bert.encoder.layer."):
+        layer, rest = stem[len("bert.encoder.layer."):].split(".", 1)
+        return (1, int(layer), _LAYER_ORDER.index(rest), 0, wb)
+    if stem.startswith("nfr_loss.projections."):
+        return (2, 0, 0, int(stem[len("nfr_loss.projections."):]), wb)
+    raise ValueError(f"{name!r} is not a trainable parameter of the reference's PMGT")
+
+
+def optimizer_param_groups(names) -> Tuple[list, list]:
+    """The two groups `get_optimizer` builds (pmgt/base_trainer.py:35-59) over the TRAINABLE parameter names: ([decayed], [not decayed:
+    any of "bias", "LayerNorm.weight" in the name]), each in named_parameters() order.  torch.optim.Optimizer.state_dict() numbers the
+    parameters by their running index across the groups: group 0 takes 0 .. len - 1, group 1 continues.  The frozen feat_embeddings are
+    left out here; a file of the reference lists them at the tail of group 0 (get_optimizer does not filter on requires_grad) with no
+    state: optimizer_state_to_flat steps over them."""
+    ordered = sorted(names, key=_reference_position)
+    nd = lambda n: any(k in n for k in NO_DECAY)
+    return [n for n in ordered if not nd(n)], [n for n in ordered if nd(n)]
+
+
+def flat_to_optimizer_state(entries, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int, lr: float, weight_decay: float,
+                            betas=(0.9, 0.999), eps: float = 1e-8, current_lr: Optional[float] = None) -> dict:
+    """Flat CPU moments (the engine's layout: `entries` = [{name, offset, numel, shape}]) -> torch.optim.Optimizer.state_dict() form of the
+    reference's DenseSparseAdamW: per parameter {"step", "exp_avg", "exp_avg_sq"} (pmgt/optimizers.py:187-201).  current_lr: the rate a
+    LambdaLR has written into the groups (then `lr` is their "initial_lr")."""
+    by = {e["name"]: e for e in entries}
+    decay, no_decay = optimizer_param_groups(by)
+    state = {}
+    for i, n in enumerate(decay + no_decay):
+        e = by[n]
+        sl = slice(e["offset"], e["offset"] + e["numel"])
+        state[i] = {"step": int(step), "exp_avg": exp_avg[sl].reshape(tuple(e["shape"])).clone(),
+                    "exp_avg_sq": exp_avg_sq[sl].reshape(tuple(e["shape"])).clone()}
+    groups = []
+    for lo, members, wd in ((0, decay, float(weight_decay)), (len(decay), no_decay, 0.0)):
+        g = {"params": list(range(lo, lo + len(members))), "weight_decay": wd, "lr": float(lr if current_lr is None else current_lr),
+             "betas": tuple(float(b) for b in betas), "eps": float(eps)}
+        if current_lr is not None:
+            g["initial_lr"] = float(lr)
+        groups.append(g)
+    return {"state": state, "param_groups": groups}
+
+
+def optimizer_state_to_flat(entries, opt_state: dict, n_params: int, n_frozen: int = 0):
+    """Inverse of flat_to_optimizer_state: (exp_avg, exp_avg_sq, step) with the elements no entry covers (alignment gaps, never
+    touched by a step) zero.  n_frozen: how many frozen parameters a file of the reference may list behind the decayed ones in group 0.
+    A parameter without state (the reference creates it at the first step that sees a gradient) keeps zero moments."""
+    by = {e["name"]: e for e in entries}
+    decay, no_decay = optimizer_param_groups(by)
+    groups = opt_state["param_groups"]
+    if len(groups) != 2:
+        raise ValueError(f"optimizer state has {len(groups)} parameter groups, the reference's get_optimizer builds 2")
+    ids0, ids1 = list(groups[0]["params"]), list(groups[1]["params"])
+    if len(ids0) == len(decay) + n_frozen and n_frozen:
+        ids0 = ids0[:len(decay)]
+    if len(ids0) != len(decay) or len(ids1) != len(no_decay):
+        raise ValueError(f"optimizer state lists {len(groups[0]['params'])} + {len(ids1)} parameters in its groups, this model has "
+                         f"{len(decay)} decayed (+ {n_frozen} frozen tables in a file of the reference) + {len(no_decay)} undecayed")
+    m, v = torch.zeros(n_params, dtype=torch.float32), torch.zeros(n_params, dtype=torch.float32)
+    step = 0
+    for idx, n in zip(ids0 + ids1, decay + no_decay):
+        st = opt_state["state"].get(idx)
+        if not st:
+            continue
+        e = by[n]
+        for buf, key in ((m, "exp_avg"), (v, "exp_avg_sq")):
+            t = torch.as_tensor(st[key]).to(torch.float32)
+            if t.numel() != e["numel"]:
+                raise ValueError(f"optimizer state {idx} ({n}): {key} has {t.numel()} elements, the parameter has {e['numel']}")
+            buf[e["offset"]: e["offset"] + e["numel"]] = t.reshape(-1)
+        step = max(step, int(st["step"]))
+    return m, v, step
+
+
+def _callback(callbacks: dict, prefix: str) -> Optional[dict]:
+    """Lightning keys a callback's state by its class name followed by its arguments (pmgt/base_trainer.py:105-108 looks one up the same way)."""
+    for k, v in (callbacks or {}).items():
+        if isinstance(k, str) and k.startswith(prefix):
+            return v
+    return None
+
+
+def training_checkpoint(state_dict: Dict[str, torch.Tensor], entries, trainer_sd: dict, epoch: int = 0, callbacks: Optional[dict] = None,
+                        fit: Optional[dict] = None, **extra) -> dict:
+    """The checkpoint as plain data (pure: CPU tensors in, a dict out).  `state_dict`: the weights under their `net.` keys, what
+    save_checkpoint writes; `trainer_sd`: Trainer.state_dict().  Keys of a Lightning checkpoint of the reference, plus the block
+    "pmgt_amd" for what that format has no place for."""
+    est, hp = trainer_sd["engine"], trainer_sd["hyper_parameters"]
+    steps = int(est["opt_step"])
+    current = None
+    if hp["schedule"] is not None:
+        from .schedule import lr_lambda
+        kind, W, T = hp["schedule"]
+        current = hp["lr"] * lr_lambda(kind, W, T, hp["lr"])(steps)
+    opt = flat_to_optimizer_state(entries, est["exp_avg"], est["exp_avg_sq"], steps, hp["lr"], hp["weight_decay"], hp["betas"], hp["eps"], current)
+    sched = []
+    if hp["schedule"] is not None:
+        sched = [{"base_lrs": [hp["lr"]] * 2, "last_epoch": steps, "_step_count": steps + 1, "verbose": False,
+                  "_get_lr_called_within_step": False, "_last_lr": [current] * 2, "lr_lambdas": [None, None]}]
+    private = {"format_version": FORMAT_VERSION, "rng_state": dict(est["rng_state"]), "opt_steps": int(trainer_sd["opt_steps"]),
+               "options": list(est["options"]), "pipeline_step": int(trainer_sd["pipeline_step"]), "dtype": est["dtype"],
+               "n_params": int(est["n_params"]), "config": dict(est["config"]), "hyper_parameters": dict(hp),
+               "accumulate_grad_batches": int(trainer_sd["accumulate_grad_batches"]), "fit": fit}
+    return {"state_dict": state_dict, "optimizer_states": [opt], "lr_schedulers": sched, "global_step": steps, "epoch": int(epoch),
+            "callbacks": dict(callbacks or {}), "pmgt_amd": private, **extra}
+
+
+def training_state_from_checkpoint(ck: dict, entries, n_params: int, n_frozen: int = 0, prefix: str = "net.") -> dict:
+    """A checkpoint (ours, or a Lightning file of the reference as read_checkpoint returns it) -> Trainer.state_dict() layout.  Pure.
+    Without the "pmgt_amd" block the weights, the moments and the step count are still there; what the reference does not record comes
+    back as None (rng_state, options, dtype) or absent (clip value, schedule, accumulation factor), and Trainer.load_state_dict keeps its
+    own for those."""
+    sd = ck["state_dict"]
+    if any(k.startswith(prefix) for k in sd):
+        sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    params = torch.zeros(n_params, dtype=torch.float32)
+    for e in entries:
+        if e["name"] not in sd:
+            raise ValueError(f"checkpoint has no weights for {e['name']!r}")
+        t = torch.as_tensor(sd[e["name"]]).to(torch.float32)
+        if t.numel() != e["numel"]:
+            raise ValueError(f"checkpoint: {e['name']} has shape {tuple(t.shape)}, this model's has {tuple(e['shape'])}")
+        params[e["offset"]: e["offset"] + e["numel"]] = t.reshape(-1)
+    m, v, step = optimizer_state_to_flat(entries, ck["optimizer_states"][0], n_params, n_frozen)
+    pv = ck.get("pmgt_amd")
+    if pv is not None:
+        if int(pv.get("format_version", 0)) > FORMAT_VERSION:
+            raise ValueError(f"checkpoint format version {pv['format_version']} is newer than this library's ({FORMAT_VERSION})")
+        eng = dict(n_params=int(pv["n_params"]), dtype=pv["dtype"], config=dict(pv["config"]), rng_state=dict(pv["rng_state"]), options=list(pv["options"]))
+        out = {"opt_steps": int(pv["opt_steps"]), "pipeline_step": int(pv["pipeline_step"]), "hyper_parameters": dict(pv["hyper_parameters"]),
+               "accumulate_grad_batches": int(pv["accumulate_grad_batches"])}
+    else:
+        g0 = ck["optimizer_states"][0]["param_groups"][0]
+        eng = dict(n_params=n_params, dtype=None, config=None, rng_state=None, options=None)
+        hp = {"lr": float(g0.get("initial_lr", g0["lr"])), "weight_decay": float(g0["weight_decay"])}
+        if "betas" in g0:
+            hp["betas"] = tuple(float(b) for b in g0["betas"])
+        if "eps" in g0:
+            hp["eps"] = float(g0["eps"])
+        out = {"opt_steps": step, "hyper_parameters": hp}
+    eng.update(params=params, exp_avg=m, exp_avg_sq=v, opt_step=step)
+    out["engine"] = eng
+    return out
+
+
+def atomic_save(obj, path) -> None:
+    """torch.save to a temporary name in the same directory, then one rename: a kill at any point leaves the previous file whole."""
+    path = os.fspath(path)
+    tmp = f"{path}.tmp.{os.getpid()}"
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+
+
+def _engine_of(model_or_engine):
+    return getattr(model_or_engine, "engine", model_or_engine)
+
+
+def save_training_checkpoint(model_or_engine, trainer, path, prefix: str = "net.", **extra):
+    """save_checkpoint's file plus everything a resume needs (training_checkpoint above).  `model_or_engine`: a PMGT module (its
+    state_dict, frozen tables and id buffers included, exactly what save_checkpoint writes) or a bare Engine (its trainable entries: the
+    frozen tables are the caller's input to set_tables).  Only at an optimizer-step boundary (Trainer.state_dict).  Under data
+    parallelism only rank 0 writes -- the replicas are identical -- and the returned dict is None elsewhere."""
+    from .parallel import world
+    if trainer.world_size > 1 and world()[0] != 0:
+        if trainer._micro != 0:
+            trainer.state_dict()                   # raises the same error on every rank
+        return None
+    eng = _engine_of(model_or_engine)
+    if eng is not trainer.engine:
+        raise ValueError("save_training_checkpoint: the trainer drives another engine than the one passed")
+    tsd = trainer.state_dict()
+    if model_or_engine is eng:
+        sd = {prefix + e["name"]: tsd["engine"]["params"][e["offset"]: e["offset"] + e["numel"]].reshape(tuple(e["shape"])).clone() for e in eng.entries}
+    else:
+        sd = to_reference_state_dict(model_or_engine, prefix)
+    ck = training_checkpoint(sd, eng.entries, tsd, **extra)
+    atomic_save(ck, path)
+    return ck
+
+
+def load_training_checkpoint(model_or_engine, trainer, path_or_dict, strict: bool = True, prefix: str = "net.") -> dict:
+    """Restores weights, moments, counters, RNG state and path options from a file of save_training_checkpoint -- or the weights,
+    moments and step count from a Lightning checkpoint of the reference -- through Trainer.load_state_dict (in place; see there for
+    `strict`).  Every rank loads.  Returns the checkpoint as read (callbacks, epoch, the "pmgt_amd" block)."""
+    ck = read_checkpoint(path_or_dict) if isinstance(path_or_dict, (str, os.PathLike)) else path_or_dict
+    eng = _engine_of(model_or_engine)
+    if eng is not trainer.engine:
+        raise ValueError("load_training_checkpoint: the trainer drives another engine than the one passed")
+    trainer.load_state_dict(training_state_from_checkpoint(ck, eng.entries, eng.n_params, eng.n_feats, prefix), strict=strict)
+    if model_or_engine is not eng and hasattr(model_or_engine, "set_features"):
+        tabs = [ck["state_dict"].get(f"{prefix}feat_embeddings.{i}.weight") for i in range(eng.n_feats)]
+        if all(t is not None for t in tabs):
+            model_or_engine.set_features(tabs)
+    return ck
+
+
 # ---- exported embeddings ------------------------------------------------------------------------------------------
 def save_embeddings(path: str, emb: np.ndarray):
     """[N, d] fp32 in node-id order (pmgt/base_trainer.py:403-405: np.save(args.inference_result_path, predictions))."""

@@ -35,7 +35,7 @@ class Trainer:
         it, evaluated ON THE DEVICE by the fused step (pmgt_amd.schedule states the multipliers).  It advances once per optimizer
         step, so gradient accumulation and data parallelism (every rank's counter is equal) need nothing more, and a captured
         step / run_live(graphs=True) follows it with no re-capture.  The schedule's position is `engine.opt_step`, the same
-        device counter as Adam's bias corrections: setting that counter, as a resume does, moves both together."""
+        device counter as Adam's bias corrections: setting that counter, as a resume does (load_state_dict), moves both together."""
         self.engine = engine
         self.scheduler_type, self.num_warmup_steps, self.num_training_steps = scheduler_type, num_warmup_steps, num_training_steps
         if scheduler_type is not None:
@@ -56,6 +56,9 @@ class Trainer:
         # step is captured)
         self.check_carrier_every = int(check_carrier_every)
         self._opt_steps = 0
+        # global index of the next step of the live input pipeline (run_live / fit): the sampler streams of step g start at counter
+        # g * batch_size, so a call that starts where the last one ended draws no stream twice.  Part of state_dict().
+        self.pipeline_step = 0
         # world_size > 1: per-bucket all-reduce started from the engine's gradient-ready hook while the backward pass of
         # the earlier layers is still running (overlap_allreduce=False: ONE blocking all-reduce after the backward pass)
         self._exchange = None
@@ -130,6 +133,13 @@ class Trainer:
             self._micro = 0
         return loss
 
+    def flush_accumulation(self):
+        """Steps the optimizer on an accumulation window that the end of an epoch cut short (Lightning steps on the last batch of an epoch
+        whatever the window holds; the gradients keep their 1 / accumulate_grad_batches scale).  Nothing to do at a window boundary."""
+        if self._micro:
+            self.optimizer_step()
+            self._micro = 0
+
     # ---- the whole step as ONE hipGraph ---------------------------------------------------------------------------
     def capture_step(self, batch, warmup: int = 2, capture_error_mode: str = "global"):
         """Captures train_step(batch) (mask -> forward -> losses -> backward -> clip + AdamW) into a hipGraph and
@@ -199,16 +209,76 @@ class Trainer:
             torch.cuda.synchronize(self.engine.device)
             reps.clear()
 
+    # ---- full training state: what a resume needs beyond the weights ---------------------------------------------------------
+    HYPER_NAMES = ("lr", "weight_decay", "betas", "eps", "max_grad_norm", "random_node_ratio", "mask_node_ratio", "schedule")
+
+    def hyper_parameters(self) -> dict:
+        """_hyper_key() by name: what decides the curve besides the data (the schedule as its descriptor (type, W, T) or None)."""
+        return dict(zip(self.HYPER_NAMES, self._hyper_key()))
+
+    def state_dict(self) -> dict:
+        """Everything a training step mutates (Engine.training_state(): flat parameters, both Adam moments, opt_step, rng_state, path
+        options) plus the trainer's own counters: the phase of the LayerNorm-carrier guard (_opt_steps), the pipeline position, the
+        hyper-parameters and the accumulation factor the state was produced with.  Only at an optimizer-step boundary: between the
+        micro-batches of one accumulation window the gradient buffer is part of the state, and it is not saved."""
+        if self._micro != 0:
+            raise RuntimeError(f"Trainer.state_dict(): {self._micro} of {self.accum} micro-batches of the current accumulation window have "
+                               "run; the training state can only be saved at an optimizer-step boundary (_micro == 0)")
+        return {"engine": self.engine.training_state(), "opt_steps": int(self._opt_steps), "pipeline_step": int(self.pipeline_step),
+                "hyper_parameters": self.hyper_parameters(), "accumulate_grad_batches": int(self.accum)}
+
+    def hyper_mismatches(self, sd: dict) -> list:
+        """[(name, checkpoint value, trainer value)] over the hyper-parameters and the accumulation factor `sd` records."""
+        mine = dict(self.hyper_parameters(), accumulate_grad_batches=int(self.accum))
+        theirs = dict(sd.get("hyper_parameters") or {})
+        if sd.get("accumulate_grad_batches") is not None:
+            theirs["accumulate_grad_batches"] = int(sd["accumulate_grad_batches"])
+        norm = lambda v: tuple(norm(x) for x in v) if isinstance(v, (list, tuple)) else v
+        return [(k, norm(theirs[k]), norm(mine[k])) for k in mine if k in theirs and norm(theirs[k]) != norm(mine[k])]
+
+    def load_state_dict(self, sd: dict, strict: bool = True) -> None:
+        """Continues from `sd` (state_dict()'s layout).  The tensors are written INTO the engine's existing buffers, so the steps
+        run_live(graphs=True) captured stay valid and replay from the loaded state -- unless `sd` was produced under other
+        hyper-parameters or engine path options than the live ones: those are frozen into the captured launches, so the captures are
+        dropped first (run_live records them again).  strict: a hyper-parameter or accumulation factor that differs raises a
+        ValueError naming both values (a silently different curve is worse); strict=False takes the checkpoint's tensors and counters
+        and keeps this trainer's hyper-parameters.  A state of another parameter count, engine dtype or configuration is refused
+        either way, before anything is written."""
+        eng = self.engine
+        est = sd["engine"]
+        eng.check_training_state(est)
+        bad = self.hyper_mismatches(sd)
+        options_differ = est.get("options") is not None and set(est["options"]) != set(eng.options_set())
+        if (bad or options_differ) and self.__dict__.get("_live_replays"):
+            import gc
+            self.drop_captured_steps()
+            gc.collect()
+        if bad and strict:
+            raise ValueError("Trainer.load_state_dict: the checkpoint was written under other hyper-parameters: " +
+                             "; ".join(f"{k}: checkpoint {a!r}, trainer {b!r}" for k, a, b in bad) +
+                             " (strict=False loads the tensors and counters and keeps the trainer's values)")
+        eng.load_training_state(est)
+        if est.get("rng_state") is None:
+            # a checkpoint of the reference has no dropout counter: this engine's seed, at the step a run of ours would have reached
+            eng.rng_state[1] = int(est["opt_step"]) * self.accum
+        self._opt_steps = int(sd.get("opt_steps", est["opt_step"]))
+        self.pipeline_step = int(sd.get("pipeline_step", int(est["opt_step"]) * self.accum))
+        self._micro = 0
+
     # ---- live input pipeline: threaded C++ MCNSampling -> pinned buffers -> side-stream H2D ------------
     def run_live(self, sampler, node_ids: np.ndarray, batch_size: int, steps: int, threads: int = 8, depth: int = 3,
-                 stall_timeout_s: float = 120.0, graphs: bool = False):
+                 stall_timeout_s: float = 120.0, graphs: bool = False, first_step: int = 0, base_seed: int = 7):
         """Training steps fed by the live host pipeline (the reference: a DataLoader over PMGTDataset, pmgt/pmgt/trainer.py:84-105):
         ONE producer thread runs the threaded C++ sampler into a pinned host slot and issues the slot's async H2D copies on a
         side stream into that slot's PRE-ALLOCATED device buffers (no allocator call, no record_stream on the step's path); the
         launch thread orders each step behind its copies with one event and hands the slot back with a completion event.
         graphs=True: the step is captured once per slot over that slot's device buffers (train-mode batches have a fixed shape: every
         target brings max_total_samples pairs) and replayed -- ONE launch per step, so a launch thread that loses its CPU for a
-        millisecond in the middle of a step's ~70 launches (a shared host) no longer shows up as GPU idle time inside the step."""
+        millisecond in the middle of a step's ~70 launches (a shared host) no longer shows up as GPU idle time inside the step.
+        first_step: global index of this call's first step; the sampler streams of step i start at counter (first_step + i) *
+        batch_size, so `first_step=trainer.pipeline_step` continues where the previous call (or a loaded checkpoint) ended instead of
+        drawing its contexts and negatives again.  The default 0 restarts the streams, as every call did before the keyword existed.
+        The slice of `node_ids` a step takes stays relative to the call.  `pipeline_step` is left at first_step + the steps run."""
         eng = self.engine
         dev = eng.device
         copy_stream = torch.cuda.Stream(device=dev)
@@ -231,7 +301,7 @@ class Trainer:
             tg = np.resize(node_ids[lo:], batch_size)
             t1 = time.perf_counter()
             tgt, pair, num_pairs, labels = sampler.batch(tg, MODE_TRAIN, out=slots[slot], threads=threads,
-                                                        base_seed=7, counter=step * batch_size)
+                                                        base_seed=base_seed, counter=(first_step + step) * batch_size)
             t2 = time.perf_counter()
             P = int(pair["node_ids"].shape[0])
             d = dslots[slot]
@@ -293,6 +363,7 @@ class Trainer:
                 else:
                     self.train_step(b)
                 ev_b[i].record()
+                self.pipeline_step = first_step + i + 1
                 pipe.release(slot, ev_b[i])   # the launch thread does not wait for the GPU: the producer does, before it refills
                 t_launch += time.perf_counter() - tl
         finally:
@@ -449,3 +520,193 @@ def export_embeddings(engine, sampler, n_nodes: int, batch_size: int = 1024, thr
         last, _, _ = engine.encode(ids=tgt["node_ids"].to(engine.device), attention_mask=tgt["attention_mask"].to(engine.device))
         out[lo: lo + len(tg)] = last[:, 0].float().cpu().numpy()
     return out
+
+
+# ================================================================================================
+# fit: the reference's driver (pmgt/base_trainer.py:283-336: pl.Trainer.fit with max_epochs, validation every epoch,
+# EarlyStopping(monitor, patience, mode), ModelCheckpoint(save_top_k=1, save_last=True), resume through ckpt_path)
+# ================================================================================================
+def monitor_of(early_criterion: str):
+    """(monitor, mode) as init_run derives them (pmgt/base_trainer.py:283-286)."""
+    if early_criterion == "loss":
+        return "loss/val", "min"
+    return f"val/{early_criterion}", "max"
+
+
+def _improves(mode: str, value: float, best: Optional[float]) -> bool:
+    """Strictly better (torch.lt / torch.gt in both Lightning callbacks): a tie is not an improvement."""
+    if mode not in ("min", "max"):
+        raise ValueError(f"mode={mode!r}: expected 'min' or 'max'")
+    return best is None or (value < best if mode == "min" else value > best)
+
+
+class EarlyStopping:
+    """Lightning's EarlyStopping(monitor, patience, mode) with its defaults (min_delta 0, checked after every validation): `update`
+    returns True once `patience` validations in a row brought no improvement."""
+
+    def __init__(self, monitor: str, patience: int, mode: str):
+        self.monitor, self.patience, self.mode = monitor, int(patience), mode
+        self.wait_count, self.best_score, self.stopped_epoch = 0, None, 0
+
+    @property
+    def state_key(self) -> str:
+        return f"EarlyStopping{{'monitor': '{self.monitor}', 'mode': '{self.mode}'}}"
+
+    def update(self, value: float, epoch: int = 0) -> bool:
+        if _improves(self.mode, float(value), self.best_score):
+            self.best_score, self.wait_count = float(value), 0
+            return False
+        self.wait_count += 1
+        if self.wait_count >= self.patience:
+            self.stopped_epoch = int(epoch)
+            return True
+        return False
+
+    def state_dict(self) -> dict:
+        return {"wait_count": self.wait_count, "stopped_epoch": self.stopped_epoch, "patience": self.patience,
+                "best_score": None if self.best_score is None else torch.tensor(self.best_score, dtype=torch.float64)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.wait_count, self.stopped_epoch = int(sd["wait_count"]), int(sd.get("stopped_epoch", 0))
+        self.best_score = None if sd.get("best_score") is None else float(sd["best_score"])
+
+
+class BestCheckpoint:
+    """The bookkeeping of ModelCheckpoint(monitor, mode, save_top_k=1, save_last=True) with the reference's file-name pattern
+    `epoch={epoch:02d}-{loss|auc}={value:.4f}.ckpt` (pmgt/base_trainer.py:291-298).  No file is touched here: `update` says which
+    path to write and which to remove."""
+
+    def __init__(self, dirpath: str, monitor: str, mode: str):
+        self.dirpath, self.monitor, self.mode = str(dirpath), monitor, mode
+        self.best_model_path, self.best_model_score = "", None
+        self.last_model_path = ""
+
+    @property
+    def state_key(self) -> str:
+        return (f"ModelCheckpoint{{'monitor': '{self.monitor}', 'mode': '{self.mode}', 'every_n_train_steps': 0, 'every_n_epochs': 1, "
+                "'train_time_interval': None, 'save_on_train_epoch_end': True}")
+
+    def filename(self, epoch: int, value: float) -> str:
+        # the criterion's name: "loss" of loss/val, "auc" of val/auc (the reference's own split('/')[-1] would call the first one "val")
+        short = next(p for p in self.monitor.split("/") if p != "val")
+        return f"epoch={int(epoch):02d}-{short}={float(value):.4f}.ckpt"
+
+    def update(self, epoch: int, value: float):
+        """(path to write, path to remove) when `value` is the best so far, (None, None) otherwise."""
+        import os
+        if not _improves(self.mode, float(value), self.best_model_score):
+            return None, None
+        old = self.best_model_path or None
+        self.best_model_path, self.best_model_score = os.path.join(self.dirpath, self.filename(epoch, value)), float(value)
+        return self.best_model_path, (old if old != self.best_model_path else None)
+
+    def state_dict(self) -> dict:
+        score = None if self.best_model_score is None else torch.tensor(self.best_model_score, dtype=torch.float64)
+        return {"monitor": self.monitor, "best_model_score": score, "best_model_path": self.best_model_path, "current_score": score,
+                "dirpath": self.dirpath, "last_model_path": self.last_model_path}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.best_model_path = str(sd.get("best_model_path") or "")
+        self.best_model_score = None if sd.get("best_model_score") is None else float(sd["best_model_score"])
+        self.last_model_path = str(sd.get("last_model_path") or "")
+
+
+def epoch_order(n: int, seed: int, epoch: int, rank: int = 0, world_size: int = 1) -> np.ndarray:
+    """Positions into the training ids this rank visits in epoch `epoch`: its strided shard of ONE permutation of 0 .. n - 1 seeded by
+    (seed, epoch) (parallel.shard_indices: DistributedSampler semantics).  A pure function of its arguments: every rank computes the
+    same permutation, and a resumed run the same one again."""
+    from .parallel import shard_indices
+    return shard_indices(int(n), int(rank), int(world_size), seed=int(seed), epoch=int(epoch), shuffle=True)
+
+
+def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid_ids: np.ndarray, batch_size: int, max_epochs: int,
+        early_criterion: str = "loss", patience: int = 10, ckpt_dir: str = ".", resume_from: Optional[str] = None,
+        save_every_n_steps: int = 0, seed: int = 0, graphs: bool = False, threads: int = 8, valid_batch_size: int = 256, log=None) -> dict:
+    """pl.Trainer.fit as the reference's init_run configures it, restated: `max_epochs` epochs; epoch e trains on this rank's shard of
+    a permutation of `train_ids` seeded by (seed, e) -- the len // batch_size full batches through run_live, a remainder as one eager
+    train_step of its true size (DataLoader drop_last=False), an unfinished accumulation window stepped at the end of the epoch as
+    Lightning does; validation after every epoch (evaluate; over all ranks under a process group); monitor loss/val (min) or
+    val/<criterion> (max); stop after `patience` validations without improvement; `last.ckpt` after every epoch and every
+    `save_every_n_steps` optimizer steps (> 0), the single best checkpoint under the reference's name pattern with its predecessor
+    removed.  resume_from: a path, or "last" (= ckpt_dir/last.ckpt): restores weights, optimizer, counters, RNG, the early-stopping and
+    best-checkpoint bookkeeping and the position inside the epoch, and continues as the uninterrupted run would have.
+    log: optional callable, log({"event": "train", epoch, global_step, batches_done, loss}) after every run of training steps between two
+    checkpoint opportunities and log({"event": "valid", epoch, global_step, <metrics>}) after every validation.
+    Returns {best_model_path, best_model_score, epochs_run, stopped_early, history: per-epoch metrics}."""
+    import os
+
+    from . import io as pio
+    eng = trainer.engine
+    if getattr(model_or_engine, "engine", model_or_engine) is not eng:
+        raise ValueError("fit: the trainer drives another engine than the one passed")
+    rank, ws = world() if trainer.world_size > 1 else (0, 1)
+    monitor, mode = monitor_of(early_criterion)
+    stopper, best = EarlyStopping(monitor, patience, mode), BestCheckpoint(ckpt_dir, monitor, mode)
+    last_path = os.path.join(ckpt_dir, "last.ckpt")
+    best.last_model_path = last_path
+    if rank == 0:
+        os.makedirs(ckpt_dir, exist_ok=True)
+    train_ids, valid_ids = np.asarray(train_ids), np.asarray(valid_ids)
+    run = {"seed": int(seed), "batch_size": int(batch_size), "n_train": int(len(train_ids)), "world_size": int(ws)}
+    epoch, done, history, stopped = 0, 0, [], False
+    if resume_from is not None:
+        ck = pio.load_training_checkpoint(model_or_engine, trainer, last_path if resume_from == "last" else resume_from)
+        st = (ck.get("pmgt_amd") or {}).get("fit")
+        if st is None:
+            raise ValueError("fit(resume_from=...): the checkpoint was not written by fit (no epoch position in it)")
+        for k, v in run.items():
+            if st[k] != v:
+                raise ValueError(f"fit(resume_from=...): the checkpoint was written with {k} = {st[k]!r}, this call has {v!r}: the epoch "
+                                 "order and the sampler streams would not continue it")
+        epoch, done, history, stopped = int(st["epoch"]), int(st["batches_done"]), [dict(h) for h in st["history"]], bool(st["stopped_early"])
+        stopper.load_state_dict(pio._callback(ck["callbacks"], "EarlyStopping"))
+        best.load_state_dict(pio._callback(ck["callbacks"], "ModelCheckpoint"))
+        best.dirpath, best.last_model_path = str(ckpt_dir), last_path
+
+    def save(path, top_epoch):
+        st = dict(run, epoch=epoch, batches_done=done, history=history, stopped_early=stopped)
+        pio.save_training_checkpoint(model_or_engine, trainer, path, epoch=top_epoch, fit=st,
+                                     callbacks={stopper.state_key: stopper.state_dict(), best.state_key: best.state_dict()})
+
+    def say(event, **kw):
+        if log is not None:
+            log(dict(event=event, epoch=epoch, global_step=trainer._opt_steps, **kw))
+
+    stream_seed = int(seed) + rank                       # ranks see different targets: their sampler streams differ too
+    while epoch < max_epochs and not stopped:
+        order = train_ids[epoch_order(len(train_ids), seed, epoch, rank, ws)]
+        n_full = len(order) // batch_size
+        chunk = save_every_n_steps * trainer.accum if save_every_n_steps > 0 else max(n_full, 1)
+        while done < n_full:
+            k = min(chunk - done % chunk, n_full - done)
+            ids = order[done * batch_size: (done + k) * batch_size]
+            # run_live wraps its slice position at len(node_ids) - batch_size: one id more than the k batches keeps every slice exact
+            trainer.run_live(sampler, np.concatenate([ids, ids[:1]]), batch_size, k, threads=threads, graphs=graphs,
+                             first_step=trainer.pipeline_step, base_seed=stream_seed)
+            done += k
+            if save_every_n_steps > 0 and trainer._micro == 0 and done < n_full:
+                save(last_path, epoch)
+            say("train", batches_done=done, loss=float(trainer.last_loss))
+        if len(order) > n_full * batch_size and done == n_full:
+            tgt, pair, num_pairs, labels = sampler.batch(order[n_full * batch_size:], MODE_TRAIN, threads=threads, base_seed=stream_seed,
+                                                          counter=trainer.pipeline_step * batch_size)
+            cu = lambda d: {k_: v.to(eng.device) for k_, v in d.items()}
+            trainer.train_step((cu(tgt), cu(pair), num_pairs.to(eng.device), labels.to(eng.device)))
+            trainer.pipeline_step += 1
+            done += 1
+            say("train", batches_done=done, loss=float(trainer.last_loss))
+        trainer.flush_accumulation()
+        metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1)
+        history.append(dict(epoch=epoch, **metrics))
+        top_epoch = epoch
+        new_best, old_best = best.update(epoch, metrics[monitor])
+        stopped = stopper.update(metrics[monitor], epoch)
+        epoch, done = epoch + 1, 0
+        if new_best is not None:
+            save(new_best, top_epoch)
+            if old_best is not None and rank == 0 and os.path.exists(old_best):
+                os.unlink(old_best)
+        save(last_path, top_epoch)
+        say("valid", **metrics)
+    return {"best_model_path": best.best_model_path, "best_model_score": best.best_model_score, "epochs_run": epoch,
+            "stopped_early": stopped, "history": history}
