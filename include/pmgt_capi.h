@@ -184,6 +184,36 @@ typedef struct pmgt_lr_schedule {
  * per-phase timers do not bracket this entry. */
 int pmgt_optimizer_step_scheduled(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched, void* stream);
 
+/* The guarded step: what a GradScaler gives the reference under --mp-enabled (pmgt/base_trainer.py:312) -- an optimizer step whose
+ * gradients hold an Inf or a NaN is skipped -- decided ON THE DEVICE, so it holds inside a captured step, plus device-side counters and
+ * an optional per-step log ring.  The step is bad when the global gradient norm is not finite: any Inf / NaN element, and also finite
+ * gradients whose sum of squares overflows fp32 (torch.nn.utils.clip_grad_norm_ on fp32 gradients reports the same Inf norm).
+ *   counters  device int64 [4], required: [0] attempts, [1] skipped in total, [2] skipped in a row (a good step resets it), [3] reserved
+ *   log_f     device fp32 [log_rows][PMGT_STEP_LOG_FLOATS], row = attempt index % log_rows: [0] loss (NaN when `loss` is NULL), [1] pre-clip
+ *             gradient norm, [2] clip coefficient (0 on a skipped step), [3] lr_t, [4] flag: 0 applied, 1 skipped, 2 applied although the
+ *             norm is not finite (skip_nonfinite = 0); [5..7] not written
+ *   log_i     device int64 [log_rows][2]: [0] attempt index (0-based), [1] *a->step after the step
+ *   log_rows  0 = no log (both log pointers may be NULL then)
+ *   loss      device fp32 scalar the log copies (e.g. pmgt_outputs.loss of the step's last micro-batch), or NULL
+ *   skip_nonfinite  1 = skip bad steps; 0 = count and log only, the step is applied whatever the norm (pmgt_optimizer_step's behaviour) */
+#define PMGT_STEP_LOG_FLOATS 8
+typedef struct pmgt_step_guard {
+    int64_t* counters;
+    float* log_f;
+    int64_t* log_i;
+    int64_t log_rows;
+    const float* loss;
+    int skip_nonfinite;
+} pmgt_step_guard;
+/* pmgt_optimizer_step_scheduled (sched = NULL: constant a->lr, then pmgt_optimizer_step bit for bit) with the guard.  a->scalars is
+ * device [8]: [0..4] as the scheduled step on an applied step, [5] = 1 when the step was skipped, else 0.  A skipped step touches no
+ * parameter or moment, does NOT advance *a->step (bias corrections and schedule count applied steps), and writes [0] = 0, [3] = the
+ * non-finite norm, [4] = the rate it would have used.  Refused (-2): what pmgt_optimizer_step_scheduled refuses, a NULL guard or
+ * counters, log_rows < 0, log_rows > 0 with a NULL log pointer.  The same three launches, no sync, no allocation: capturable.
+ * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (one struct, one entry), nothing existing moved. */
+int pmgt_optimizer_step_guarded(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched,
+                                const pmgt_step_guard* guard, void* stream);
+
 /* Gradient-ready notification for the data-parallel exchange (replaces DDP's autograd hooks + buckets,
  * pmgt/base_trainer.py:309-322 -> pl.Trainer(gpus=N)): during a backward pass the engine calls cb(user, offset, numel) on
  * the CALLING host thread right after it has enqueued the last launch that writes grads[offset, offset + numel) -- i.e.

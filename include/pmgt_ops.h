@@ -217,6 +217,11 @@ int pmgt_op_adamw(float* p, const float* g, float* m, float* v, const uint8_t* d
 int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                             float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                             void* stream);
+/* the same behind the step guard (pmgt_step_guard, pmgt_capi.h); sched may be NULL (constant lr: pmgt_op_adamw bit for bit on an applied
+ * step); scal [8], [5] = 1 when the step was skipped */
+int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
+                          float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
+                          const pmgt_step_guard* guard, void* stream);
 /* out [n] = lr * lambda of steps first_step .. first_step + n - 1: the device function of the scheduled step, one launch */
 int pmgt_op_lr_schedule(const pmgt_lr_schedule* sched, float lr, int64_t first_step, int n, float* out, void* stream);
 /* weight mirror: per descriptor, W = params[src ..] [rows, cols] copied as dtype to mirror[dst ..], transposed to mirror[dst_t ..] and

@@ -16,9 +16,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 # outside csrc/ (bench.py fingerprints the kernel sources there): the host-only single-kernel entries of the test surface
-# (include/pmgt_ops.h), and the learning-rate-scheduled form of the optimizer step, which the measured step never launches
+# (include/pmgt_ops.h), and the learning-rate-scheduled and the guarded form of the optimizer step, which the measured step never launches
 OPS_SOURCES = [os.path.join(HERE, "ops", "row_ops.hip"), os.path.join(HERE, "ops", "lr_schedule.hip"),
-               os.path.join(HERE, "ops", "dropout_keep.hip")]
+               os.path.join(HERE, "ops", "dropout_keep.hip"), os.path.join(HERE, "ops", "guarded_step.hip")]
 HIP_SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_wsr.hip", "gemm_rowln.hip", "fp8.hip", "rowops.hip", "attention.hip", "attention_mfma.hip", "qkvc_attn.hip", "segsum.hip", "loss.hip", "optim.hip", "engine.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in architectural VGPRs (no v_accvgpr_read moves before every VALU
@@ -56,6 +56,7 @@ def build_hip(force=False):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("pmgt_capi.h", "pmgt_ops.h")]
+    headers += [os.path.join(HERE, "ops", f) for f in os.listdir(os.path.join(HERE, "ops")) if f.endswith(".h")]
     jobs, objs = [], []
     for src in [os.path.join(CSRC, s) for s in HIP_SOURCES] + OPS_SOURCES:
         obj = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))

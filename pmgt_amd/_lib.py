@@ -66,6 +66,15 @@ class LrScheduleC(C.Structure):
     _fields_ = [("type", C.c_int), ("num_warmup_steps", C.c_int64), ("num_training_steps", C.c_int64)]
 
 
+class StepGuardC(C.Structure):
+    """pmgt_step_guard (include/pmgt_capi.h): device counters int64 [4], log ring fp32 [rows][STEP_LOG_FLOATS] + int64 [rows][2]."""
+    _fields_ = [("counters", C.c_void_p), ("log_f", C.c_void_p), ("log_i", C.c_void_p), ("log_rows", C.c_int64), ("loss", C.c_void_p),
+                ("skip_nonfinite", C.c_int)]
+
+
+STEP_LOG_FLOATS = 8      # PMGT_STEP_LOG_FLOATS: loss, pre-clip norm, clip coefficient, lr_t, flag, 3 reserved
+STEP_LOG_APPLIED, STEP_LOG_SKIPPED, STEP_LOG_APPLIED_NONFINITE = 0, 1, 2      # the flag column
+
 # PMGT_LR_* in order: the choices of the reference's --scheduler-type (train.py:38-52)
 LR_SCHEDULE_TYPES = ("constant", "constant_with_warmup", "linear", "cosine", "cosine_with_restarts", "polynomial")
 
@@ -79,7 +88,7 @@ EPI_NONE, EPI_GELU, EPI_GELU_GRAD = 0, 1, 2
 HIP_SYMBOLS = [
     "pmgt_last_error", "pmgt_abi_version", "pmgt_engine_create", "pmgt_engine_destroy", "pmgt_param_count",
     "pmgt_param_num_entries", "pmgt_param_entry", "pmgt_workspace_bytes", "pmgt_pretrain_step", "pmgt_encode_ids",
-    "pmgt_encode_feats", "pmgt_encode_train", "pmgt_encode_backward", "pmgt_optimizer_step", "pmgt_optimizer_step_scheduled", "pmgt_profile_begin",
+    "pmgt_encode_feats", "pmgt_encode_train", "pmgt_encode_backward", "pmgt_optimizer_step", "pmgt_optimizer_step_scheduled", "pmgt_optimizer_step_guarded", "pmgt_profile_begin",
     "pmgt_profile_end", "pmgt_profile_sequence", "pmgt_profile_records", "pmgt_cast_from_f32", "pmgt_cast_to_f32", "pmgt_quantize_e4m3", "pmgt_dequantize_e4m3",
     "pmgt_engine_set_grad_ready_callback", "pmgt_engine_set_option", "pmgt_engine_get_option",
 ]
@@ -93,6 +102,7 @@ OPS_SYMBOLS = [
     "pmgt_op_seg_part_elems", "pmgt_op_seg_sum", "pmgt_op_pair_offsets", "pmgt_op_nfr_compact", "pmgt_op_gsr", "pmgt_op_nfr_diff_parts",
     "pmgt_op_nfr_diff", "pmgt_op_loss_finish", "pmgt_op_scatter_rows", "pmgt_op_adamw", "pmgt_op_mirror",
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
+    "pmgt_op_adamw_guarded",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -150,6 +160,7 @@ def hip():
     L.pmgt_encode_backward.argtypes = [vp, C.POINTER(TensorsC), featp, vp, i, i, vp, i64, i, vp]
     L.pmgt_optimizer_step.argtypes = [vp, C.POINTER(TensorsC), C.POINTER(AdamC), vp]
     L.pmgt_optimizer_step_scheduled.argtypes = [vp, C.POINTER(TensorsC), C.POINTER(AdamC), C.POINTER(LrScheduleC), vp]
+    L.pmgt_optimizer_step_guarded.argtypes = [vp, C.POINTER(TensorsC), C.POINTER(AdamC), C.POINTER(LrScheduleC), C.POINTER(StepGuardC), vp]
     L.pmgt_profile_begin.argtypes = [vp]
     L.pmgt_profile_end.argtypes = [vp, C.c_char_p, i]
     L.pmgt_profile_sequence.argtypes = [vp, C.c_char_p, i]
@@ -207,6 +218,7 @@ def hip():
     L.pmgt_op_scatter_rows.argtypes = [i, vp, vp, vp, i, i, vp, i, vp]
     L.pmgt_op_adamw.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, vp]
     L.pmgt_op_adamw_scheduled.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), vp]
+    L.pmgt_op_adamw_guarded.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), C.POINTER(StepGuardC), vp]
     L.pmgt_op_lr_schedule.argtypes = [C.POINTER(LrScheduleC), f, i64, i, vp, vp]
     L.pmgt_op_mirror.argtypes = [i, vp, vp, C.POINTER(MirrorDescC), i, i, vp]
     L.pmgt_op_nfr_generate.argtypes = [vp, i, i, i, f, f, vp, vp, vp, vp]

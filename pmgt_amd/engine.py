@@ -75,10 +75,15 @@ class Engine:
         # optimizer state (created lazily)
         self.exp_avg = self.exp_avg_sq = None
         self.opt_step = torch.zeros(1, dtype=torch.int64, device=self.device)
-        # 8 floats for the scheduled step (slot 4 = the step's learning rate); the unscheduled step sees the first 4
+        # 8 floats for the scheduled step (slot 4 = the step's learning rate) and the guarded one (slot 5 = skipped flag); the unscheduled step
+        # sees the first 4
         self._opt_scalars8 = torch.zeros(8, dtype=torch.float32, device=self.device)
         self.opt_scalars = self._opt_scalars8[:4]
         self.opt_scratch = torch.zeros(1024, dtype=torch.float32, device=self.device)
+        # the guarded step (optimizer_step(guard=...)): attempts, skipped, skipped in a row, reserved -- device counters like opt_step;
+        # the log ring is created by ensure_step_log
+        self.step_counters_dev = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self.step_log_f = self.step_log_i = None
 
     def __del__(self):
         try:
@@ -371,24 +376,75 @@ class Engine:
             self.exp_avg = torch.zeros_like(self.params)
             self.exp_avg_sq = torch.zeros_like(self.params)
 
-    def optimizer_step(self, lr=1e-3, weight_decay=1e-2, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, schedule=None):
+    def ensure_step_log(self, rows: int):
+        """The log ring of the guarded step (`rows` steps; 0 drops it), created OUTSIDE any stream capture like the Adam moments: a
+        captured step addresses it by pointer.  Attempt index -1 marks a row no step has written."""
+        rows = int(rows)
+        have = 0 if self.step_log_f is None else int(self.step_log_f.shape[0])
+        if rows == have:
+            return
+        if rows < 0:
+            raise ValueError(f"step log of {rows} rows")
+        if torch.cuda.is_current_stream_capturing() or getattr(self, "_live_graphs", 0) > 0:
+            raise RuntimeError(f"pmgt_amd: the step log ({have} -> {rows} rows) must exist before a step is captured and cannot change "
+                               "while captured steps are alive (call Engine.ensure_step_log(rows) first)")
+        if rows == 0:
+            self.step_log_f = self.step_log_i = None
+            return
+        self.step_log_f = torch.zeros(rows, _lib.STEP_LOG_FLOATS, dtype=torch.float32, device=self.device)
+        self.step_log_i = torch.full((rows, 2), -1, dtype=torch.int64, device=self.device)
+
+    def optimizer_step(self, lr=1e-3, weight_decay=1e-2, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, schedule=None, guard=None):
         """schedule = (type, num_warmup_steps, num_training_steps), type one of _lib.LR_SCHEDULE_TYPES: the step uses
-        lr * lambda(opt_step), evaluated on the device from the step counter (see pmgt_amd.schedule); last_lr() reads it back."""
+        lr * lambda(opt_step), evaluated on the device from the step counter (see pmgt_amd.schedule); last_lr() reads it back.
+        guard = None: the two entries above, as ever.  guard = dict(skip_nonfinite=bool, log_rows=R, loss=device scalar or None): the
+        guarded entry -- a step whose global gradient norm is not finite (an Inf / NaN gradient, or a sum of squares past fp32) is
+        skipped ON THE DEVICE when skip_nonfinite is set (no parameter, moment or opt_step changes; was_skipped() reads the flag), every
+        step counts in step_counters(), and with log_rows > 0 leaves a row in the ring step_log() reads.  On an applied step the
+        arithmetic is that of the unguarded entries bit for bit."""
         self.ensure_optimizer_state()
         ac = _lib.AdamC(self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.decay_mask.data_ptr(), lr, weight_decay,
                         betas[0], betas[1], eps, float(max_grad_norm) if max_grad_norm else 0.0,
                         self.opt_step.data_ptr(), self.opt_scalars.data_ptr(), self.opt_scratch.data_ptr())
         tc = self._tensors()
+        sc = None
         if schedule is not None:
             kind, warmup, total = schedule
             if kind not in _lib.LR_SCHEDULE_TYPES:
                 raise ValueError(f"scheduler type {kind!r}: expected one of {_lib.LR_SCHEDULE_TYPES}")
             sc = _lib.LrScheduleC(_lib.LR_SCHEDULE_TYPES.index(kind), int(warmup), int(total))
+        if guard is not None:
+            rows = int(guard.get("log_rows", 0))
+            self.ensure_step_log(rows)
+            loss = guard.get("loss")
+            gd = _lib.StepGuardC(self.step_counters_dev.data_ptr(), self.step_log_f.data_ptr() if rows else None,
+                                  self.step_log_i.data_ptr() if rows else None, rows, None if loss is None else loss.data_ptr(),
+                                  1 if guard.get("skip_nonfinite") else 0)
+            _lib.check(self.lib.pmgt_optimizer_step_guarded(self.h, C.byref(tc), C.byref(ac), None if sc is None else C.byref(sc),
+                                                            C.byref(gd), _stream()))
+            return
+        if sc is not None:
             _lib.check(self.lib.pmgt_optimizer_step_scheduled(self.h, C.byref(tc), C.byref(ac), C.byref(sc), _stream()))
             return
         _lib.check(self.lib.pmgt_optimizer_step(self.h, C.byref(tc), C.byref(ac), _stream()))
 
     # ---- everything a training step mutates, as plain data (Trainer.state_dict / pmgt_amd.io carry it to disk) --------------
+    def step_counters(self) -> dict:
+        """{"attempts", "skipped", "skipped_in_a_row"} of the guarded step: one small device -> host read (it waits for the steps
+        launched so far)."""
+        a, sk, row, _ = (int(x) for x in self.step_counters_dev.cpu())
+        return {"attempts": a, "skipped": sk, "skipped_in_a_row": row}
+
+    def step_log(self) -> list:
+        """The rows of the log ring that hold a step, oldest first, as records {attempt, opt_step (after the step: it counts applied
+        steps), loss, grad_norm (pre-clip), clip_coef, lr, skipped, nonfinite}.  Two small reads.  Loading a training state empties it."""
+        if self.step_log_f is None:
+            return []
+        f, i = self.step_log_f.cpu(), self.step_log_i.cpu()
+        rows = sorted((int(i[r, 0]), r) for r in range(i.shape[0]) if int(i[r, 0]) >= 0)
+        return [dict(attempt=a, opt_step=int(i[r, 1]), loss=float(f[r, 0]), grad_norm=float(f[r, 1]), clip_coef=float(f[r, 2]), lr=float(f[r, 3]),
+                     skipped=int(f[r, 4]) == _lib.STEP_LOG_SKIPPED, nonfinite=int(f[r, 4]) != _lib.STEP_LOG_APPLIED) for a, r in rows]
+
     def config_key(self) -> dict:
         """The configuration fields that decide the parameter layout and the kernels' arithmetic."""
         c = self.config
@@ -410,7 +466,7 @@ class Engine:
         seed, step = (int(x) for x in self.rng_state.cpu())
         return dict(n_params=self.n_params, dtype=self.dtype_name, config=self.config_key(), params=self.params.cpu(),
                     exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), opt_step=int(self.opt_step.cpu()),
-                    rng_state={"seed": seed, "step": step}, options=self.options_set())
+                    rng_state={"seed": seed, "step": step}, options=self.options_set(), step_counters=self.step_counters())
 
     def check_training_state(self, state: dict) -> None:
         """Refuses, with the reason, a state whose shape is not this engine's."""
@@ -447,6 +503,10 @@ class Engine:
         self.exp_avg.copy_(state["exp_avg"].to(torch.float32))
         self.exp_avg_sq.copy_(state["exp_avg_sq"].to(torch.float32))
         self.opt_step.fill_(int(state["opt_step"]))
+        cnt = state.get("step_counters") or {}                   # a state written before the guarded step existed: zeros
+        self.step_counters_dev.copy_(torch.tensor([int(cnt.get(k, 0)) for k in ("attempts", "skipped", "skipped_in_a_row")] + [0], dtype=torch.int64))
+        if self.step_log_i is not None:
+            self.step_log_i[:, 0].fill_(-1)                      # the ring is not part of the state: its rows belong to the run that wrote them
         rng = state.get("rng_state")
         if rng is not None:
             self.rng_state.copy_(torch.tensor([int(rng["seed"]), int(rng["step"])], dtype=torch.int64))
@@ -506,6 +566,10 @@ class Engine:
     def grad_norm(self) -> torch.Tensor:
         """Pre-clip global gradient norm of the last optimizer_step (device scalar)."""
         return self.opt_scalars[3]
+
+    def was_skipped(self) -> torch.Tensor:
+        """1.0 when the last GUARDED optimizer_step was skipped for a non-finite gradient norm, else 0.0 (device scalar)."""
+        return self._opt_scalars8[5]
 
     def last_lr(self) -> torch.Tensor:
         """Learning rate the last SCHEDULED optimizer_step used, lr * lambda of the steps completed before it (device scalar)."""

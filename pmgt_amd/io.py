@@ -271,7 +271,8 @@ def training_checkpoint(state_dict: Dict[str, torch.Tensor], entries, trainer_sd
     private = {"format_version": FORMAT_VERSION, "rng_state": dict(est["rng_state"]), "opt_steps": int(trainer_sd["opt_steps"]),
                "options": list(est["options"]), "pipeline_step": int(trainer_sd["pipeline_step"]), "dtype": est["dtype"],
                "n_params": int(est["n_params"]), "config": dict(est["config"]), "hyper_parameters": dict(hp),
-               "accumulate_grad_batches": int(trainer_sd["accumulate_grad_batches"]), "fit": fit}
+               "accumulate_grad_batches": int(trainer_sd["accumulate_grad_batches"]), "fit": fit,
+               "step_counters": dict(est.get("step_counters") or {"attempts": 0, "skipped": 0, "skipped_in_a_row": 0})}
     return {"state_dict": state_dict, "optimizer_states": [opt], "lr_schedulers": sched, "global_step": steps, "epoch": int(epoch),
             "callbacks": dict(callbacks or {}), "pmgt_amd": private, **extra}
 
@@ -297,7 +298,8 @@ def training_state_from_checkpoint(ck: dict, entries, n_params: int, n_frozen: i
     if pv is not None:
         if int(pv.get("format_version", 0)) > FORMAT_VERSION:
             raise ValueError(f"checkpoint format version {pv['format_version']} is newer than this library's ({FORMAT_VERSION})")
-        eng = dict(n_params=int(pv["n_params"]), dtype=pv["dtype"], config=dict(pv["config"]), rng_state=dict(pv["rng_state"]), options=list(pv["options"]))
+        eng = dict(n_params=int(pv["n_params"]), dtype=pv["dtype"], config=dict(pv["config"]), rng_state=dict(pv["rng_state"]), options=list(pv["options"]),
+                   step_counters=dict(pv.get("step_counters") or {}))       # absent before the guarded step existed: zeros
         out = {"opt_steps": int(pv["opt_steps"]), "pipeline_step": int(pv["pipeline_step"]), "hyper_parameters": dict(pv["hyper_parameters"]),
                "accumulate_grad_batches": int(pv["accumulate_grad_batches"])}
     else:

@@ -5,31 +5,11 @@
 // defaults get_scheduler leaves in place (the reference: --scheduler-type / --scheduler-warmup, train.py:38-52, pmgt/base_trainer.py:71-90).
 // Kept out of csrc/: the unscheduled step and every kernel bench.py measures (and fingerprints there) stay byte for byte what they were; the
 // gradient-norm partials are csrc/optim.hip's own kernel, so the step is the same three launches.
-#include "../../include/pmgt_ops.h"
-#include "../csrc/optim.h"
+#include "lr_schedule.h"      // LrSchedule, scheduled_lr, schedule_from: shared with guarded_step.hip
 
 namespace pmgt {
 
 __global__ void sqnorm_part_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part);      // csrc/optim.hip
-
-struct LrSchedule {
-    int type;                  // PMGT_LR_*
-    int64_t warmup, total;     // num_warmup_steps (W), num_training_steps (T)
-};
-
-// lr * lambda(s): LambdaLR's rate after s completed optimizer steps
-__device__ double scheduled_lr(const LrSchedule sc, double lr, int64_t s) {
-    const double W = (double)sc.warmup, T = (double)sc.total, x = (double)s;
-    if (sc.type != PMGT_LR_CONSTANT && s < sc.warmup) return lr * (x / fmax(1.0, W));
-    const double q = (x - W) / fmax(1.0, T - W);
-    switch (sc.type) {
-        case PMGT_LR_LINEAR: return lr * fmax(0.0, (T - x) / fmax(1.0, T - W));
-        case PMGT_LR_COSINE: return lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * q)));                                  // half a cycle
-        case PMGT_LR_COSINE_WITH_RESTARTS: return q >= 1.0 ? 0.0 : lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * fmod(q, 1.0))));      // one cycle
-        case PMGT_LR_POLYNOMIAL: return lr * ((s > sc.total ? 1e-7 : (lr - 1e-7) * (1.0 - (x - W) / (T - W)) + 1e-7) / lr);    // power 1, lr_end 1e-7
-        default: return lr;                                                                                      // constant, constant_with_warmup
-    }
-}
 
 // adam_prepare_kernel of csrc/optim.hip with lr_t for lr.  scal [8]: [0] = clip coefficient, [1] = lr_t / bc1, [2] = 1 / sqrt(bc2),
 // [3] = total grad norm (pre-clip), [4] = lr_t; [5..7] are not written
@@ -78,20 +58,6 @@ __global__ __launch_bounds__(256) void adamw_scheduled_kernel(float* __restrict_
 __global__ __launch_bounds__(256) void lr_schedule_kernel(const LrSchedule sched, float lr, int64_t first_step, int n, float* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = (float)scheduled_lr(sched, (double)lr, first_step + i);
-}
-
-static int schedule_from(const pmgt_lr_schedule* in, float lr, const char* who, LrSchedule* out) {
-    PMGT_CHECK(in != nullptr, -2, "%s: NULL schedule", who);
-    const long long W = in->num_warmup_steps, T = in->num_training_steps;
-    PMGT_CHECK(in->type >= PMGT_LR_CONSTANT && in->type <= PMGT_LR_POLYNOMIAL, -2, "%s: unknown lr schedule type %d", who, in->type);
-    PMGT_CHECK(W >= 0, -2, "%s: num_warmup_steps = %lld is negative", who, W);
-    PMGT_CHECK(in->type < PMGT_LR_LINEAR || T > 0, -2, "%s: this lr schedule needs num_training_steps > 0 (got %lld)", who, T);
-    if (in->type == PMGT_LR_POLYNOMIAL) {
-        PMGT_CHECK((double)lr > 1e-7, -2, "%s: polynomial lr schedule: lr_end (1e-07) must be smaller than the initial lr (%g)", who, (double)lr);
-        PMGT_CHECK(T > W, -2, "%s: polynomial lr schedule needs num_training_steps (%lld) > num_warmup_steps (%lld)", who, T, W);
-    }
-    *out = LrSchedule{in->type, in->num_warmup_steps, in->num_training_steps};
-    return 0;
 }
 
 // adamw_step of csrc/optim.hip: norm partials -> prepare -> AdamW, three launches

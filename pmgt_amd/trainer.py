@@ -23,20 +23,48 @@ from .datasets import MODE_EVAL, MODE_INFERENCE, MODE_TRAIN
 from .parallel import BucketedAllReduce, allreduce_mean_, broadcast_, gather_predictions, world
 
 
+class NonFiniteGradientsError(RuntimeError):
+    """Too many optimizer steps in a row were skipped for a non-finite gradient norm (Trainer.check_nonfinite): the run is not
+    recovering by itself.  `counters` = Engine.step_counters() at the time."""
+
+    def __init__(self, message, counters=None):
+        super().__init__(message)
+        self.counters = dict(counters or {})
+
+
 class Trainer:
     def __init__(self, engine, lr: float = 1e-3, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_grad_norm: Optional[float] = None, world_size: int = 1, accumulate_grad_batches: int = 1,
                  random_node_ratio: float = 0.02, mask_node_ratio: float = 0.16, overlap_allreduce: bool = True,
                  buckets: str = "two", check_carrier_every: int = 200, force_exchange: bool = False,
                  scheduler_type: Optional[str] = None, num_warmup_steps: Optional[int] = None,
-                 num_training_steps: Optional[int] = None):
+                 num_training_steps: Optional[int] = None, nonfinite: Optional[str] = None, step_log: int = 0,
+                 max_skipped_in_a_row: int = 25):
         """scheduler_type (one of the reference's --scheduler-type choices; None = constant `lr`, the step as it always was) with
         num_warmup_steps / num_training_steps: every optimizer step uses lr * lambda(k), k = the optimizer steps completed before
         it, evaluated ON THE DEVICE by the fused step (pmgt_amd.schedule states the multipliers).  It advances once per optimizer
         step, so gradient accumulation and data parallelism (every rank's counter is equal) need nothing more, and a captured
         step / run_live(graphs=True) follows it with no re-capture.  The schedule's position is `engine.opt_step`, the same
-        device counter as Adam's bias corrections: setting that counter, as a resume does (load_state_dict), moves both together."""
+        device counter as Adam's bias corrections: setting that counter, as a resume does (load_state_dict), moves both together.
+
+        nonfinite="skip": what the GradScaler of the reference's --mp-enabled run does (pmgt/base_trainer.py:312) -- an optimizer step
+        whose gradients hold an Inf or a NaN (global norm not finite; that includes a sum of squares past fp32, for which
+        clip_grad_norm_ reports Inf too) is skipped, decided ON THE DEVICE inside the fused step, so it holds in a captured step and
+        under run_live(graphs=True) with no host sync: parameters, moments and opt_step stay as they were, so bias corrections and
+        the schedule count applied steps only.  With accumulation the window's gradients are dropped: the next micro-batch overwrites
+        the buffer.  Under data parallelism the decision is taken after the all-reduce, on gradients that are identical on every
+        rank: every rank decides alike and no extra collective is needed.  step_log=R keeps the last R optimizer steps (loss of the
+        step's last micro-batch, pre-clip norm, clip coefficient, rate, skipped flag) in a device ring, Engine.step_log(); alone it
+        logs without guarding.  Both are frozen into a captured step and recorded in checkpoints like the other hyper-parameters.
+        None / 0 (default): the step through the entries it always took.  max_skipped_in_a_row: check_nonfinite() raises
+        NonFiniteGradientsError at that many consecutive skips (25 is a policy default, not a measurement); it runs only where the
+        host waits for the GPU anyway (end of run_live, epoch end and checkpoint writes of fit, state_dict()), never per step."""
         self.engine = engine
+        if nonfinite not in (None, "skip"):
+            raise ValueError(f"nonfinite={nonfinite!r}: expected None or 'skip'")
+        if int(step_log) < 0 or int(max_skipped_in_a_row) < 1:
+            raise ValueError(f"step_log={step_log!r} must be >= 0 and max_skipped_in_a_row={max_skipped_in_a_row!r} >= 1")
+        self.nonfinite, self.step_log, self.max_skipped_in_a_row = nonfinite, int(step_log), int(max_skipped_in_a_row)
         self.scheduler_type, self.num_warmup_steps, self.num_training_steps = scheduler_type, num_warmup_steps, num_training_steps
         if scheduler_type is not None:
             from .schedule import lr_lambda
@@ -105,7 +133,7 @@ class Trainer:
         if self.accum > 1:
             eng.grads.div_(self.accum)
         eng.optimizer_step(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
-                           max_grad_norm=self.max_grad_norm, schedule=self._schedule())
+                           max_grad_norm=self.max_grad_norm, schedule=self._schedule(), guard=self._guard())
         self._opt_steps += 1
         if self.check_carrier_every and self._opt_steps % self.check_carrier_every == 0 and not getattr(self, "_capturing", False):
             self._check_carrier()
@@ -156,6 +184,8 @@ class Trainer:
         self.engine.check_layernorm_carrier()
         # Adam moments exist before the capture: their zero-fill must not become a node of the graph (it would reset them on every replay)
         self.engine.ensure_optimizer_state()
+        if self._guard() is not None:
+            self.engine.ensure_step_log(self.step_log)       # the log ring too
         st = torch.cuda.Stream(device=dev)
         st.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(st):
@@ -193,12 +223,35 @@ class Trainer:
             return None
         return (self.scheduler_type, int(self.num_warmup_steps or 0), int(self.num_training_steps or 0))
 
+    def _guard(self):
+        """The guard argument of Engine.optimizer_step, or None when neither nonfinite nor step_log is set (the unguarded entries).  The
+        loss it logs is the loss scalar of the step's last micro-batch: in a capture that is the capture's private output."""
+        if self.nonfinite is None and not self.step_log:
+            return None
+        return dict(skip_nonfinite=self.nonfinite == "skip", log_rows=self.step_log, loss=self.last_loss)
+
+    def check_nonfinite(self, counters: Optional[dict] = None) -> Optional[dict]:
+        """Reads the step counters (one small read; pass `counters` when they were just read) and raises NonFiniteGradientsError when
+        max_skipped_in_a_row or more optimizer steps in a row were skipped.  Returns the counters (None without a guard).  Under data
+        parallelism every rank holds the same counters, so every rank raises alike."""
+        if self._guard() is None:
+            return None
+        c = counters if counters is not None else self.engine.step_counters()
+        if self.nonfinite == "skip" and c["skipped_in_a_row"] >= self.max_skipped_in_a_row:
+            log = self.engine.step_log()
+            norm = f"{log[-1]['grad_norm']!r} (attempt {log[-1]['attempt']})" if log else "not logged (step_log=0)"
+            raise NonFiniteGradientsError(
+                f"the last {c['skipped_in_a_row']} optimizer steps in a row were skipped for a non-finite gradient norm "
+                f"(max_skipped_in_a_row={self.max_skipped_in_a_row}; {c['skipped']} of {c['attempts']} steps skipped in total; last logged "
+                f"pre-clip norm: {norm}); parameters and optimizer state are those of the last applied step", c)
+        return c
+
     def _hyper_key(self):
         """What a captured step froze into kernel arguments: a replay is only valid for the same values.  Of a learning-rate schedule
         that is its descriptor (type, W, T) and the base lr; the current rate is computed on the device and is not part of the key."""
         return (float(self.lr), float(self.weight_decay), tuple(float(b) for b in self.betas), float(self.eps),
                 None if self.max_grad_norm is None else float(self.max_grad_norm), float(self.random_node_ratio), float(self.mask_node_ratio),
-                self._schedule())
+                self.nonfinite, int(self.step_log), self._schedule())
 
     def drop_captured_steps(self):
         """Forgets every step run_live(graphs=True) captured (call after changing lr / weight decay / clip / ratios / engine options by
@@ -210,7 +263,7 @@ class Trainer:
             reps.clear()
 
     # ---- full training state: what a resume needs beyond the weights ---------------------------------------------------------
-    HYPER_NAMES = ("lr", "weight_decay", "betas", "eps", "max_grad_norm", "random_node_ratio", "mask_node_ratio", "schedule")
+    HYPER_NAMES = ("lr", "weight_decay", "betas", "eps", "max_grad_norm", "random_node_ratio", "mask_node_ratio", "nonfinite", "step_log", "schedule")
 
     def hyper_parameters(self) -> dict:
         """_hyper_key() by name: what decides the curve besides the data (the schedule as its descriptor (type, W, T) or None)."""
@@ -224,13 +277,18 @@ class Trainer:
         if self._micro != 0:
             raise RuntimeError(f"Trainer.state_dict(): {self._micro} of {self.accum} micro-batches of the current accumulation window have "
                                "run; the training state can only be saved at an optimizer-step boundary (_micro == 0)")
-        return {"engine": self.engine.training_state(), "opt_steps": int(self._opt_steps), "pipeline_step": int(self.pipeline_step),
+        est = self.engine.training_state()
+        self.check_nonfinite(est["step_counters"])      # a run that no longer applies its steps is not checkpointed
+        return {"engine": est, "opt_steps": int(self._opt_steps), "pipeline_step": int(self.pipeline_step),
                 "hyper_parameters": self.hyper_parameters(), "accumulate_grad_batches": int(self.accum)}
 
     def hyper_mismatches(self, sd: dict) -> list:
         """[(name, checkpoint value, trainer value)] over the hyper-parameters and the accumulation factor `sd` records."""
         mine = dict(self.hyper_parameters(), accumulate_grad_batches=int(self.accum))
         theirs = dict(sd.get("hyper_parameters") or {})
+        if "schedule" in theirs:       # a file of this package (the reference's records no schedule) from before the guard existed: off
+            theirs.setdefault("nonfinite", None)
+            theirs.setdefault("step_log", 0)
         if sd.get("accumulate_grad_batches") is not None:
             theirs["accumulate_grad_batches"] = int(sd["accumulate_grad_batches"])
         norm = lambda v: tuple(norm(x) for x in v) if isinstance(v, (list, tuple)) else v
@@ -321,6 +379,9 @@ class Trainer:
 
         pipe = ProducerPipeline(produce, steps, depth, stall_timeout_s=stall_timeout_s)
         torch.cuda.synchronize()
+        guarded = self._guard() is not None
+        if guarded:
+            count0 = eng.step_counters()               # the GPU is idle here
         t_start = time.perf_counter()
         t0 = None
         pipe.start()
@@ -370,6 +431,14 @@ class Trainer:
             torch.cuda.synchronize()
             pipe.close()
         el = time.perf_counter() - t0
+        extra = {}
+        if guarded:
+            count1 = eng.step_counters()               # the one read of the call's end, after its final synchronize
+            extra["skipped_steps"] = count1["skipped"] - count0["skipped"]
+            tried = count1["attempts"] - count0["attempts"]
+            if self.step_log and 0 < tried <= self.step_log:
+                extra["loss_train"] = [r["loss"] for r in eng.step_log() if r["attempt"] >= count0["attempts"]]
+            self.check_nonfinite(count1)
         idle = sum(ev_b[i - 1].elapsed_time(ev_a[i]) for i in range(1, steps))
         busy = sum(ev_a[i].elapsed_time(ev_b[i]) for i in range(steps))
         return {"nodes_per_s": round(steps * batch_size / el, 1), "ms_per_step": round(el / steps * 1e3, 3),
@@ -380,7 +449,7 @@ class Trainer:
                 "launch_thread_busy_ms_per_step": round(t_launch / steps * 1e3, 3),
                 "launch_thread_waiting_for_input_ms_per_step": round(pipe.starved_s / steps * 1e3, 3),
                 "producer_ms_per_batch": {"sampling": round(t_sample[0] / steps * 1e3, 3), "h2d_issue": round(t_copy[0] / steps * 1e3, 3),
-                                          "waiting_for_a_free_slot": round(t_wait[0] / steps * 1e3, 3)}}
+                                          "waiting_for_a_free_slot": round(t_wait[0] / steps * 1e3, 3)}, **extra}
 
 
 class PipelineError(RuntimeError):
@@ -621,7 +690,8 @@ def epoch_order(n: int, seed: int, epoch: int, rank: int = 0, world_size: int = 
 
 def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid_ids: np.ndarray, batch_size: int, max_epochs: int,
         early_criterion: str = "loss", patience: int = 10, ckpt_dir: str = ".", resume_from: Optional[str] = None,
-        save_every_n_steps: int = 0, seed: int = 0, graphs: bool = False, threads: int = 8, valid_batch_size: int = 256, log=None) -> dict:
+        save_every_n_steps: int = 0, seed: int = 0, graphs: bool = False, threads: int = 8, valid_batch_size: int = 256, log=None,
+        nonfinite="keep", step_log="keep", max_skipped_in_a_row="keep") -> dict:
     """pl.Trainer.fit as the reference's init_run configures it, restated: `max_epochs` epochs; epoch e trains on this rank's shard of
     a permutation of `train_ids` seeded by (seed, e) -- the len // batch_size full batches through run_live, a remainder as one eager
     train_step of its true size (DataLoader drop_last=False), an unfinished accumulation window stepped at the end of the epoch as
@@ -632,6 +702,12 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     best-checkpoint bookkeeping and the position inside the epoch, and continues as the uninterrupted run would have.
     log: optional callable, log({"event": "train", epoch, global_step, batches_done, loss}) after every run of training steps between two
     checkpoint opportunities and log({"event": "valid", epoch, global_step, <metrics>}) after every validation.
+    nonfinite / step_log / max_skipped_in_a_row: passed through to the trainer (Trainer.__init__ states them; "keep" leaves the trainer's
+    own).  With either of the first two set, an epoch's history entry also carries `skipped_steps` (optimizer steps of the epoch skipped for
+    a non-finite gradient norm) and, with a step log, `loss/train`: the mean loss over the epoch's applied steps that are still in the ring
+    (NaN when there is none; a resume empties the ring).  Trainer.check_nonfinite runs at the end of every run of training steps, at the
+    end of an epoch and before every checkpoint write: a run that trips it stops with NonFiniteGradientsError BEFORE that write, so the
+    previous last.ckpt stays.
     Returns {best_model_path, best_model_score, epochs_run, stopped_early, history: per-epoch metrics}."""
     import os
 
@@ -639,6 +715,11 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     eng = trainer.engine
     if getattr(model_or_engine, "engine", model_or_engine) is not eng:
         raise ValueError("fit: the trainer drives another engine than the one passed")
+    passed = {k: v for k, v in (("nonfinite", nonfinite), ("step_log", step_log), ("max_skipped_in_a_row", max_skipped_in_a_row)) if v != "keep"}
+    if passed:
+        checked = Trainer(None, **passed)                 # the constructor's argument checks
+        for k in passed:
+            setattr(trainer, k, getattr(checked, k))      # (run_live re-captures: both settings are part of _hyper_key())
     rank, ws = world() if trainer.world_size > 1 else (0, 1)
     monitor, mode = monitor_of(early_criterion)
     stopper, best = EarlyStopping(monitor, patience, mode), BestCheckpoint(ckpt_dir, monitor, mode)
@@ -649,6 +730,7 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     train_ids, valid_ids = np.asarray(train_ids), np.asarray(valid_ids)
     run = {"seed": int(seed), "batch_size": int(batch_size), "n_train": int(len(train_ids)), "world_size": int(ws)}
     epoch, done, history, stopped = 0, 0, [], False
+    at_epoch_start = None                                    # step counters at the start of the current epoch (guarded trainers)
     if resume_from is not None:
         ck = pio.load_training_checkpoint(model_or_engine, trainer, last_path if resume_from == "last" else resume_from)
         st = (ck.get("pmgt_amd") or {}).get("fit")
@@ -662,9 +744,11 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
         stopper.load_state_dict(pio._callback(ck["callbacks"], "EarlyStopping"))
         best.load_state_dict(pio._callback(ck["callbacks"], "ModelCheckpoint"))
         best.dirpath, best.last_model_path = str(ckpt_dir), last_path
+        at_epoch_start = st.get("counters_at_epoch_start")
 
     def save(path, top_epoch):
-        st = dict(run, epoch=epoch, batches_done=done, history=history, stopped_early=stopped)
+        trainer.check_nonfinite()                            # on every rank, before rank 0 writes anything
+        st = dict(run, epoch=epoch, batches_done=done, history=history, stopped_early=stopped, counters_at_epoch_start=at_epoch_start)
         pio.save_training_checkpoint(model_or_engine, trainer, path, epoch=top_epoch, fit=st,
                                      callbacks={stopper.state_key: stopper.state_dict(), best.state_key: best.state_dict()})
 
@@ -675,6 +759,8 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     stream_seed = int(seed) + rank                       # ranks see different targets: their sampler streams differ too
     while epoch < max_epochs and not stopped:
         order = train_ids[epoch_order(len(train_ids), seed, epoch, rank, ws)]
+        if trainer._guard() is not None and (at_epoch_start is None or done == 0):
+            at_epoch_start = eng.step_counters()
         n_full = len(order) // batch_size
         chunk = save_every_n_steps * trainer.accum if save_every_n_steps > 0 else max(n_full, 1)
         while done < n_full:
@@ -696,8 +782,15 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
             done += 1
             say("train", batches_done=done, loss=float(trainer.last_loss))
         trainer.flush_accumulation()
+        train_metrics = {}
+        counters = trainer.check_nonfinite()
+        if counters is not None:
+            train_metrics["skipped_steps"] = counters["skipped"] - at_epoch_start["skipped"]
+            if trainer.step_log:
+                mine = [r["loss"] for r in eng.step_log() if r["attempt"] >= at_epoch_start["attempts"] and not r["skipped"]]
+                train_metrics["loss/train"] = float(np.mean(mine)) if mine else float("nan")
         metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1)
-        history.append(dict(epoch=epoch, **metrics))
+        history.append(dict(epoch=epoch, **metrics, **train_metrics))
         top_epoch = epoch
         new_best, old_best = best.update(epoch, metrics[monitor])
         stopped = stopper.update(metrics[monitor], epoch)
