@@ -214,6 +214,37 @@ typedef struct pmgt_step_guard {
 int pmgt_optimizer_step_guarded(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched,
                                 const pmgt_step_guard* guard, void* stream);
 
+/* Validation loss and ROC AUC ON THE DEVICE: `_validation_and_test_step` / `_valid_and_test_epoch_end` (pmgt/pmgt/trainer.py:162-195 --
+ * sigmoid(logits) and labels collected per batch, the batch loss weighted by its size, sklearn's roc_auc_score over the epoch) without a
+ * device-to-host copy per batch.  The caller owns one workspace of pmgt_eval_workspace_bytes(capacity) bytes (16-byte aligned device memory,
+ * capacity = prediction slots, 1 .. 2^26) and passes the same `capacity` to every call on it.  Layout, capr = capacity rounded up to 256:
+ *   [0, 64)   scalars: [0] fp64 loss accumulator; uint64 [1] twoU, [2] n_pos, [3] n_neg (written by reduce), [4] scores that were NaN
+ *             (counted by append), [5] the n of the last reduce, [6..7] reserved
+ *   then      keys uint32 [capr], scores fp32 [capr], labels uint8 [capr] in slot order, then scratch of the reduce.
+ * The result STAYS in the workspace: the host reads the 64 scalar bytes with one copy and divides,
+ *   loss/val = acc / n_targets_total,   val/auc = twoU / (2 n_pos n_neg)
+ * (twoU < 2^53 is exact in a double, so that one division is the only rounding).  Every entry is stream-ordered, allocates nothing,
+ * never synchronises and keeps no state outside the workspace.  Refused (-2): NULL / misaligned workspace, a capacity outside the range,
+ * slots past the capacity (nothing is written then), n outside [1, capacity] for reduce.
+ * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (four entries), nothing existing moved. */
+#define PMGT_EVAL_HEADER_BYTES 64
+/* pmgt/pmgt/trainer.py:162-195: the storage `outputs` of the validation epoch would take; < 0 for a capacity outside 1 .. 2^26 */
+int64_t pmgt_eval_workspace_bytes(int64_t capacity);
+/* pmgt/pmgt/trainer.py:162-195: start of a validation epoch -- zeroes the scalars (loss accumulator, NaN counter, last result) */
+int pmgt_eval_reset(void* workspace, int64_t capacity, void* stream);
+/* pmgt/pmgt/trainer.py:162-195, one validation step: score = 1.0f / (1.0f + expf(-logit)) (accurate expf), key and label != 0 of logits /
+ * labels [n] (device fp32) go to slots offset .. offset + n; the key is the order-preserving uint32 image of the score with -0.0f folded
+ * onto +0.0f; a NaN score gets no key and counts in scalar [4].  loss (device fp32 scalar, or NULL): acc += (double)loss * n_targets, rounded
+ * as the host's `loss_sum += loss.item() * len(batch)`.  offset, n, n_targets are host integers (the sampler knows them). */
+int pmgt_eval_append(void* workspace, int64_t capacity, const float* logits, const float* labels, const float* loss, int64_t offset,
+                     int64_t n, int64_t n_targets, void* stream);
+/* pmgt/pmgt/trainer.py:162-195, epoch end: sorts the keys of slots 0 .. n and writes the Mann-Whitney statistic with midranks in exact
+ * integers, twoU = sum over tie groups of p (2 neg_below + q) (p / q = positives / negatives of the group, neg_below = negatives in all lower
+ * groups), with n_pos and n_neg.  Bit-reproducible, independent of launch geometry; the slot-order arrays are left as they are, so a
+ * reduce can be repeated or follow further appends.  One launch of one workgroup up to 4 096 predictions (the size switch: include/pmgt_ops.h
+ * exports it), the multi-tile radix path above. */
+int pmgt_eval_reduce(void* workspace, int64_t capacity, int64_t n, void* stream);
+
 /* Gradient-ready notification for the data-parallel exchange (replaces DDP's autograd hooks + buckets,
  * pmgt/base_trainer.py:309-322 -> pl.Trainer(gpus=N)): during a backward pass the engine calls cb(user, offset, numel) on
  * the CALLING host thread right after it has enqueued the last launch that writes grads[offset, offset + numel) -- i.e.

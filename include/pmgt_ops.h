@@ -222,6 +222,13 @@ int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const 
 int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                           float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                           const pmgt_step_guard* guard, void* stream);
+/* The append entry of the validation metrics in pmgt_capi.h, on ready scores: no sigmoid, everything else the same (negative, subnormal, infinite and NaN scores reach
+ * the key function as they are) */
+int pmgt_op_eval_append_scores(void* workspace, int64_t capacity, const float* scores, const float* labels, const float* loss, int64_t offset,
+                               int64_t n, int64_t n_targets, void* stream);
+/* size switch of pmgt_eval_reduce: up to this many predictions one workgroup sorts in LDS (it is that workgroup's element count too);
+ * more take the multi-tile radix path */
+int pmgt_op_eval_small_max(void);
 /* out [n] = lr * lambda of steps first_step .. first_step + n - 1: the device function of the scheduled step, one launch */
 int pmgt_op_lr_schedule(const pmgt_lr_schedule* sched, float lr, int64_t first_step, int n, float* out, void* stream);
 /* weight mirror: per descriptor, W = params[src ..] [rows, cols] copied as dtype to mirror[dst ..], transposed to mirror[dst_t ..] and

@@ -91,6 +91,7 @@ HIP_SYMBOLS = [
     "pmgt_encode_feats", "pmgt_encode_train", "pmgt_encode_backward", "pmgt_optimizer_step", "pmgt_optimizer_step_scheduled", "pmgt_optimizer_step_guarded", "pmgt_profile_begin",
     "pmgt_profile_end", "pmgt_profile_sequence", "pmgt_profile_records", "pmgt_cast_from_f32", "pmgt_cast_to_f32", "pmgt_quantize_e4m3", "pmgt_dequantize_e4m3",
     "pmgt_engine_set_grad_ready_callback", "pmgt_engine_set_option", "pmgt_engine_get_option",
+    "pmgt_eval_workspace_bytes", "pmgt_eval_reset", "pmgt_eval_append", "pmgt_eval_reduce",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -102,7 +103,7 @@ OPS_SYMBOLS = [
     "pmgt_op_seg_part_elems", "pmgt_op_seg_sum", "pmgt_op_pair_offsets", "pmgt_op_nfr_compact", "pmgt_op_gsr", "pmgt_op_nfr_diff_parts",
     "pmgt_op_nfr_diff", "pmgt_op_loss_finish", "pmgt_op_scatter_rows", "pmgt_op_adamw", "pmgt_op_mirror",
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
-    "pmgt_op_adamw_guarded",
+    "pmgt_op_adamw_guarded", "pmgt_op_eval_append_scores", "pmgt_op_eval_small_max",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -224,6 +225,13 @@ def hip():
     L.pmgt_op_nfr_generate.argtypes = [vp, i, i, i, f, f, vp, vp, vp, vp]
     L.pmgt_op_build_need_rows.argtypes = [i, i, i, vp, vp, vp, vp, vp, i64, vp]
     L.pmgt_op_dropout_keep.argtypes = [vp, f, u32, i, i, vp, vp]
+    L.pmgt_eval_workspace_bytes.restype = i64
+    L.pmgt_eval_workspace_bytes.argtypes = [i64]
+    L.pmgt_eval_reset.argtypes = [vp, i64, vp]
+    L.pmgt_eval_append.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp]
+    L.pmgt_eval_reduce.argtypes = [vp, i64, i64, vp]
+    L.pmgt_op_eval_append_scores.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp]
+    L.pmgt_op_eval_small_max.argtypes = []
     _hip = L
     return L
 

@@ -542,18 +542,67 @@ def roc_auc_score(labels: np.ndarray, scores: np.ndarray) -> float:
     return float((r[labels].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
 
 
+EVAL_PINNED_SLOTS = 4      # evaluate(metrics="device"): pinned batch buffers in flight
+
+
+def _evaluate_device(engine, sampler, mine: np.ndarray, batch_size: int, threads: int, seed: int, rank: int, ws: int):
+    """evaluate(metrics="device"): the same batches through pinned host buffers and non-blocking copies, scores / labels / loss kept on the
+    device by a ValidationMetrics.  Nothing in the loop waits for the GPU's compute, so the sampler call of batch k + 1 runs while the GPU
+    works on batch k.  The pinned buffers form a ring of EVAL_PINNED_SLOTS: before the sampler overwrites a slot, the host waits for the
+    event behind THAT slot's own copies, EVAL_PINNED_SLOTS batches back -- back-pressure that bounds the run-ahead, not a per-batch sync."""
+    from .metrics import ValidationMetrics
+    dev = engine.device
+    vm = ValidationMetrics(dev, max(len(mine) * max(sampler.max_pairs(MODE_EVAL), 1), 1))
+    rows = max(min(int(batch_size), len(mine)), 1)
+    ring = [dict(buf=sampler.alloc(rows, MODE_EVAL, pinned=True), copied=None) for _ in range(EVAL_PINNED_SLOTS)]
+    for k, lo in enumerate(range(0, len(mine), batch_size)):
+        tg = mine[lo: lo + batch_size]
+        slot = ring[k % EVAL_PINNED_SLOTS]
+        if slot["copied"] is not None:
+            slot["copied"].synchronize()
+        tgt, pair, num_pairs, labels = sampler.batch(tg, MODE_EVAL, out=slot["buf"], threads=threads, base_seed=seed, counter=rank + ws * lo,
+                                                      counter_stride=ws)
+        cu = lambda d: {k_: v.to(dev, non_blocking=True) for k_, v in d.items()}
+        labels_dev = labels.to(dev, non_blocking=True)
+        batch = (cu(tgt), cu(pair), num_pairs.to(dev, non_blocking=True), labels_dev)
+        slot["copied"] = torch.cuda.Event()
+        slot["copied"].record()
+        out = engine.pretrain_step(batch, training=False, want_hidden=False)
+        vm.update(out["logits"], labels_dev, out["loss"], len(tg))
+    n_total = len(mine)
+    if ws > 1:
+        import torch.distributed as dist
+        preds, labs = gather_predictions(vm.scores(), vm.labels())       # one transfer per validation, not one per batch
+        parts = [None] * ws
+        dist.all_gather_object(parts, (vm.loss_sum(), n_total))
+        loss_sum, n_total = sum(p[0] for p in parts), sum(p[1] for p in parts)
+        vm = ValidationMetrics(dev, max(len(preds), 1))
+        if len(preds):
+            vm.update_scores(torch.from_numpy(preds).to(dev), torch.from_numpy(labs).to(dev))
+        return {"loss/val": float(loss_sum / max(n_total, 1)), "val/auc": vm.result()["val/auc"]}
+    return vm.result()
+
+
 @torch.no_grad()
 def evaluate(engine, sampler, node_ids: np.ndarray, batch_size: int = 256, threads: int = 8, seed: int = 0,
-             distributed: bool = False):
+             distributed: bool = False, metrics: str = "host"):
     """Validation pass (pmgt/pmgt/trainer.py:162-195): eval-mode forward with 1 positive + 1 negative
     per target, sigmoid(logits) vs labels -> {'loss/val', 'val/auc'}.  `loss/val` is the mean of the per-batch losses
     (what `self.log("loss/val", ...)` aggregates over an epoch, weighted by batch size).  distributed=True under an
     initialised process group: rank r evaluates node_ids[r::W] and the predictions of all ranks are gathered, so every
     rank reports the same AUC over the whole validation set (the reference's AUC is per rank: no sync_dist); every node
-    draws from the stream of its GLOBAL index, so the result equals the single-process evaluation of the same list."""
+    draws from the stream of its GLOBAL index, so the result equals the single-process evaluation of the same list.
+    metrics="host" (default): predictions and the loss are copied to the host after every batch and roc_auc_score runs there.
+    metrics="device": they stay on the device (pmgt_amd.metrics.ValidationMetrics: sigmoid, loss accumulation, sort and the Mann-Whitney
+    statistic in HIP) and one small copy at the end fetches the result; `loss/val` is bit-identical to the host path, `val/auc` is
+    roc_auc_score of the scores the device computed, exactly (its sigmoid may differ from torch's in the last bit)."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
     node_ids = np.asarray(node_ids)
     rank, ws = world() if distributed else (0, 1)
     mine = node_ids[rank::ws]
+    if metrics == "device":
+        return _evaluate_device(engine, sampler, mine, batch_size, threads, seed, rank, ws)
     preds, labs = [np.empty(0, np.float32)], [np.empty(0, np.float32)]
     loss_sum = 0.0
     for lo in range(0, len(mine), batch_size):
@@ -691,7 +740,7 @@ def epoch_order(n: int, seed: int, epoch: int, rank: int = 0, world_size: int = 
 def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid_ids: np.ndarray, batch_size: int, max_epochs: int,
         early_criterion: str = "loss", patience: int = 10, ckpt_dir: str = ".", resume_from: Optional[str] = None,
         save_every_n_steps: int = 0, seed: int = 0, graphs: bool = False, threads: int = 8, valid_batch_size: int = 256, log=None,
-        nonfinite="keep", step_log="keep", max_skipped_in_a_row="keep") -> dict:
+        nonfinite="keep", step_log="keep", max_skipped_in_a_row="keep", eval_metrics: str = "host") -> dict:
     """pl.Trainer.fit as the reference's init_run configures it, restated: `max_epochs` epochs; epoch e trains on this rank's shard of
     a permutation of `train_ids` seeded by (seed, e) -- the len // batch_size full batches through run_live, a remainder as one eager
     train_step of its true size (DataLoader drop_last=False), an unfinished accumulation window stepped at the end of the epoch as
@@ -708,6 +757,8 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     (NaN when there is none; a resume empties the ring).  Trainer.check_nonfinite runs at the end of every run of training steps, at the
     end of an epoch and before every checkpoint write: a run that trips it stops with NonFiniteGradientsError BEFORE that write, so the
     previous last.ckpt stays.
+    eval_metrics: "host" (default) or "device", passed to evaluate(metrics=...) for the validation after every epoch.  Not part of the training
+    state: a checkpoint written under one setting resumes under the other.
     Returns {best_model_path, best_model_score, epochs_run, stopped_early, history: per-epoch metrics}."""
     import os
 
@@ -715,6 +766,8 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     eng = trainer.engine
     if getattr(model_or_engine, "engine", model_or_engine) is not eng:
         raise ValueError("fit: the trainer drives another engine than the one passed")
+    if eval_metrics not in ("host", "device"):
+        raise ValueError(f"eval_metrics={eval_metrics!r}: expected 'host' or 'device'")
     passed = {k: v for k, v in (("nonfinite", nonfinite), ("step_log", step_log), ("max_skipped_in_a_row", max_skipped_in_a_row)) if v != "keep"}
     if passed:
         checked = Trainer(None, **passed)                 # the constructor's argument checks
@@ -789,7 +842,8 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
             if trainer.step_log:
                 mine = [r["loss"] for r in eng.step_log() if r["attempt"] >= at_epoch_start["attempts"] and not r["skipped"]]
                 train_metrics["loss/train"] = float(np.mean(mine)) if mine else float("nan")
-        metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1)
+        metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1,
+                           metrics=eval_metrics)
         history.append(dict(epoch=epoch, **metrics, **train_metrics))
         top_epoch = epoch
         new_best, old_best = best.update(epoch, metrics[monitor])
