@@ -177,8 +177,11 @@ typedef struct pmgt_lr_schedule {
     int type; /* PMGT_LR_* */
     int64_t num_warmup_steps, num_training_steps;
 } pmgt_lr_schedule;
-/* pmgt_optimizer_step with the schedule: a->scalars is device [8] here and receives lr_t / bc1 in [1] and lr_t in [4] ([5..7]
- * are not written); the weight decay uses lr_t too.  a->step is the schedule's position as well as Adam's.  Refused (-2): an unknown
+/* pmgt_optimizer_step with the schedule; the weight decay uses lr_t too.  a->step is the schedule's position as well as Adam's.
+ * a->scalars is device [8] here -- THE scal [8] LAYOUT of this entry, pmgt_optimizer_step_guarded and the pmgt_op_adamw_scheduled /
+ * _guarded entries of pmgt_ops.h: [0] clip coefficient, [1] lr_t / bc1, [2] 1 / sqrt(bc2), [3] total gradient norm (pre-clip), [4] lr_t,
+ * [5] guarded entries only: 1 when the step was skipped, else 0; [6..7] never touched.  The unguarded entries neither read nor write
+ * [5] either.  Refused (-2): a NULL schedule, an unknown
  * type, num_warmup_steps < 0, num_training_steps <= 0 for linear / cosine / cosine_with_restarts / polynomial, polynomial with
  * lr <= 1e-7 or num_training_steps <= num_warmup_steps.  Three launches, as the unscheduled step (norm partials, prepare, AdamW); the
  * per-phase timers do not bracket this entry. */
@@ -205,10 +208,10 @@ typedef struct pmgt_step_guard {
     const float* loss;
     int skip_nonfinite;
 } pmgt_step_guard;
-/* pmgt_optimizer_step_scheduled (sched = NULL: constant a->lr, then pmgt_optimizer_step bit for bit) with the guard.  a->scalars is
- * device [8]: [0..4] as the scheduled step on an applied step, [5] = 1 when the step was skipped, else 0.  A skipped step touches no
- * parameter or moment, does NOT advance *a->step (bias corrections and schedule count applied steps), and writes [0] = 0, [3] = the
- * non-finite norm, [4] = the rate it would have used.  Refused (-2): what pmgt_optimizer_step_scheduled refuses, a NULL guard or
+/* pmgt_optimizer_step_scheduled (sched = NULL: constant a->lr, then pmgt_optimizer_step bit for bit) with the guard; a->scalars as
+ * there, [0..4] bit for bit on an applied step.  A skipped step touches no parameter or moment, does NOT advance *a->step (bias
+ * corrections and schedule count applied steps), and writes [0] = 0, [3] = the non-finite norm, [4] = the rate it would have used,
+ * [1] and [2] not at all.  Refused (-2): what pmgt_optimizer_step_scheduled refuses of a schedule that is given, a NULL guard or
  * counters, log_rows < 0, log_rows > 0 with a NULL log pointer.  The same three launches, no sync, no allocation: capturable.
  * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (one struct, one entry), nothing existing moved. */
 int pmgt_optimizer_step_guarded(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched,

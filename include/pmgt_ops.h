@@ -212,13 +212,13 @@ int pmgt_op_scatter_rows(int dtype, const void* src, const int64_t* rows, const 
  * lr / bc1, 1 / sqrt(bc2), gradient norm; part: 1024 floats of scratch */
 int pmgt_op_adamw(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1, float b2,
                   float eps, float max_norm, int64_t* step, float* scal, float* part, void* stream);
-/* the same with a learning-rate schedule (pmgt_lr_schedule, pmgt_capi.h) evaluated on the device from *step: scal is [8] here,
- * [1] = lr_t / bc1, [4] = lr_t = lr * lambda of the steps completed before this one, [5..7] not written */
+/* the same with a learning-rate schedule (pmgt_lr_schedule, pmgt_capi.h) evaluated on the device from *step; scal is [8] here, laid out as
+ * pmgt_optimizer_step_scheduled states (lr_t = lr * lambda of the steps completed before this one) */
 int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                             float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                             void* stream);
 /* the same behind the step guard (pmgt_step_guard, pmgt_capi.h); sched may be NULL (constant lr: pmgt_op_adamw bit for bit on an applied
- * step); scal [8], [5] = 1 when the step was skipped */
+ * step); scal [8] of the same layout */
 int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                           float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                           const pmgt_step_guard* guard, void* stream);

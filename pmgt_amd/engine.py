@@ -84,6 +84,8 @@ class Engine:
         # the log ring is created by ensure_step_log
         self.step_counters_dev = torch.zeros(4, dtype=torch.int64, device=self.device)
         self.step_log_f = self.step_log_i = None
+        self._live_graphs = 0         # captured steps alive (Trainer.capture_step counts them): options and the step log are frozen meanwhile
+        self._hook_error = None       # what the gradient-ready hook raised, until _raise_hook_error re-raises it
 
     def __del__(self):
         try:
@@ -142,7 +144,7 @@ class Engine:
         `check_carrier_every` optimizer steps and before a step is captured into a graph."""
         worst = self.layernorm_carrier_ratio()
         if worst > self.LN_CARRIER_MAX_RATIO and not self.get_option("store_ln_input"):
-            if getattr(self, "_live_graphs", 0) > 0:
+            if self._live_graphs > 0:
                 raise RuntimeError(f"pmgt_amd: LayerNorm |beta / gamma| reaches {worst:.1f}, so the backward must switch to stored "
                                    "LayerNorm inputs, but captured steps of this engine are alive and keep the old kernels: call "
                                    "Trainer.drop_captured_steps() (run_live does it by itself) and capture again")
@@ -154,7 +156,7 @@ class Engine:
 
     # ---- path options (include/pmgt_ops.h): state of THIS engine, not of the process ----------------
     def set_option(self, key: str, value) -> None:
-        if getattr(self, "_live_graphs", 0) > 0 and bool(value) != self.get_option(key):
+        if self._live_graphs > 0 and bool(value) != self.get_option(key):
             # a captured step keeps the kernels it was captured with, while the workspace would be re-carved for the new option
             raise RuntimeError(f"pmgt_amd: option {key!r} cannot change while a captured step of this engine is alive "
                                "(drop the replay handle first)")
@@ -385,7 +387,7 @@ class Engine:
             return
         if rows < 0:
             raise ValueError(f"step log of {rows} rows")
-        if torch.cuda.is_current_stream_capturing() or getattr(self, "_live_graphs", 0) > 0:
+        if torch.cuda.is_current_stream_capturing() or self._live_graphs > 0:
             raise RuntimeError(f"pmgt_amd: the step log ({have} -> {rows} rows) must exist before a step is captured and cannot change "
                                "while captured steps are alive (call Engine.ensure_step_log(rows) first)")
         if rows == 0:
@@ -529,7 +531,7 @@ class Engine:
         self.lib.pmgt_engine_set_grad_ready_callback(self.h, self._grad_cb, None)
 
     def _raise_hook_error(self):
-        err, self._hook_error = getattr(self, "_hook_error", None), None
+        err, self._hook_error = self._hook_error, None
         if err is not None:
             raise err
 

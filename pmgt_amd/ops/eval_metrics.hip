@@ -1,7 +1,7 @@
 // Validation loss and ROC AUC on the device (pmgt_eval_* of include/pmgt_capi.h; pmgt_op_eval_* of include/pmgt_ops.h): what
 // `_validation_and_test_step` / `_valid_and_test_epoch_end` compute on the host (pmgt/pmgt/trainer.py:162-195: sigmoid(logits) and labels
 // collected per batch, the batch loss weighted by its size, sklearn's roc_auc_score at the end), without a device-to-host copy per batch.
-// Kept out of csrc/ for lr_schedule.hip's reason: the measured step launches nothing of this.
+// Kept out of csrc/ for optimizer_step.hip's reason: the measured step launches nothing of this.
 //
 // append: one thread per prediction writes score, sort key and label bit to its slot; one lane adds (double)loss * n_targets to the fp64
 //   accumulator -- a multiply and an add, each rounded once (no fused multiply-add), in batch order: the host loop's arithmetic.

@@ -1,0 +1,255 @@
+// The derived forms of the fused clip + AdamW step (csrc/optim.hip) -- scheduled, and scheduled + guarded -- as ONE kernel pair, and every
+// optimizer entry point outside csrc/: pmgt_optimizer_step_scheduled / pmgt_optimizer_step_guarded of include/pmgt_capi.h (which states the
+// scal [8] layout and the log ring), pmgt_op_adamw / pmgt_op_adamw_scheduled / pmgt_op_adamw_guarded / pmgt_op_lr_schedule of
+// include/pmgt_ops.h.
+// Scheduled: the prepare lane computes lr_t = lr * lambda(steps completed so far) from the device-side step counter, so a captured step
+// follows the schedule with no re-capture and no host write between replays.  lambda: the multipliers of transformers 4.11.2
+// optimization.py with the defaults get_scheduler leaves in place (the reference: --scheduler-type / --scheduler-warmup, train.py:38-52,
+// pmgt/base_trainer.py:71-90).
+// Guarded: what a GradScaler gives the reference under --mp-enabled (pmgt/base_trainer.py:312): a step whose gradients hold an Inf or a
+// NaN is SKIPPED.  The same lane decides it, from the global gradient norm it computes anyway, so a captured step carries the decision
+// with no host `if` between backward and optimizer; it also keeps the attempt / skip counters and one row per step of a log ring, which
+// is what a replayed run can be watched by without a host sync per step.  "Bad" = the norm is not finite: any Inf or NaN gradient
+// element, and also finite gradients whose sum of squares overflows the fp32 partials of sqnorm_part_kernel
+// (torch.nn.utils.clip_grad_norm_ on fp32 gradients reports the same Inf norm for those).
+// Kept out of csrc/: the plain step and every kernel bench.py measures (and fingerprints there) stay byte for byte what they were.  The
+// gradient-norm partials are csrc/optim.hip's own kernel, so every form is the same three launches, no sync, no allocation.
+#include "../../include/pmgt_ops.h"
+#include "../csrc/optim.h"
+
+namespace pmgt {
+
+__global__ void sqnorm_part_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part);      // csrc/optim.hip
+
+struct LrSchedule {
+    int type;                  // PMGT_LR_*
+    int64_t warmup, total;     // num_warmup_steps (W), num_training_steps (T)
+};
+
+struct StepGuard {
+    int64_t* counters;      // [4]: attempts, skipped, skipped in a row, reserved
+    float* log_f;           // [log_rows][PMGT_STEP_LOG_FLOATS] or NULL
+    int64_t* log_i;         // [log_rows][2] or NULL
+    int64_t log_rows;
+    const float* loss;      // device scalar or NULL
+    int skip_nonfinite;
+};
+
+// lr * lambda(s): LambdaLR's rate after s completed optimizer steps
+static __device__ double scheduled_lr(const LrSchedule sc, double lr, int64_t s) {
+    const double W = (double)sc.warmup, T = (double)sc.total, x = (double)s;
+    if (sc.type != PMGT_LR_CONSTANT && s < sc.warmup) return lr * (x / fmax(1.0, W));
+    const double q = (x - W) / fmax(1.0, T - W);
+    switch (sc.type) {
+        case PMGT_LR_LINEAR: return lr * fmax(0.0, (T - x) / fmax(1.0, T - W));
+        case PMGT_LR_COSINE: return lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * q)));                                  // half a cycle
+        case PMGT_LR_COSINE_WITH_RESTARTS: return q >= 1.0 ? 0.0 : lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * fmod(q, 1.0))));      // one cycle
+        case PMGT_LR_POLYNOMIAL: return lr * ((s > sc.total ? 1e-7 : (lr - 1e-7) * (1.0 - (x - W) / (T - W)) + 1e-7) / lr);    // power 1, lr_end 1e-7
+        default: return lr;                                                                                      // constant, constant_with_warmup
+    }
+}
+
+// adam_prepare_kernel of csrc/optim.hip with lr_t for lr: fp64, rounded once per slot.  Guarded adds the decision, the counters and the
+// log row; a skipped step leaves step[0], scal[1] and scal[2] alone (the bias corrections and the schedule count applied steps only) and
+// reports the rate it would have used.  The unguarded form neither reads nor writes scal[5..7], nor gd.
+template <bool Guarded>
+__global__ __launch_bounds__(64) void adam_prepare_step_kernel(const float* __restrict__ part, int nparts, float max_norm, float lr, float b1,
+                                                               float b2, int64_t* __restrict__ step, float* __restrict__ scal,
+                                                               const LrSchedule sched, const StepGuard gd) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 64) s += (double)part[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(s);
+    bool bad = false, skip = false;
+    if constexpr (Guarded) {
+        bad = !isfinite(norm);
+        skip = bad && gd.skip_nonfinite != 0;
+    }
+    int64_t t = step[0];
+    double coef = 0.0, lr_t;
+    if (skip) {
+        lr_t = scheduled_lr(sched, (double)lr, t);
+        scal[0] = 0.f;
+    } else {
+        t += 1;
+        step[0] = t;
+        coef = 1.0;
+        if (max_norm > 0.f) coef = fmin((double)max_norm / (norm + 1e-6), 1.0);
+        const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+        lr_t = scheduled_lr(sched, (double)lr, t - 1);
+        scal[0] = (float)coef;
+        scal[1] = (float)(lr_t / bc1);
+        scal[2] = (float)(1.0 / sqrt(bc2));
+    }
+    scal[3] = (float)norm;
+    scal[4] = (float)lr_t;
+    if constexpr (Guarded) {
+        scal[5] = skip ? 1.f : 0.f;
+        const int64_t attempt = gd.counters[0];
+        gd.counters[0] = attempt + 1;
+        if (skip) {
+            gd.counters[1] += 1;
+            gd.counters[2] += 1;
+        } else {
+            gd.counters[2] = 0;
+        }
+        if (gd.log_rows > 0) {
+            const int64_t r = attempt % gd.log_rows;
+            float* f = gd.log_f + r * PMGT_STEP_LOG_FLOATS;
+            f[0] = gd.loss ? gd.loss[0] : __builtin_nanf("");
+            f[1] = (float)norm;
+            f[2] = (float)coef;
+            f[3] = (float)lr_t;
+            f[4] = skip ? 1.f : (bad ? 2.f : 0.f);
+            gd.log_i[r * 2 + 0] = attempt;
+            gd.log_i[r * 2 + 1] = t;
+        }
+    }
+}
+
+// adamw_kernel of csrc/optim.hip, the same fp32 arithmetic in the same order, with the decay term's rate read from scal[4].  Guarded sits
+// behind the skipped flag: scal[5] is one value for the whole grid, so the branch is uniform and a skipped step moves no parameter byte.
+template <bool Guarded>
+__global__ __launch_bounds__(256) void adamw_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, const uint8_t* __restrict__ decay, int64_t n, float wd,
+                                                         float b1, float b2, float eps, const float* __restrict__ scal) {
+    if constexpr (Guarded) {
+        if (scal[5] != 0.f) return;
+    }
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float coef = scal[0], step_size = scal[1], inv_sqrt_bc2 = scal[2], lr = scal[4];
+    const int cnt = (int)min((int64_t)4, n - i);
+    for (int k = 0; k < cnt; ++k) {
+        const int64_t j = i + k;
+        const float gg = g[j] * coef;
+        float pp = p[j] * (1.f - lr * (decay[j] ? wd : 0.f));
+        const float mm = m[j] * b1 + gg * (1.f - b1);
+        const float vv = v[j] * b2 + gg * gg * (1.f - b2);
+        const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
+        pp -= step_size * (mm / denom);
+        p[j] = pp; m[j] = mm; v[j] = vv;
+    }
+}
+
+__global__ __launch_bounds__(256) void lr_schedule_kernel(const LrSchedule sched, float lr, int64_t first_step, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (float)scheduled_lr(sched, (double)lr, first_step + i);
+}
+
+// adamw_step of csrc/optim.hip: norm partials -> prepare -> AdamW, three launches; gd = NULL: the scheduled form, else the guarded one
+static int adamw_step_derived(const AdamArgs& a, const LrSchedule& sched, const StepGuard* gd, hipStream_t st) {
+    if (a.n <= 0) return 0;
+    const int nparts = (int)std::min<int64_t>(1024, cdiv64(a.n, 1024));
+    const auto prepare = gd ? adam_prepare_step_kernel<true> : adam_prepare_step_kernel<false>;
+    const auto update = gd ? adamw_step_kernel<true> : adamw_step_kernel<false>;
+    hipLaunchKernelGGL(sqnorm_part_kernel, dim3(nparts), dim3(256), 0, st, a.g, a.n, a.part);
+    PMGT_LAUNCH_OK();
+    hipLaunchKernelGGL(prepare, dim3(1), dim3(64), 0, st, a.part, nparts, a.max_norm, a.lr, a.b1, a.b2, a.step, a.scal, sched,
+                       gd ? *gd : StepGuard{});
+    PMGT_LAUNCH_OK();
+    hipLaunchKernelGGL(update, dim3((unsigned)cdiv64(cdiv64(a.n, 4), 256)), dim3(256), 0, st, a.p, a.g, a.m, a.v, a.decay, a.n, a.wd, a.b1, a.b2,
+                       a.eps, a.scal);
+    PMGT_LAUNCH_OK();
+    return 0;
+}
+
+// null_is_constant: a NULL schedule is the constant rate (lambda = 1, so lr_t = (double)lr and the step is pmgt_optimizer_step's bit for bit)
+static int schedule_from(const pmgt_lr_schedule* in, bool null_is_constant, float lr, const char* who, LrSchedule* out) {
+    if (in == nullptr && null_is_constant) {
+        *out = LrSchedule{PMGT_LR_CONSTANT, 0, 0};
+        return 0;
+    }
+    PMGT_CHECK(in != nullptr, -2, "%s: NULL schedule", who);
+    const long long W = in->num_warmup_steps, T = in->num_training_steps;
+    PMGT_CHECK(in->type >= PMGT_LR_CONSTANT && in->type <= PMGT_LR_POLYNOMIAL, -2, "%s: unknown lr schedule type %d", who, in->type);
+    PMGT_CHECK(W >= 0, -2, "%s: num_warmup_steps = %lld is negative", who, W);
+    PMGT_CHECK(in->type < PMGT_LR_LINEAR || T > 0, -2, "%s: this lr schedule needs num_training_steps > 0 (got %lld)", who, T);
+    if (in->type == PMGT_LR_POLYNOMIAL) {
+        PMGT_CHECK((double)lr > 1e-7, -2, "%s: polynomial lr schedule: lr_end (1e-07) must be smaller than the initial lr (%g)", who, (double)lr);
+        PMGT_CHECK(T > W, -2, "%s: polynomial lr schedule needs num_training_steps (%lld) > num_warmup_steps (%lld)", who, T, W);
+    }
+    *out = LrSchedule{in->type, in->num_warmup_steps, in->num_training_steps};
+    return 0;
+}
+
+static int guard_from(const pmgt_step_guard* in, const char* who, StepGuard* out) {
+    PMGT_CHECK(in != nullptr, -2, "%s: NULL guard", who);
+    PMGT_CHECK(in->counters != nullptr, -2, "%s: NULL guard counters", who);
+    PMGT_CHECK(in->log_rows >= 0, -2, "%s: log_rows = %lld is negative", who, (long long)in->log_rows);
+    PMGT_CHECK(in->log_rows == 0 || (in->log_f && in->log_i), -2, "%s: log_rows = %lld but a log pointer is NULL", who, (long long)in->log_rows);
+    *out = StepGuard{in->counters, in->log_f, in->log_i, in->log_rows, in->loss, in->skip_nonfinite};
+    return 0;
+}
+
+// the loose argument list of the pmgt_op_adamw* entries is AdamArgs' field order
+static AdamArgs adam_args(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1, float b2,
+                          float eps, float max_norm, int64_t* step, float* scal, float* part) {
+    return AdamArgs{p, g, m, v, decay, n, lr, wd, b1, b2, eps, max_norm, step, scal, part};
+}
+static bool adam_ptrs_ok(const pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a) {
+    return e && t && a && t->params && t->grads && a->exp_avg && a->exp_avg_sq && a->decay && a->step && a->scalars && a->scratch;
+}
+static AdamArgs adam_args(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a) {
+    return adam_args(t->params, t->grads, a->exp_avg, a->exp_avg_sq, a->decay, pmgt_param_count(e), a->lr, a->weight_decay, a->beta1, a->beta2,
+                     a->eps, a->max_grad_norm, a->step, a->scalars, a->scratch);
+}
+
+}  // namespace pmgt
+
+using namespace pmgt;
+
+extern "C" {
+
+int pmgt_optimizer_step_scheduled(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched, void* stream) {
+    PMGT_CHECK(adam_ptrs_ok(e, t, a) && sched, -2, "pmgt_optimizer_step_scheduled: NULL argument");
+    LrSchedule s;
+    if (int rc = schedule_from(sched, false, a->lr, "pmgt_optimizer_step_scheduled", &s)) return rc;
+    return adamw_step_derived(adam_args(e, t, a), s, nullptr, (hipStream_t)stream);
+}
+
+int pmgt_optimizer_step_guarded(pmgt_engine* e, const pmgt_tensors* t, const pmgt_adam* a, const pmgt_lr_schedule* sched,
+                                const pmgt_step_guard* guard, void* stream) {
+    PMGT_CHECK(adam_ptrs_ok(e, t, a), -2, "pmgt_optimizer_step_guarded: NULL argument");
+    LrSchedule s;
+    if (int rc = schedule_from(sched, true, a->lr, "pmgt_optimizer_step_guarded", &s)) return rc;
+    StepGuard gd;
+    if (int rc = guard_from(guard, "pmgt_optimizer_step_guarded", &gd)) return rc;
+    return adamw_step_derived(adam_args(e, t, a), s, &gd, (hipStream_t)stream);
+}
+
+int pmgt_op_adamw(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1, float b2,
+                  float eps, float max_norm, int64_t* step, float* scal, float* part, void* stream) {
+    return adamw_step(adam_args(p, g, m, v, decay, n, lr, wd, b1, b2, eps, max_norm, step, scal, part), (hipStream_t)stream);
+}
+
+int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
+                            float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
+                            void* stream) {
+    LrSchedule s;
+    if (int rc = schedule_from(sched, false, lr, "pmgt_op_adamw_scheduled", &s)) return rc;
+    return adamw_step_derived(adam_args(p, g, m, v, decay, n, lr, wd, b1, b2, eps, max_norm, step, scal, part), s, nullptr, (hipStream_t)stream);
+}
+
+int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
+                          float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
+                          const pmgt_step_guard* guard, void* stream) {
+    LrSchedule s;
+    if (int rc = schedule_from(sched, true, lr, "pmgt_op_adamw_guarded", &s)) return rc;
+    StepGuard gd;
+    if (int rc = guard_from(guard, "pmgt_op_adamw_guarded", &gd)) return rc;
+    return adamw_step_derived(adam_args(p, g, m, v, decay, n, lr, wd, b1, b2, eps, max_norm, step, scal, part), s, &gd, (hipStream_t)stream);
+}
+
+int pmgt_op_lr_schedule(const pmgt_lr_schedule* sched, float lr, int64_t first_step, int n, float* out, void* stream) {
+    LrSchedule s;
+    if (int rc = schedule_from(sched, false, lr, "pmgt_op_lr_schedule", &s)) return rc;
+    PMGT_CHECK(out || n <= 0, -2, "pmgt_op_lr_schedule: NULL output");
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(lr_schedule_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, s, lr, first_step, n, out);
+    PMGT_LAUNCH_OK();
+    return 0;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // Single-kernel entry points (include/pmgt_ops.h) of the row kernels of the training step: the embedding mix, the per-node segment sums,
-// the loss heads and the optimizer.  Host code only: each entry fills the argument struct and calls the host function the engine calls, so
-// a test sees the engine's own dispatch.  (Kept out of csrc/: bench.py fingerprints the kernel sources there, and these entries launch
-// nothing of their own.)
+// the loss heads and the weight mirror (the optimizer's entries: optimizer_step.hip).  Host code only: each entry fills the argument struct
+// and calls the host function the engine calls, so a test sees the engine's own dispatch.  (Kept out of csrc/: bench.py fingerprints the
+// kernel sources there, and these entries launch nothing of their own.)
 #include <vector>
 
 #include "../../include/pmgt_ops.h"
@@ -101,13 +101,6 @@ int pmgt_op_scatter_rows(int dtype, const void* src, const int64_t* rows, const 
     return scatter_rows<float>((const float*)src, rows, count, cap, d, (float*)dst, (hipStream_t)stream, add != 0);
 }
 
-int pmgt_op_adamw(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1, float b2,
-                  float eps, float max_norm, int64_t* step, float* scal, float* part, void* stream) {
-    AdamArgs a;
-    a.p = p; a.g = g; a.m = m; a.v = v; a.decay = decay; a.n = n; a.lr = lr; a.wd = wd; a.b1 = b1; a.b2 = b2; a.eps = eps;
-    a.max_norm = max_norm; a.step = step; a.scal = scal; a.part = part;
-    return adamw_step(a, (hipStream_t)stream);
-}
 static int mirror_from_host(int dtype, const float* params, void* mirror, const MirrorDesc* h, MirrorDesc* dev, int ndesc, int total_tiles,
                             hipStream_t st) {
     PMGT_HIP(hipMemcpyAsync(dev, h, sizeof(MirrorDesc) * (size_t)ndesc, hipMemcpyHostToDevice, st));

@@ -78,7 +78,12 @@ class Trainer:
         self.accum = max(1, accumulate_grad_batches)
         self.random_node_ratio, self.mask_node_ratio = random_node_ratio, mask_node_ratio
         self.last_loss = None
+        self.last_outputs = None      # the output set of the last training_step
         self._micro = 0
+        self._capturing = False       # inside capture_step's stream capture: the step writes an output set of its own
+        # run_live: pinned host + device slot buffers by shape, and (slot buffers, shape, hyper-parameters) -> captured step; both live
+        # as long as the trainer
+        self._live_slots, self._live_replays = {}, {}
         # every N optimizer steps re-check that the LayerNorm parameters still allow x^ = (y - beta) / gamma from the bf16 output
         # (Engine.check_layernorm_carrier: one small device -> host read per LayerNorm; 0 = only when parameters are loaded or a
         # step is captured)
@@ -117,7 +122,7 @@ class Trainer:
             self._exchange.enabled = (self.world_size > 1 or self.force_exchange) and self._micro == self.accum - 1
         out = self.engine.pretrain_step(batch, training=True, backward=True, accumulate=self._micro > 0,
                                         random_node_ratio=self.random_node_ratio, mask_node_ratio=self.mask_node_ratio,
-                                        want_hidden=False, private_outputs=getattr(self, "_capturing", False))
+                                        want_hidden=False, private_outputs=self._capturing)
         self.last_loss = out["loss"]
         self.last_outputs = out
         return out["loss"]
@@ -135,7 +140,7 @@ class Trainer:
         eng.optimizer_step(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
                            max_grad_norm=self.max_grad_norm, schedule=self._schedule(), guard=self._guard())
         self._opt_steps += 1
-        if self.check_carrier_every and self._opt_steps % self.check_carrier_every == 0 and not getattr(self, "_capturing", False):
+        if self.check_carrier_every and self._opt_steps % self.check_carrier_every == 0 and not self._capturing:
             self._check_carrier()
 
     def _check_carrier(self):
@@ -146,7 +151,7 @@ class Trainer:
         error, which names the remedy."""
         eng = self.engine
         flips = eng.layernorm_carrier_ratio() > eng.LN_CARRIER_MAX_RATIO and not eng.get_option("store_ln_input")
-        if flips and getattr(eng, "_live_graphs", 0) > 0 and self.__dict__.get("_live_replays"):
+        if flips and eng._live_graphs > 0 and self._live_replays:
             import gc
             self.drop_captured_steps()
             gc.collect()
@@ -208,7 +213,7 @@ class Trainer:
             return loss
         import weakref
         eng = self.engine
-        eng._live_graphs = getattr(eng, "_live_graphs", 0) + 1      # Engine.set_option refuses changes while a captured step lives
+        eng._live_graphs += 1      # Engine.set_option refuses changes while a captured step lives
         weakref.finalize(graph, lambda: setattr(eng, "_live_graphs", eng._live_graphs - 1))
         replay.graph = graph
         replay.outputs = outputs          # loss / logits / nfr_count the replays write (kept alive with the graph)
@@ -257,10 +262,9 @@ class Trainer:
         """Forgets every step run_live(graphs=True) captured (call after changing lr / weight decay / clip / ratios / engine options by
         hand; run_live itself re-captures when the hyper-parameters it was captured with no longer match).  Waits for the GPU first: a
         graph must not be destroyed while a replay of it is still executing."""
-        reps = self.__dict__.get("_live_replays")
-        if reps:
+        if self._live_replays:
             torch.cuda.synchronize(self.engine.device)
-            reps.clear()
+            self._live_replays.clear()
 
     # ---- full training state: what a resume needs beyond the weights ---------------------------------------------------------
     HYPER_NAMES = ("lr", "weight_decay", "betas", "eps", "max_grad_norm", "random_node_ratio", "mask_node_ratio", "nonfinite", "step_log", "schedule")
@@ -307,7 +311,7 @@ class Trainer:
         eng.check_training_state(est)
         bad = self.hyper_mismatches(sd)
         options_differ = est.get("options") is not None and set(est["options"]) != set(eng.options_set())
-        if (bad or options_differ) and self.__dict__.get("_live_replays"):
+        if (bad or options_differ) and self._live_replays:
             import gc
             self.drop_captured_steps()
             gc.collect()
@@ -343,7 +347,7 @@ class Trainer:
         # the slots (pinned host + device buffers) live as long as the trainer: a second pass over the same shapes re-uses them -- and, with
         # graphs=True, the steps captured over them
         skey = (int(sampler.S), int(sampler.max_pairs(MODE_TRAIN)), batch_size, depth)      # shapes, not id(sampler): an id can be re-used
-        cache = self.__dict__.setdefault("_live_slots", {})
+        cache = self._live_slots
         if skey not in cache:
             sl = [sampler.alloc(batch_size, MODE_TRAIN, pinned=True) for _ in range(depth)]
             cache[skey] = (sl, [{k: torch.empty_like(v, device=dev) for k, v in s_.items()} for s_ in sl])
@@ -390,7 +394,7 @@ class Trainer:
         ev_a = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
         ev_b = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
         t_launch = 0.0
-        replays = self.__dict__.setdefault("_live_replays", {})       # (slot buffers, shape, hyper-parameters) -> captured step, kept across calls
+        replays = self._live_replays       # (slot buffers, shape, hyper-parameters) -> captured step, kept across calls
         hyper = self._hyper_key()
         if graphs and any(k[-1] != hyper for k in replays):
             self.drop_captured_steps()       # lr / weight decay / clip / ratios changed since the capture: those are frozen kernel arguments

@@ -1,6 +1,6 @@
-"""The guarded optimizer step (pmgt_amd/ops/guarded_step.hip: adam_prepare_guarded_kernel, adamw_guarded_kernel) from the single-kernel
-entry up to captured steps, checkpoints and fit: a step whose global gradient norm is not finite is skipped on the device, every step is
-counted, and a device ring keeps one row per step.
+"""The guarded optimizer step (pmgt_amd/ops/optimizer_step.hip: the guarded instantiation of adam_prepare_step_kernel / adamw_step_kernel)
+from the single-kernel entry up to captured steps, checkpoints and fit: a step whose global gradient norm is not finite is skipped on the
+device, every step is counted, and a device ring keeps one row per step.
 
 Bounds.  Everything here is bit-exact (torch.equal, ==): an applied guarded step is the unguarded step's arithmetic in the same order, a
 skipped one writes no parameter byte, and the log copies fp32 values the step computed anyway.  An Inf or NaN float is ordinary data to
@@ -45,10 +45,10 @@ def same_bits(a, b):
 
 # =========================================================================================== the single-kernel entry
 class OpState:
-    """p, g-independent optimizer state of one op run, with the guard's buffers."""
+    """p, g-independent optimizer state of one op run over n elements, with the guard's buffers."""
 
-    def __init__(self, p, m, v, step=0, rows=4):
-        self.p, self.m, self.v = p.clone(), m.clone(), v.clone()
+    def __init__(self, p, m, v, step=0, rows=4, n=N):
+        self.p, self.m, self.v, self.n = p.clone(), m.clone(), v.clone(), n
         self.step = torch.full((1,), step, dtype=torch.int64, device="cuda")
         self.scal, self.part = nans((8,)), nans((1024,))
         self.counters = torch.zeros(4, dtype=torch.int64, device="cuda")
@@ -59,30 +59,30 @@ class OpState:
     def unguarded(self, g, dec, max_norm, sc):
         a = ADAM
         if sc is None:
-            check(H().pmgt_op_adamw(P(self.p), P(g), P(self.m), P(self.v), P(dec), N, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"], max_norm,
+            check(H().pmgt_op_adamw(P(self.p), P(g), P(self.m), P(self.v), P(dec), self.n, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"], max_norm,
                                     P(self.step), P(self.scal), P(self.part), stream()))
         else:
-            check(H().pmgt_op_adamw_scheduled(P(self.p), P(g), P(self.m), P(self.v), P(dec), N, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"],
+            check(H().pmgt_op_adamw_scheduled(P(self.p), P(g), P(self.m), P(self.v), P(dec), self.n, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"],
                                               max_norm, P(self.step), P(self.scal), P(self.part), C.byref(sc), stream()))
 
     def guarded(self, g, dec, max_norm, sc, skip, loss=None):
         from pmgt_amd import _lib
         a = ADAM
         gd = _lib.StepGuardC(P(self.counters), P(self.log_f), P(self.log_i), self.rows, None if loss is None else P(loss), skip)
-        check(H().pmgt_op_adamw_guarded(P(self.p), P(g), P(self.m), P(self.v), P(dec), N, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"], max_norm,
+        check(H().pmgt_op_adamw_guarded(P(self.p), P(g), P(self.m), P(self.v), P(dec), self.n, a["lr"], a["wd"], a["b1"], a["b2"], a["eps"], max_norm,
                                         P(self.step), P(self.scal), P(self.part), None if sc is None else C.byref(sc), C.byref(gd), stream()))
 
     def tensors(self):
         return self.p, self.m, self.v, self.step
 
 
-def op_inputs(seed):
+def op_inputs(seed, n=N):
     gen = torch.Generator(device="cuda").manual_seed(seed)
-    p = torch.randn(N, device="cuda", generator=gen)
-    m = torch.randn(N, device="cuda", generator=gen) * 0.1
-    v = torch.rand(N, device="cuda", generator=gen) * 0.01
-    dec = (torch.rand(N, device="cuda", generator=gen) < 0.6).to(torch.uint8)
-    gs = [torch.randn(N, device="cuda", generator=gen) * (0.5 * t) for t in (1, 2, 3)]
+    p = torch.randn(n, device="cuda", generator=gen)
+    m = torch.randn(n, device="cuda", generator=gen) * 0.1
+    v = torch.rand(n, device="cuda", generator=gen) * 0.01
+    dec = (torch.rand(n, device="cuda", generator=gen) < 0.6).to(torch.uint8)
+    gs = [torch.randn(n, device="cuda", generator=gen) * (0.5 * t) for t in (1, 2, 3)]
     return p, m, v, dec, gs
 
 
@@ -113,6 +113,32 @@ def test_good_steps_are_bit_identical_to_the_unguarded_entries(max_norm, sched, 
         assert row[0] == 0.75 and row[1:5] == [float(b.scal[3]), float(b.scal[0]), float(b.scal[4]), 0.0]
         assert b.log_i[t].tolist() == [t, 3 + t + 1]
     assert int(b.step[0]) == 6 and bool(torch.isfinite(b.p).all()) and not torch.equal(b.p, p)
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1.0])
+@pytest.mark.parametrize("n", [1, 3, 4, 1024, 1025, 4099])
+def test_every_entry_runs_one_step_body_at_the_edge_sizes(n, max_norm):
+    """pmgt_op_adamw, pmgt_op_adamw_scheduled with the constant schedule and pmgt_op_adamw_guarded with a NULL schedule (guarding off and
+    on) leave p, m, v, step and scal[0..3] bit-identical over two consecutive steps from random p, g, m, v.  n: a single lane, a tail-only
+    group of the 4-wide AdamW loop, exactly one group, exactly one norm partial (1024 elements), a second partial with a one-element
+    tail, and N.  The scheduled entry leaves scal[5..7] alone (still NaN), the guarded one writes scal[5] = 0 and leaves [6..7]."""
+    p, m, v, dec, gs = op_inputs(14, n)
+    const = _sched("constant", 0, 0)
+    plain, scheduled, counting, skipping = (OpState(p, m, v, n=n) for _ in range(4))
+    for t, g in enumerate(gs[:2]):
+        plain.unguarded(g, dec, max_norm, None)
+        scheduled.unguarded(g, dec, max_norm, const)
+        counting.guarded(g, dec, max_norm, None, 0)
+        skipping.guarded(g, dec, max_norm, None, 1)
+        torch.cuda.synchronize()
+        assert int(plain.step[0]) == t + 1 and bool(torch.isfinite(plain.scal[:4]).all()) and not same_bits(plain.p, p)
+        for other in (scheduled, counting, skipping):
+            for x, y in zip(plain.tensors(), other.tensors()):
+                assert same_bits(x, y)
+            assert same_bits(plain.scal[:4], other.scal[:4]), (plain.scal, other.scal)
+        assert bool(torch.isnan(scheduled.scal[5:]).all())
+        for guarded in (counting, skipping):
+            assert float(guarded.scal[5]) == 0.0 and bool(torch.isnan(guarded.scal[6:]).all())
 
 
 def poison(g, how):

@@ -1,5 +1,5 @@
-"""Learning-rate schedules evaluated on the device (pmgt_amd/ops/lr_schedule.hip: scheduled_lr, adam_prepare_scheduled_kernel,
-adamw_scheduled_kernel), from the single-kernel entries up to captured trainer steps.  Expected values: the closed forms of transformers 4.11.2
+"""Learning-rate schedules evaluated on the device (pmgt_amd/ops/optimizer_step.hip: scheduled_lr and the unguarded instantiation of
+adam_prepare_step_kernel / adamw_step_kernel), from the single-kernel entries up to captured trainer steps.  Expected values: the closed forms of transformers 4.11.2
 in float64 (tests/lr_schedule_util.py); the reference's own get_scheduler cannot run, so no fixture comes from it.
 
 Bounds.  A rate: one fp32 ulp of float32(lr * lambda(s)) plus 1e-12 lr -- the device evaluates in double, its cos differs from the
