@@ -248,6 +248,47 @@ int pmgt_eval_append(void* workspace, int64_t capacity, const float* logits, con
  * exports it), the multi-tile radix path above. */
 int pmgt_eval_reduce(void* workspace, int64_t capacity, int64_t n, void* stream);
 
+/* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
+ * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average
+ * that lives inside a captured step.  One update is, per element,
+ *   avg[j] = avg[j] * w_old + params[j] * w_new
+ * in fp32 with THREE roundings (two products, one sum; never a fused multiply-add), so a numpy fp32 restatement matches bit for bit.
+ *   PMGT_AVG_SWA  the caller passes both weights by value (the reference: beta = 1.0 / models_num, w_old = 1 - beta, w_new = beta, formed
+ *                 in doubles and rounded to fp32 once); decay, warmup, state and skip_flag are ignored.  One launch.
+ *   PMGT_AVG_EMA  the weights are computed on the device from the count of applied updates n_upd kept in `state`:
+ *                 d = decay, or with warmup != 0 d = min(decay, (1 + n_upd) / (10 + n_upd)), in fp64; w_old = (float)d,
+ *                 w_new = (float)(1.0 - d); then n_upd += 1.  skip_flag (device fp32 scalar, or NULL = never skipped) is the optimizer's
+ *                 scal [5] of pmgt_optimizer_step_guarded: when it is non-zero the update is SKIPPED -- the skip word is set, n_upd and
+ *                 every byte of avg stay as they were.  w_old / w_new of the struct are ignored.  Two launches (one lane that prepares,
+ *                 then the update, which reads only what the earlier launch wrote), no sync, no allocation: capturable.
+ * THE DEVICE STATE, PMGT_AVG_STATE_BYTES of 8-byte aligned device memory owned by the caller, zero-filled before the first update:
+ *   bytes [0, 8)    int64  n_upd: updates applied so far (a skipped one does not count)
+ *   bytes [8, 12)   uint32 skip word: 1 when the last update was skipped, else 0
+ *   bytes [12, 16)  fp32   w_old of the last applied update
+ *   bytes [16, 20)  fp32   w_new of the last applied update
+ *   bytes [20, 32)  reserved, never touched
+ * avg and params are device fp32 [n]; 16-byte aligned bases (any torch allocation) take 16-byte accesses, others a scalar form of the
+ * same arithmetic.  Refused (-2): a NULL buffer or cfg, n < 0, an unknown mode, and in PMGT_AVG_EMA a decay outside [0, 1) or a NULL /
+ * misaligned state.  n = 0 is valid (PMGT_AVG_EMA still counts the update).
+ * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (one struct, two entries), nothing existing moved. */
+#define PMGT_AVG_SWA 0
+#define PMGT_AVG_EMA 1
+#define PMGT_AVG_STATE_BYTES 32
+typedef struct pmgt_avg_step {
+    int mode;                /* PMGT_AVG_* */
+    int warmup;              /* PMGT_AVG_EMA: != 0 applies the warm-up of the decay */
+    double decay;            /* PMGT_AVG_EMA: in [0, 1) */
+    void* state;             /* PMGT_AVG_EMA: the device state above */
+    const float* skip_flag;  /* PMGT_AVG_EMA: device fp32 scalar or NULL */
+    float w_old, w_new;      /* PMGT_AVG_SWA: the two weights */
+} pmgt_avg_step;
+/* pmgt/utils/train.py:53-69 (swa_step) and the per-step form of the same update */
+int pmgt_weight_average_update(float* avg, const float* params, int64_t n, const pmgt_avg_step* cfg, void* stream);
+/* pmgt/utils/train.py:72-85 (swap_swa_params): exchanges the CONTENTS of a and b (device fp32 [n], not overlapping) as raw 32-bit words --
+ * the engine, its captured steps and the nn.Parameter views address the parameter buffer by pointer, so the pointers cannot be exchanged
+ * as the reference does.  Applying it twice restores both.  Refused (-2): a NULL buffer, n < 0, a == b. */
+int pmgt_weight_swap(float* a, float* b, int64_t n, void* stream);
+
 /* Gradient-ready notification for the data-parallel exchange (replaces DDP's autograd hooks + buckets,
  * pmgt/base_trainer.py:309-322 -> pl.Trainer(gpus=N)): during a backward pass the engine calls cb(user, offset, numel) on
  * the CALLING host thread right after it has enqueued the last launch that writes grads[offset, offset + numel) -- i.e.

@@ -72,6 +72,15 @@ class StepGuardC(C.Structure):
                 ("skip_nonfinite", C.c_int)]
 
 
+class AvgStepC(C.Structure):
+    """pmgt_avg_step (include/pmgt_capi.h): mode = index in AVG_MODES; state = the AVG_STATE_BYTES device buffer of the "ema" mode."""
+    _fields_ = [("mode", C.c_int), ("warmup", C.c_int), ("decay", C.c_double), ("state", C.c_void_p), ("skip_flag", C.c_void_p),
+                ("w_old", C.c_float), ("w_new", C.c_float)]
+
+
+AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
+AVG_STATE_BYTES = 32            # PMGT_AVG_STATE_BYTES: int64 n_upd; 32-bit words [2] skip word, [3] w_old, [4] w_new, [5..7] reserved
+
 STEP_LOG_FLOATS = 8      # PMGT_STEP_LOG_FLOATS: loss, pre-clip norm, clip coefficient, lr_t, flag, 3 reserved
 STEP_LOG_APPLIED, STEP_LOG_SKIPPED, STEP_LOG_APPLIED_NONFINITE = 0, 1, 2      # the flag column
 
@@ -92,6 +101,7 @@ HIP_SYMBOLS = [
     "pmgt_profile_end", "pmgt_profile_sequence", "pmgt_profile_records", "pmgt_cast_from_f32", "pmgt_cast_to_f32", "pmgt_quantize_e4m3", "pmgt_dequantize_e4m3",
     "pmgt_engine_set_grad_ready_callback", "pmgt_engine_set_option", "pmgt_engine_get_option",
     "pmgt_eval_workspace_bytes", "pmgt_eval_reset", "pmgt_eval_append", "pmgt_eval_reduce",
+    "pmgt_weight_average_update", "pmgt_weight_swap",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -232,6 +242,8 @@ def hip():
     L.pmgt_eval_reduce.argtypes = [vp, i64, i64, vp]
     L.pmgt_op_eval_append_scores.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp]
     L.pmgt_op_eval_small_max.argtypes = []
+    L.pmgt_weight_average_update.argtypes = [vp, vp, i64, C.POINTER(AvgStepC), vp]
+    L.pmgt_weight_swap.argtypes = [vp, vp, i64, vp]
     _hip = L
     return L
 

@@ -251,11 +251,23 @@ def _callback(callbacks: dict, prefix: str) -> Optional[dict]:
     return None
 
 
+def average_model_state(entries, block: dict, prefix: str = "net.") -> dict:
+    """The callback state the reference's on_save_checkpoint returns (pmgt/callbacks.py:284-295): {"average_model": swa_state}, swa_state =
+    {parameter name: tensor, ..., "models_num": n} (pmgt/utils/train.py:39-50).  The tensors are VIEWS of the block's flat average, so a
+    file stores the average once.  An "ema" average carries "n_upd" in place of "models_num"."""
+    flat = block["average"]
+    count = "models_num" if block["mode"] == "swa" else "n_upd"
+    model = {prefix + e["name"]: flat[e["offset"]: e["offset"] + e["numel"]].view(tuple(e["shape"])) for e in entries}
+    model[count] = int(block[count])
+    return {"average_model": model}
+
+
 def training_checkpoint(state_dict: Dict[str, torch.Tensor], entries, trainer_sd: dict, epoch: int = 0, callbacks: Optional[dict] = None,
-                        fit: Optional[dict] = None, **extra) -> dict:
+                        fit: Optional[dict] = None, swa_key: str = "StochasticWeightAveraging", prefix: str = "net.", **extra) -> dict:
     """The checkpoint as plain data (pure: CPU tensors in, a dict out).  `state_dict`: the weights under their `net.` keys, what
     save_checkpoint writes; `trainer_sd`: Trainer.state_dict().  Keys of a Lightning checkpoint of the reference, plus the block
-    "pmgt_amd" for what that format has no place for."""
+    "pmgt_amd" for what that format has no place for.  A trainer that averages its weights adds its `weight_average` block (settings,
+    count, flat average) there and, under `swa_key` among the callbacks, the reference's `average_model` state."""
     est, hp = trainer_sd["engine"], trainer_sd["hyper_parameters"]
     steps = int(est["opt_step"])
     current = None
@@ -273,8 +285,13 @@ def training_checkpoint(state_dict: Dict[str, torch.Tensor], entries, trainer_sd
                "n_params": int(est["n_params"]), "config": dict(est["config"]), "hyper_parameters": dict(hp),
                "accumulate_grad_batches": int(trainer_sd["accumulate_grad_batches"]), "fit": fit,
                "step_counters": dict(est.get("step_counters") or {"attempts": 0, "skipped": 0, "skipped_in_a_row": 0})}
+    callbacks = dict(callbacks or {})
+    block = trainer_sd.get("weight_average")
+    if block is not None:      # absent without averaging: the file's structure is what it always was
+        private["weight_average"] = dict(block)
+        callbacks[swa_key] = average_model_state(entries, block, prefix)
     return {"state_dict": state_dict, "optimizer_states": [opt], "lr_schedulers": sched, "global_step": steps, "epoch": int(epoch),
-            "callbacks": dict(callbacks or {}), "pmgt_amd": private, **extra}
+            "callbacks": callbacks, "pmgt_amd": private, **extra}
 
 
 def training_state_from_checkpoint(ck: dict, entries, n_params: int, n_frozen: int = 0, prefix: str = "net.") -> dict:
@@ -302,6 +319,8 @@ def training_state_from_checkpoint(ck: dict, entries, n_params: int, n_frozen: i
                    step_counters=dict(pv.get("step_counters") or {}))       # absent before the guarded step existed: zeros
         out = {"opt_steps": int(pv["opt_steps"]), "pipeline_step": int(pv["pipeline_step"]), "hyper_parameters": dict(pv["hyper_parameters"]),
                "accumulate_grad_batches": int(pv["accumulate_grad_batches"])}
+        if pv.get("weight_average") is not None:
+            out["weight_average"] = dict(pv["weight_average"])
     else:
         g0 = ck["optimizer_states"][0]["param_groups"][0]
         eng = dict(n_params=n_params, dtype=None, config=None, rng_state=None, options=None)
@@ -350,7 +369,7 @@ def save_training_checkpoint(model_or_engine, trainer, path, prefix: str = "net.
         sd = {prefix + e["name"]: tsd["engine"]["params"][e["offset"]: e["offset"] + e["numel"]].reshape(tuple(e["shape"])).clone() for e in eng.entries}
     else:
         sd = to_reference_state_dict(model_or_engine, prefix)
-    ck = training_checkpoint(sd, eng.entries, tsd, **extra)
+    ck = training_checkpoint(sd, eng.entries, tsd, prefix=prefix, **extra)
     atomic_save(ck, path)
     return ck
 

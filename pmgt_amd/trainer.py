@@ -39,7 +39,7 @@ class Trainer:
                  buckets: str = "two", check_carrier_every: int = 200, force_exchange: bool = False,
                  scheduler_type: Optional[str] = None, num_warmup_steps: Optional[int] = None,
                  num_training_steps: Optional[int] = None, nonfinite: Optional[str] = None, step_log: int = 0,
-                 max_skipped_in_a_row: int = 25):
+                 max_skipped_in_a_row: int = 25, weight_average=None):
         """scheduler_type (one of the reference's --scheduler-type choices; None = constant `lr`, the step as it always was) with
         num_warmup_steps / num_training_steps: every optimizer step uses lr * lambda(k), k = the optimizer steps completed before
         it, evaluated ON THE DEVICE by the fused step (pmgt_amd.schedule states the multipliers).  It advances once per optimizer
@@ -58,8 +58,27 @@ class Trainer:
         logs without guarding.  Both are frozen into a captured step and recorded in checkpoints like the other hyper-parameters.
         None / 0 (default): the step through the entries it always took.  max_skipped_in_a_row: check_nonfinite() raises
         NonFiniteGradientsError at that many consecutive skips (25 is a policy default, not a measurement); it runs only where the
-        host waits for the GPU anyway (end of run_live, epoch end and checkpoint writes of fit, state_dict()), never per step."""
+        host waits for the GPU anyway (end of run_live, epoch end and checkpoint writes of fit, state_dict()), never per step.
+
+        weight_average: None (default: the step through the entries it always took), a pmgt_amd.averaging.WeightAverage over this engine,
+        or a dict of its arguments (mode="swa" | "ema", decay=0.999, warmup=True).  The average starts as a copy of the parameters as they
+        are NOW (load them first, or call weight_average.init_from_params()).  "ema": every optimizer step is followed by one exponential
+        update of the average ON THE DEVICE (count and decay there too), so a captured step / run_live(graphs=True) simply records the
+        two extra launches, and with nonfinite="skip" a skipped optimizer step is not averaged in.  "swa": the step does nothing extra; the
+        running mean is updated by whoever decides when (fit(swa_epoch_start=...): before every validation).  averaged_weights() puts the
+        average into the parameter buffer for forward work.  The settings are frozen into a captured step and the average travels in
+        checkpoints."""
         self.engine = engine
+        self.weight_average = None
+        self._averaged = False        # inside averaged_weights(): the parameter buffer holds the average
+        if weight_average is not None:
+            from .averaging import WeightAverage
+            wa = WeightAverage(engine, **weight_average) if isinstance(weight_average, dict) else weight_average
+            if not isinstance(wa, WeightAverage):
+                raise ValueError(f"weight_average={weight_average!r}: expected None, a WeightAverage or a dict of its arguments")
+            if wa.engine is not engine:
+                raise ValueError("weight_average: the WeightAverage was built over another engine than the trainer's")
+            self.weight_average = wa
         if nonfinite not in (None, "skip"):
             raise ValueError(f"nonfinite={nonfinite!r}: expected None or 'skip'")
         if int(step_log) < 0 or int(max_skipped_in_a_row) < 1:
@@ -118,6 +137,7 @@ class Trainer:
     def training_step(self, batch, batch_idx: int = 0) -> torch.Tensor:
         """loss = net(*batch)[0] with gradients left in engine.grads (pmgt/pmgt/trainer.py:156-160).  The returned device
         scalar lives in the engine's output ring (valid for the next Engine.OUTPUT_RING - 1 steps; clone it to keep it)."""
+        self._not_averaged("training_step")
         if self._exchange is not None:      # gradients are exchanged once per optimizer step: on the last micro-batch
             self._exchange.enabled = (self.world_size > 1 or self.force_exchange) and self._micro == self.accum - 1
         out = self.engine.pretrain_step(batch, training=True, backward=True, accumulate=self._micro > 0,
@@ -128,6 +148,7 @@ class Trainer:
         return out["loss"]
 
     def optimizer_step(self):
+        self._not_averaged("optimizer_step")
         eng = self.engine
         if self.world_size > 1 or self.force_exchange:
             done = self._exchange.wait() if self._exchange is not None else 0
@@ -139,6 +160,10 @@ class Trainer:
             eng.grads.div_(self.accum)
         eng.optimizer_step(lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
                            max_grad_norm=self.max_grad_norm, schedule=self._schedule(), guard=self._guard())
+        wa = self.weight_average
+        if wa is not None and wa.mode == "ema":
+            # behind the optimizer on the same stream; the guard's skipped flag (scal[5]) keeps a skipped step out of the average
+            wa.update(skip_flag=eng.was_skipped() if self.nonfinite == "skip" else None)
         self._opt_steps += 1
         if self.check_carrier_every and self._opt_steps % self.check_carrier_every == 0 and not self._capturing:
             self._check_carrier()
@@ -159,6 +184,7 @@ class Trainer:
 
     def train_step(self, batch) -> torch.Tensor:
         """One micro-batch; steps the optimizer every `accumulate_grad_batches` calls."""
+        self._not_averaged("train_step")
         loss = self.training_step(batch)
         self._micro += 1
         if self._micro == self.accum:
@@ -173,6 +199,38 @@ class Trainer:
             self.optimizer_step()
             self._micro = 0
 
+    # ---- the averaged weights in the parameter buffer, for forward work ------------------------------------------------------
+    def _not_averaged(self, what: str):
+        if self._averaged:
+            raise RuntimeError(f"Trainer.{what}() inside Trainer.averaged_weights(): the parameter buffer holds the AVERAGED weights there; "
+                               "only forward work (evaluate, encode, export_embeddings) belongs inside that context")
+
+    def averaged_weights(self):
+        """Context manager: exchanges the CONTENTS of the parameter buffer and the average on entry and back on exit (also when the body
+        raises), so evaluate / encode / export_embeddings inside see the averaged model through the same pointers -- captured steps taken
+        before stay valid afterwards.  Training entries raise inside; entering it twice raises.  No LayerNorm-carrier re-check runs:
+        the carrier only matters to a backward pass, and none belongs here."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            wa = self.weight_average
+            if wa is None:
+                raise RuntimeError("Trainer.averaged_weights(): this trainer keeps no weight average (Trainer(weight_average=...))")
+            if self._averaged:
+                raise RuntimeError("Trainer.averaged_weights() entered twice: the parameter buffer already holds the averaged weights")
+            if self._micro != 0:
+                raise RuntimeError(f"Trainer.averaged_weights(): {self._micro} of {self.accum} micro-batches of the current accumulation "
+                                   "window have run; swap at an optimizer-step boundary")
+            wa.swap()
+            self._averaged = True
+            try:
+                yield wa
+            finally:
+                wa.swap()
+                self._averaged = False
+        return ctx()
+
     # ---- the whole step as ONE hipGraph ---------------------------------------------------------------------------
     def capture_step(self, batch, warmup: int = 2, capture_error_mode: str = "global"):
         """Captures train_step(batch) (mask -> forward -> losses -> backward -> clip + AdamW) into a hipGraph and
@@ -183,6 +241,7 @@ class Trainer:
         `warmup` eager steps run first (one-time kernel attribute calls are not capturable).  Single-GPU step only:
         the gradient all-reduce is not captured."""
         assert self.world_size == 1 and self.accum == 1 and not self.force_exchange, "capture covers the single-GPU, non-accumulating step"
+        self._not_averaged("capture_step")
         dev = self.engine.device
         # replays never run the Python-side guard: decide "x^ from the LayerNorm output or from stored inputs" once, on the
         # parameters as they are now, before the kernels are frozen into the graph
@@ -220,6 +279,8 @@ class Trainer:
         # everything the captured launches address by raw pointer lives as long as the replay handle: the engine's workspace (a later,
         # larger call makes the engine allocate a NEW one and drop its reference to this one), the static input tensors, the moments
         replay.keep = (eng._ws, batch, eng.exp_avg, eng.exp_avg_sq, eng.params, eng.grads)
+        if self.weight_average is not None:      # (allocated with the WeightAverage, i.e. before this capture)
+            replay.keep += (self.weight_average.avg, self.weight_average.state)
         return replay
 
     def _schedule(self):
@@ -258,6 +319,12 @@ class Trainer:
                 None if self.max_grad_norm is None else float(self.max_grad_norm), float(self.random_node_ratio), float(self.mask_node_ratio),
                 self.nonfinite, int(self.step_log), self._schedule())
 
+    def _capture_key(self):
+        """_hyper_key() plus the averaging settings (mode, decay, warm-up) when the trainer averages: what run_live keys a captured step on."""
+        if self.weight_average is None:
+            return self._hyper_key()
+        return self._hyper_key() + (("weight_average",) + self.weight_average.key(),)
+
     def drop_captured_steps(self):
         """Forgets every step run_live(graphs=True) captured (call after changing lr / weight decay / clip / ratios / engine options by
         hand; run_live itself re-captures when the hyper-parameters it was captured with no longer match).  Waits for the GPU first: a
@@ -283,8 +350,13 @@ class Trainer:
                                "run; the training state can only be saved at an optimizer-step boundary (_micro == 0)")
         est = self.engine.training_state()
         self.check_nonfinite(est["step_counters"])      # a run that no longer applies its steps is not checkpointed
-        return {"engine": est, "opt_steps": int(self._opt_steps), "pipeline_step": int(self.pipeline_step),
-                "hyper_parameters": self.hyper_parameters(), "accumulate_grad_batches": int(self.accum)}
+        if self._averaged:
+            raise RuntimeError("Trainer.state_dict() inside Trainer.averaged_weights(): the parameter buffer holds the averaged weights")
+        sd = {"engine": est, "opt_steps": int(self._opt_steps), "pipeline_step": int(self.pipeline_step),
+              "hyper_parameters": self.hyper_parameters(), "accumulate_grad_batches": int(self.accum)}
+        if self.weight_average is not None:      # absent without averaging: the state is what it always was
+            sd["weight_average"] = self.weight_average.state_dict()
+        return sd
 
     def hyper_mismatches(self, sd: dict) -> list:
         """[(name, checkpoint value, trainer value)] over the hyper-parameters and the accumulation factor `sd` records."""
@@ -296,7 +368,10 @@ class Trainer:
         if sd.get("accumulate_grad_batches") is not None:
             theirs["accumulate_grad_batches"] = int(sd["accumulate_grad_batches"])
         norm = lambda v: tuple(norm(x) for x in v) if isinstance(v, (list, tuple)) else v
-        return [(k, norm(theirs[k]), norm(mine[k])) for k in mine if k in theirs and norm(theirs[k]) != norm(mine[k])]
+        from .averaging import settings_mismatches
+        wa = self.weight_average
+        return [(k, norm(theirs[k]), norm(mine[k])) for k in mine if k in theirs and norm(theirs[k]) != norm(mine[k])] + \
+            settings_mismatches(sd.get("weight_average"), None if wa is None else wa.settings())
 
     def load_state_dict(self, sd: dict, strict: bool = True) -> None:
         """Continues from `sd` (state_dict()'s layout).  The tensors are written INTO the engine's existing buffers, so the steps
@@ -305,10 +380,18 @@ class Trainer:
         dropped first (run_live records them again).  strict: a hyper-parameter or accumulation factor that differs raises a
         ValueError naming both values (a silently different curve is worse); strict=False takes the checkpoint's tensors and counters
         and keeps this trainer's hyper-parameters.  A state of another parameter count, engine dtype or configuration is refused
-        either way, before anything is written."""
+        either way, before anything is written.
+        The `weight_average` block: a state without it into a trainer that averages, or with it into a trainer that does not, raises
+        under strict; strict=False re-initialises the average from the loaded parameters, respectively ignores the block.  Mode, decay
+        and warm-up are compared like the other hyper-parameters.  The average and its count are written in place too."""
+        from .averaging import reconcile
         eng = self.engine
         est = sd["engine"]
         eng.check_training_state(est)
+        if self._averaged:
+            raise RuntimeError("Trainer.load_state_dict() inside Trainer.averaged_weights()")
+        wa = self.weight_average
+        block = sd.get("weight_average")
         bad = self.hyper_mismatches(sd)
         options_differ = est.get("options") is not None and set(est["options"]) != set(eng.options_set())
         if (bad or options_differ) and self._live_replays:
@@ -319,7 +402,12 @@ class Trainer:
             raise ValueError("Trainer.load_state_dict: the checkpoint was written under other hyper-parameters: " +
                              "; ".join(f"{k}: checkpoint {a!r}, trainer {b!r}" for k, a, b in bad) +
                              " (strict=False loads the tensors and counters and keeps the trainer's values)")
+        averaging = reconcile(block, None if wa is None else wa.settings(), strict, eng.n_params)      # raises before anything is written
         eng.load_training_state(est)
+        if averaging == "load":
+            wa.load_state_dict(block)
+        elif averaging == "reinit":
+            wa.init_from_params()
         if est.get("rng_state") is None:
             # a checkpoint of the reference has no dropout counter: this engine's seed, at the step a run of ours would have reached
             eng.rng_state[1] = int(est["opt_step"]) * self.accum
@@ -395,7 +483,7 @@ class Trainer:
         ev_b = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
         t_launch = 0.0
         replays = self._live_replays       # (slot buffers, shape, hyper-parameters) -> captured step, kept across calls
-        hyper = self._hyper_key()
+        hyper = self._capture_key()
         if graphs and any(k[-1] != hyper for k in replays):
             self.drop_captured_steps()       # lr / weight decay / clip / ratios changed since the capture: those are frozen kernel arguments
         checked_at = -1
@@ -744,7 +832,7 @@ def epoch_order(n: int, seed: int, epoch: int, rank: int = 0, world_size: int = 
 def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid_ids: np.ndarray, batch_size: int, max_epochs: int,
         early_criterion: str = "loss", patience: int = 10, ckpt_dir: str = ".", resume_from: Optional[str] = None,
         save_every_n_steps: int = 0, seed: int = 0, graphs: bool = False, threads: int = 8, valid_batch_size: int = 256, log=None,
-        nonfinite="keep", step_log="keep", max_skipped_in_a_row="keep", eval_metrics: str = "host") -> dict:
+        nonfinite="keep", step_log="keep", max_skipped_in_a_row="keep", eval_metrics: str = "host", swa_epoch_start=None) -> dict:
     """pl.Trainer.fit as the reference's init_run configures it, restated: `max_epochs` epochs; epoch e trains on this rank's shard of
     a permutation of `train_ids` seeded by (seed, e) -- the len // batch_size full batches through run_live, a remainder as one eager
     train_step of its true size (DataLoader drop_last=False), an unfinished accumulation window stepped at the end of the epoch as
@@ -763,6 +851,15 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     previous last.ckpt stays.
     eval_metrics: "host" (default) or "device", passed to evaluate(metrics=...) for the validation after every epoch.  Not part of the training
     state: a checkpoint written under one setting resumes under the other.
+    swa_epoch_start: the reference's StochasticWeightAveraging callback (pmgt/callbacks.py:44-381), restated: an int >= 1 or a float in
+    [0, 1] (then int(max_epochs * f)); at the start of the 0-based training epoch max(start - 1, 0) the average becomes a copy of the
+    parameters (swa_init), and from then on every validation is preceded by swa_step (models_num += 1, avg = avg * (1 - 1 / models_num) +
+    p / models_num) and a swap-in of the average, and followed by the swap back: the monitored metric, early stopping and the best
+    checkpoint follow the AVERAGED model, the files hold the raw weights plus the average (Trainer.state_dict's weight_average block, and
+    `average_model` under the callback's name).  Needs a trainer whose average is in "swa" mode; one is attached when the trainer keeps
+    none.  The callback's SWALR scheduler swap and its BatchNorm branches are not restated: the rate stays the trainer's schedule.
+    A trainer that averages in "ema" mode validates on its average from the first epoch on (the same swap around evaluate, no swa_step).
+    Every rank's parameters are identical after the all-reduced step, so every rank's average is too: no collective is added.
     Returns {best_model_path, best_model_score, epochs_run, stopped_early, history: per-epoch metrics}."""
     import os
 
@@ -777,6 +874,18 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
         checked = Trainer(None, **passed)                 # the constructor's argument checks
         for k in passed:
             setattr(trainer, k, getattr(checked, k))      # (run_live re-captures: both settings are part of _hyper_key())
+    swa_start, swa_key = None, "StochasticWeightAveraging"
+    if swa_epoch_start is not None:
+        from .averaging import WeightAverage, swa_start_epoch
+        swa_start = swa_start_epoch(swa_epoch_start, max_epochs)          # the reference's check and message
+        if trainer.weight_average is None:
+            trainer.weight_average = WeightAverage(eng, "swa")            # before a resume reads the file, and before any capture
+        elif trainer.weight_average.mode != "swa":
+            raise ValueError(f"fit(swa_epoch_start=...): the trainer averages in {trainer.weight_average.mode!r} mode; the epoch-wise "
+                             "running mean needs a trainer whose weight_average is in 'swa' mode")
+        # Lightning's state key of the callback; on_fit_start has turned a float into the epoch number by then
+        start = int(int(max_epochs) * swa_epoch_start) if isinstance(swa_epoch_start, float) else int(swa_epoch_start)
+        swa_key = f"StochasticWeightAveraging{{'swa_epoch_start': {start!r}, 'annealing_strategy': 'cos'}}"
     rank, ws = world() if trainer.world_size > 1 else (0, 1)
     monitor, mode = monitor_of(early_criterion)
     stopper, best = EarlyStopping(monitor, patience, mode), BestCheckpoint(ckpt_dir, monitor, mode)
@@ -806,7 +915,7 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     def save(path, top_epoch):
         trainer.check_nonfinite()                            # on every rank, before rank 0 writes anything
         st = dict(run, epoch=epoch, batches_done=done, history=history, stopped_early=stopped, counters_at_epoch_start=at_epoch_start)
-        pio.save_training_checkpoint(model_or_engine, trainer, path, epoch=top_epoch, fit=st,
+        pio.save_training_checkpoint(model_or_engine, trainer, path, epoch=top_epoch, fit=st, swa_key=swa_key,
                                      callbacks={stopper.state_key: stopper.state_dict(), best.state_key: best.state_dict()})
 
     def say(event, **kw):
@@ -816,6 +925,8 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
     stream_seed = int(seed) + rank                       # ranks see different targets: their sampler streams differ too
     while epoch < max_epochs and not stopped:
         order = train_ids[epoch_order(len(train_ids), seed, epoch, rank, ws)]
+        if swa_start is not None and epoch == swa_start and done == 0:
+            trainer.weight_average.init_from_params()        # swa_init, on_train_epoch_start (a resume inside this epoch finds it in the file)
         if trainer._guard() is not None and (at_epoch_start is None or done == 0):
             at_epoch_start = eng.step_counters()
         n_full = len(order) // batch_size
@@ -846,8 +957,14 @@ def fit(trainer: Trainer, model_or_engine, sampler, train_ids: np.ndarray, valid
             if trainer.step_log:
                 mine = [r["loss"] for r in eng.step_log() if r["attempt"] >= at_epoch_start["attempts"] and not r["skipped"]]
                 train_metrics["loss/train"] = float(np.mean(mine)) if mine else float("nan")
-        metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1,
-                           metrics=eval_metrics)
+        wa = trainer.weight_average
+        averaged = wa is not None and (wa.mode == "ema" or (swa_start is not None and epoch >= swa_start))
+        if averaged and wa.mode == "swa":
+            wa.update()                                      # swa_step, on_validation_start
+        import contextlib
+        with (trainer.averaged_weights() if averaged else contextlib.nullcontext()):      # swap_swa_params around the validation
+            metrics = evaluate(eng, sampler, valid_ids, batch_size=valid_batch_size, threads=threads, seed=seed, distributed=ws > 1,
+                               metrics=eval_metrics)
         history.append(dict(epoch=epoch, **metrics, **train_metrics))
         top_epoch = epoch
         new_best, old_best = best.update(epoch, metrics[monitor])
