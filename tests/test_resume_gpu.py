@@ -378,10 +378,10 @@ def test_fit_resumed_in_the_middle_of_an_epoch_equals_the_uninterrupted_run(crit
 
 
 def test_fit_stops_early_on_a_scripted_metric(tmp_path, monkeypatch):
-    from pmgt_amd import trainer as T
+    from pmgt_amd import fit_loop, trainer as T
     script = iter([{"loss/val": 0.50, "val/auc": 0.6}, {"loss/val": 0.40, "val/auc": 0.7}, {"loss/val": 0.40, "val/auc": 0.8},
                    {"loss/val": 0.10, "val/auc": 0.9}])
-    monkeypatch.setattr(T, "evaluate", lambda *a, **k: next(script))
+    monkeypatch.setattr(fit_loop, "evaluate", lambda *a, **k: next(script))      # where fit looks it up
     eng, tr, smp, train_ids, valid_ids = fit_world()
     res = T.fit(tr, eng, smp, train_ids, valid_ids, batch_size=FIT_B, max_epochs=4, early_criterion="loss", patience=1,
                 ckpt_dir=str(tmp_path), seed=5, threads=2)
