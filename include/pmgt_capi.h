@@ -248,6 +248,54 @@ int pmgt_eval_append(void* workspace, int64_t capacity, const float* logits, con
  * exports it), the multi-tile radix path above. */
 int pmgt_eval_reduce(void* workspace, int64_t capacity, int64_t n, void* stream);
 
+/* Top-N ranking metrics ON THE DEVICE: nDCG@k, Recall@k and the per-user loss of `NCFTrainerModel._validation_and_test_step` /
+ * `validation_epoch_end` (pmgt/ncf/trainer.py:202-254 over get_ndcg / get_recall, pmgt/metrics.py:16-37: one Python iteration, one topk, one
+ * .item() and one device-to-host copy per user, then a MultiLabelBinarizer pass per rank position) from rows of candidate scores that stay
+ * on the device.  The caller owns one workspace of pmgt_rank_workspace_bytes(max_users, n_k) bytes (16-byte aligned device memory, max_users =
+ * user slots, 1 .. 2^22) and passes the same `max_users` to every call on it; reset comes first.  Limits: a row holds 1 .. PMGT_RANK_MAX_ROW
+ * candidates, up to PMGT_RANK_MAX_KS cut-offs `ks`, strictly increasing, each in [1, PMGT_RANK_MAX_K].
+ * Per user row, with key = the order-preserving uint32 image of the fp32 score (-0.0f folded onto +0.0f, +-inf at the ends):
+ *   rank(p)  = #{c : key(c) > key(p)} + #{c < p : key(c) == key(p)}       -- a permutation of the row; TIES GO TO THE LOWER CANDIDATE
+ *              INDEX (torch.topk leaves their order unspecified: this is the project's rule)
+ *   hits_k   = #{positives p : rank(p) < k},   recall_k = (double)hits_k / n_pos
+ *   dcg_k    = sum of disc[r] over the hit ranks r < k, added in ascending r in fp64,   ndcg_k = dcg_k / idcg[min(n_pos, k) - 1]
+ *   loss     = mean over the live candidates of max(x, 0) - x y + log1pf(expf(-|x|)), y = (label != 0) ? 1 : 0, fp32 (BCEWithLogitsLoss
+ *              of the row; a label other than 0 or 1 counts as 1)
+ * disc[r] = 1 / log2(r + 2) and idcg = cumsum(disc) are the HOST's fp64 tables, handed to reset: the device evaluates no logarithm, and
+ * with the ascending adds and one IEEE division the per-user values equal get_ndcg / get_recall called per user, bit for bit.
+ * Layout, capr = max_users rounded up to 64:
+ *   [0, 128)  written by reduce: fp64 [0..3] sum of ndcg per k, [4..7] sum of recall per k, [8] sum of the losses; uint64 [9] n_users,
+ *             [10] users with a NaN logit among their live candidates, [11] users without a positive, [12] slots below n_users that
+ *             no append has written since the reset (their records are zeros); [13..15] reserved
+ *   then      48 bytes of settings, disc and idcg fp64 [1024] each, and the user records in slot order: ndcg fp64 [n_k][capr],
+ *             recall fp64 [n_k][capr], loss fp32 [capr], n_pos int32 [capr], flags uint32 [capr] (bit 0 NaN, bit 1 no positive, bit 2 never
+ *             written: reset leaves every record zero with bit 2 set).
+ * The result STAYS in the workspace: the host reads the 128 header bytes with one copy and divides by n_users.  Every entry is
+ * stream-ordered, allocates nothing, never synchronises, uses no floating-point atomic and keeps no state outside the workspace: the
+ * sums do not depend on launch geometry or on how the users were split over appends, and are bitwise repeatable.
+ * Refused (-2), writing nothing: a NULL or misaligned pointer, max_users outside its range, row_stride outside [1, PMGT_RANK_MAX_ROW],
+ * ks not strictly increasing / outside [1, PMGT_RANK_MAX_K] / more than PMGT_RANK_MAX_KS, user slots past max_users, n_users outside
+ * [1, max_users] for reduce.  An append or reduce on a workspace whose last reset was for another max_users (or never ran) writes nothing.
+ * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (four entries), nothing existing moved. */
+#define PMGT_RANK_HEADER_BYTES 128
+#define PMGT_RANK_MAX_ROW 4096
+#define PMGT_RANK_MAX_K 1024
+#define PMGT_RANK_MAX_KS 4
+/* pmgt/ncf/trainer.py:202-254: the storage the per-user results of a ranking evaluation take; < 0 for arguments outside the limits */
+int64_t pmgt_rank_workspace_bytes(int64_t max_users, int n_k);
+/* pmgt/ncf/trainer.py:202-254, start of an evaluation: zeroes the header and the records (marking every slot as not written), records
+ * ks [n_k] and uploads the tables.  ks, disc and idcg are
+ * HOST arrays (disc, idcg: fp64 [ks[n_k - 1]], 8-byte aligned); they travel in kernel arguments, so they may be freed when the call returns */
+int pmgt_rank_reset(void* workspace, int64_t max_users, const int* ks, int n_k, const double* disc, const double* idcg, void* stream);
+/* pmgt/ncf/trainer.py:202-219, one batch of users: logits and labels are device fp32 [n_users][row_stride] (a candidate is positive iff its
+ * label != 0), counts device int32 [n_users] = live candidates per row, 1 .. row_stride (entries past the count are padding and are never
+ * read; NULL = full rows).  The record of row i goes to slot user_offset + i (a host integer).  One launch, one workgroup per row. */
+int pmgt_rank_append(void* workspace, int64_t max_users, const float* logits, const float* labels, const int32_t* counts, int64_t row_stride,
+                     int64_t user_offset, int64_t n_users, void* stream);
+/* pmgt/ncf/trainer.py:227-254, epoch end: sums the records of slots 0 .. n_users in user order with a fixed tree into the header; the
+ * records are left as they are, so a reduce can be repeated or follow further appends.  One launch. */
+int pmgt_rank_reduce(void* workspace, int64_t max_users, int64_t n_users, void* stream);
+
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average
  * that lives inside a captured step.  One update is, per element,

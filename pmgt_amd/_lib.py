@@ -102,6 +102,7 @@ HIP_SYMBOLS = [
     "pmgt_engine_set_grad_ready_callback", "pmgt_engine_set_option", "pmgt_engine_get_option",
     "pmgt_eval_workspace_bytes", "pmgt_eval_reset", "pmgt_eval_append", "pmgt_eval_reduce",
     "pmgt_weight_average_update", "pmgt_weight_swap",
+    "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -244,6 +245,11 @@ def hip():
     L.pmgt_op_eval_small_max.argtypes = []
     L.pmgt_weight_average_update.argtypes = [vp, vp, i64, C.POINTER(AvgStepC), vp]
     L.pmgt_weight_swap.argtypes = [vp, vp, i64, vp]
+    L.pmgt_rank_workspace_bytes.restype = i64
+    L.pmgt_rank_workspace_bytes.argtypes = [i64, i]
+    L.pmgt_rank_reset.argtypes = [vp, i64, vp, i, vp, vp, vp]
+    L.pmgt_rank_append.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp]
+    L.pmgt_rank_reduce.argtypes = [vp, i64, i64, vp]
     _hip = L
     return L
 

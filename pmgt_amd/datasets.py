@@ -203,3 +203,41 @@ def train_valid_split(n_nodes: int, valid_size: float, seed: int):
     rc = _lib.sampler().pmgt_train_valid_split(n_nodes, float(valid_size), int(seed) & 0xFFFFFFFF, _p(tr), _p(va))
     assert rc == n_test
     return tr, va
+
+
+def ranking_candidates(pairs, num_user: int, num_item: int, num_ng: int, seed: int):
+    """The per-user candidate lists of the reference's ranking evaluation: `NCFDataset(features, num_user, num_item, num_ng,
+    is_training=False)` read in index order after np.random.seed(seed) (pmgt/ncf/datasets.py:65-83,115-128).  Users in ascending order; a
+    user's candidates are its positives in ascending item order followed by negatives up to `num_ng` candidates, each negative drawn as
+    RandomState(seed).randint(num_item) and drawn again while it is one of the user's positives (a negative may repeat, as there), in the
+    reference's call order.  A user with n_pos >= num_ng gets no negatives.
+    -> users [U] int64, candidates [U, C_max] int64, labels [U, C_max] fp32, counts [U] int32, C_max = max(num_ng, largest n_pos); entries
+    past a user's count are padding (item 0, label 0)."""
+    positives = {}
+    for u, i in pairs:
+        u, i = int(u), int(i)
+        if not (0 <= u < num_user and 0 <= i < num_item):
+            raise ValueError(f"ranking_candidates: pair ({u}, {i}) outside {num_user} users x {num_item} items")
+        positives.setdefault(u, set()).add(i)
+    users = np.array(sorted(positives), dtype=np.int64)
+    if len(users) == 0:
+        raise ValueError("ranking_candidates: no interaction was given")
+    c_max = max(int(num_ng), max(len(p) for p in positives.values()))
+    candidates = np.zeros((len(users), c_max), dtype=np.int64)
+    labels = np.zeros((len(users), c_max), dtype=np.float32)
+    counts = np.empty(len(users), dtype=np.int32)
+    rs = np.random.RandomState(int(seed))
+    for row, u in enumerate(users):
+        pos = positives[int(u)]
+        if len(pos) >= num_item and len(pos) < num_ng:
+            raise ValueError(f"ranking_candidates: user {int(u)} interacted with all {num_item} items: no negative exists")
+        items = sorted(pos)
+        for _ in range(int(num_ng) - len(items)):
+            j = int(rs.randint(num_item))
+            while j in pos:
+                j = int(rs.randint(num_item))
+            items.append(j)
+        counts[row] = len(items)
+        candidates[row, :len(items)] = items
+        labels[row, :len(pos)] = 1.0
+    return users, candidates, labels, counts

@@ -38,6 +38,7 @@ class PMGT_NCF(PMGTPretrainedModel):
             "item embedding (hidden_size) must match the user embedding width (pmgt/pmgt_ncf/models.py:49-63)"
         self.config = config
         self.factor_num, self.num_layers, self.model = factor_num, num_layers, model
+        self.user_num, self.item_num = int(user_num), int(item_num)
         self.bert = PMGTModel(config, dtype=dtype, device=device)
         self.engine = self.bert.engine
         self.feat_embeddings = nn.Module()          # frozen, idx 0 <pad>, idx 1 <mask> (:36-47)
@@ -79,17 +80,23 @@ class PMGT_NCF(PMGTPretrainedModel):
         self.engine.check_layernorm_carrier()
         return out
 
-    def forward(self, user: torch.LongTensor, item: Dict[str, torch.Tensor]) -> torch.Tensor:
-        dev = self.engine.device
-        user = user.to(dev)
-        node_ids = item["node_ids"].to(dev)
+    def head(self, user: torch.LongTensor, item_ids: torch.LongTensor, item_embeds: torch.Tensor) -> torch.Tensor:
+        """The NCF part on ready item embeddings (pmgt/pmgt_ncf/models.py:91-105): user [n] and item_ids [n] (0-based item numbers, for the
+        GMF branch) on the engine's device, item_embeds [n, hidden_size] the items' CLS states.  forward() ends in this; the ranking
+        evaluation calls it on rows gathered from an embedding table of the whole catalogue."""
         mlp_user_embeds = self.mlp_user_embeddings(user)
-        item_embeds = self.bert.encode_ids(node_ids, attention_mask=item["attention_mask"].to(dev))[0][:, 0]
         interaction = self.emb_dropout(torch.cat([mlp_user_embeds, item_embeds], dim=-1))
         mlp_outputs = self.mlp_layers(interaction)
         if self.model == "NeuMF-end":
-            gmf_outputs = self.gmf_user_embeddings(user) * self.gmf_item_embeddings(node_ids[:, 0] - 2)
+            gmf_outputs = self.gmf_user_embeddings(user) * self.gmf_item_embeddings(item_ids)
             outputs = torch.cat([self.emb_dropout(gmf_outputs), mlp_outputs], dim=-1)
         else:
             outputs = mlp_outputs
         return self.predict_layer(outputs).view(-1)
+
+    def forward(self, user: torch.LongTensor, item: Dict[str, torch.Tensor]) -> torch.Tensor:
+        dev = self.engine.device
+        user = user.to(dev)
+        node_ids = item["node_ids"].to(dev)
+        item_embeds = self.bert.encode_ids(node_ids, attention_mask=item["attention_mask"].to(dev))[0][:, 0]
+        return self.head(user, node_ids[:, 0] - 2, item_embeds)

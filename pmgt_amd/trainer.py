@@ -442,6 +442,7 @@ class Trainer:
 
 
 # what lived here before the split by concern stays importable from here; at the bottom: none of the three may need this module to import
-from .evaluation import EVAL_PINNED_SLOTS, evaluate, export_embeddings, roc_auc_score  # noqa: E402,F401
+from .evaluation import (EVAL_PINNED_SLOTS, encode_catalogue, evaluate, evaluate_ranking, export_embeddings, rank_users,  # noqa: E402,F401
+                         ranking_metrics_host, roc_auc_score)
 from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, fit, monitor_of  # noqa: E402,F401
 from .pipeline import PipelineError, ProducerPipeline, live_loop  # noqa: E402,F401
