@@ -296,6 +296,70 @@ int pmgt_rank_append(void* workspace, int64_t max_users, const float* logits, co
  * records are left as they are, so a reduce can be repeated or follow further appends.  One launch. */
 int pmgt_rank_reduce(void* workspace, int64_t max_users, int64_t n_users, void* stream);
 
+/* Recommendation from the WHOLE catalogue ON THE DEVICE: the eval-mode head of PMGT_NCF (pmgt/pmgt_ncf/models.py:91-105; dropout is the
+ * identity) for a batch of users against every item, fused so that nothing per (user, item) pair touches memory except one fp32 logit,
+ * and the selection of each user's k best items that the user has not interacted with.  The reference has no such path: its test step
+ * (pmgt/ncf/trainer.py:202-219) does `pred.topk(100)` on one sampled candidate list per user.
+ *
+ * SCORING.  With d = factor_num * 2^(num_layers - 1) the width of the user and item embeddings, layer 0 of the head is linear in the
+ * concatenation [user ; item]: W0 = [W0u | W0e] (mlp_layers[0].linear.weight [d][2 d], its first d columns and its last d).  The CALLER
+ * computes, once,
+ *   pu = mlp_user_embeddings.weight[users] W0u^T         [n][d]
+ *   pi = item_table W0e^T + mlp_layers[0].linear.bias    [n_items][d]
+ * (two dense products over the item table [n_items][d] and the gathered user rows; plumbing) and the entry computes per pair (r, j)
+ *   h1 = relu(pu[r] + pi[j]),   h(i+1) = relu(W_i h_i + b_i) for i = 1 .. num_layers - 1,
+ *   scores[r][j] = predict_weight . [gmf_user[users[r]] * gmf_item[j] ; h_L] + predict_bias        (PMGT_NCF_NEUMF_END)
+ *   scores[r][j] = predict_weight . h_L + predict_bias                                              (PMGT_NCF_MLP)
+ * in fp32 end to end on the exact f32-input matrix instruction (no bf16 anywhere); a NaN in pu or pi reaches the scores (the ReLU keeps
+ * it).  Entries [r][n_items .. row_stride) are not written.  All pointers are device memory, the parameters in their state_dict
+ * layout (weight[i] = mlp_layers[i].linear.weight [d >> i][d >> (i - 1)] row-major; weight[0] / bias[0] are not read).
+ * Covered: factor_num 8, 16, 32 or 64, num_layers 1 .. PMGT_NCF_MAX_LAYERS, d <= 256, both kinds, 1 <= n <= PMGT_NCF_MAX_USERS per call,
+ * 1 <= n_items <= 2^31 - 2, row_stride >= n_items.  Refused (-2) before anything is launched, writing nothing: a head outside these
+ * limits, a NULL or misaligned buffer, NeuMF-end without its GMF tables, more workgroups than a grid holds.  A user id outside
+ * [0, user_num) (NeuMF-end reads the GMF table by it) is never dereferenced: its row of scores is NaN.
+ *
+ * SELECTION.  Per row of scores [n][row_stride] (n_items live entries; the rest is never read) the k best eligible items in the order of
+ * the pmgt_rank entries: key = the order-preserving uint32 image of the fp32 score (-0.0f folded onto +0.0f, a NaN above +inf), descending,
+ * and AMONG EQUAL KEYS THE LOWER ITEM INDEX FIRST.  Item j is excluded for row r iff it occurs in the list of users[r] in a device CSR
+ * over user ids, indptr int64 [user_num + 1] and excluded int32 [n_excluded] (duplicates are harmless; the CALLER validates the CSR on
+ * the host: indptr non-decreasing from 0 to n_excluded, items in [0, n_items); entries outside are skipped, never dereferenced);
+ * indptr = NULL: every item is eligible and users is not read.  Output per row: out_items int32 [n][k] and out_scores fp32 [n][k] (the
+ * scores as they came in, bit for bit); slots past the eligible count hold item -1 and score -inf; out_flags uint32 [n]:
+ * PMGT_TOPK_FLAG_NAN = a NaN among the eligible scores, PMGT_TOPK_FLAG_SHORT = fewer than k eligible items.  The workspace (the caller's,
+ * 16-byte aligned, the byte count below for this n and n_items) holds the key image of the rows.  One launch, stream-ordered, no
+ * allocation, no wait; integer counting only, so the result is a pure function of the inputs and bitwise repeatable.
+ * Refused (-2), writing nothing: k outside [1, PMGT_TOPK_MAX_K], n_items outside [1, 2^31 - 2], n < 1, row_stride < n_items, a NULL or
+ * misaligned buffer, a CSR without users / user_num / its item array.
+ * Added without a bump of pmgt_abi_version(): the ABI grew by addition only (one struct, three entries), nothing existing moved. */
+#define PMGT_NCF_MLP 0
+#define PMGT_NCF_NEUMF_END 1
+#define PMGT_NCF_MAX_LAYERS 4
+#define PMGT_NCF_MAX_USERS 1048576
+#define PMGT_TOPK_MAX_K 1024
+#define PMGT_TOPK_FLAG_NAN 1u
+#define PMGT_TOPK_FLAG_SHORT 2u
+typedef struct pmgt_ncf_head {
+    int factor_num, num_layers;
+    int kind;                                     /* PMGT_NCF_* */
+    int reserved;
+    const float* weight[PMGT_NCF_MAX_LAYERS];     /* mlp_layers[i].linear.weight; [0] is the caller's (the split layer) */
+    const float* bias[PMGT_NCF_MAX_LAYERS];       /* mlp_layers[i].linear.bias */
+    const float* predict_weight;                  /* predict_layer.weight [factor_num], NeuMF-end [2 factor_num] = [gmf | mlp] */
+    const float* predict_bias;                    /* predict_layer.bias [1] */
+    const float* gmf_user;                        /* NeuMF-end: gmf_user_embeddings.weight [user_num][factor_num]; else NULL */
+    const float* gmf_item;                        /* NeuMF-end: gmf_item_embeddings.weight [n_items][factor_num]; else NULL */
+    int64_t user_num;                             /* rows of gmf_user */
+} pmgt_ncf_head;
+/* pmgt/pmgt_ncf/models.py:91-105 for n users x n_items items: users int64 [n], scores fp32 [n][row_stride] */
+int pmgt_ncf_score(const pmgt_ncf_head* head, const float* pu, const float* pi, const int64_t* users, int64_t n, int64_t n_items,
+                   float* scores, int64_t row_stride, void* stream);
+/* pmgt/ncf/trainer.py:202-219: the bytes of the key image of n rows of n_items entries; < 0 for arguments outside the limits */
+int64_t pmgt_topk_workspace_bytes(int64_t n, int64_t n_items);
+/* pmgt/ncf/trainer.py:202-219 (`pred.topk`) for whole rows with the users' known items left out */
+int pmgt_topk_rows(const float* scores, int64_t row_stride, int64_t n, int64_t n_items, int k, const int64_t* users, const int64_t* indptr,
+                   const int32_t* excluded, int64_t user_num, int64_t n_excluded, void* workspace, int32_t* out_items, float* out_scores,
+                   uint32_t* out_flags, void* stream);
+
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average
  * that lives inside a captured step.  One update is, per element,

@@ -1,4 +1,6 @@
 """pmgt_amd — MI355X-native PMGT pre-training hot path (HIP kernels behind the reference's Python surface)."""
 from .configuration_pmgt import PMGTConfig  # noqa: F401
+# (binds the name `recommend` to the function: the submodule stays reachable as `from pmgt_amd.recommend import ...`)
+from .recommend import ncf_head_host, recommend, topk_host  # noqa: F401
 
-__all__ = ["PMGTConfig"]
+__all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host"]

@@ -78,6 +78,17 @@ class AvgStepC(C.Structure):
                 ("w_old", C.c_float), ("w_new", C.c_float)]
 
 
+class NcfHeadC(C.Structure):
+    """pmgt_ncf_head (include/pmgt_capi.h): kind = index in NCF_KINDS; device pointers of the head's parameters in state_dict layout."""
+    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("reserved", C.c_int),
+                ("weight", C.c_void_p * 4), ("bias", C.c_void_p * 4), ("predict_weight", C.c_void_p), ("predict_bias", C.c_void_p),
+                ("gmf_user", C.c_void_p), ("gmf_item", C.c_void_p), ("user_num", C.c_int64)]
+
+
+NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
+NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
+TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
+
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
 AVG_STATE_BYTES = 32            # PMGT_AVG_STATE_BYTES: int64 n_upd; 32-bit words [2] skip word, [3] w_old, [4] w_new, [5..7] reserved
 
@@ -103,6 +114,7 @@ HIP_SYMBOLS = [
     "pmgt_eval_workspace_bytes", "pmgt_eval_reset", "pmgt_eval_append", "pmgt_eval_reduce",
     "pmgt_weight_average_update", "pmgt_weight_swap",
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
+    "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -250,6 +262,10 @@ def hip():
     L.pmgt_rank_reset.argtypes = [vp, i64, vp, i, vp, vp, vp]
     L.pmgt_rank_append.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp]
     L.pmgt_rank_reduce.argtypes = [vp, i64, i64, vp]
+    L.pmgt_ncf_score.argtypes = [C.POINTER(NcfHeadC), vp, vp, vp, i64, i64, vp, i64, vp]
+    L.pmgt_topk_workspace_bytes.restype = i64
+    L.pmgt_topk_workspace_bytes.argtypes = [i64, i64]
+    L.pmgt_topk_rows.argtypes = [vp, i64, i64, i64, i, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
     _hip = L
     return L
 

@@ -1,0 +1,345 @@
+"""Recommendation from the whole catalogue: for a batch of users, the k best items of a trained PMGT_NCF that the user has not interacted
+with.  The reference has no such path (its test step, pmgt/ncf/trainer.py:202-219, does `pred.topk(100)` on one sampled candidate list per
+user); here the head (pmgt/pmgt_ncf/models.py:91-105) is fused into one HIP kernel that scores every (user, item) pair of a batch without
+materialising pair rows (pmgt_ncf_score), and a second kernel selects per row (pmgt_topk_rows).
+
+THE ORDER is that of the ranking metrics: descending `score_key`, and among equal keys THE LOWER ITEM INDEX FIRST.
+
+The pure-numpy part (topk_host, ncf_head_host, exclusion_csr) needs no GPU and is the yardstick of the kernels."""
+import ctypes as C
+
+import numpy as np
+
+from .evaluation import score_key
+
+TOPK_MAX_K = 1024                                # PMGT_TOPK_MAX_K
+TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1, 2            # PMGT_TOPK_FLAG_*
+SCORE_WORKSPACE_BYTES = 256 << 20                # recommend(batch_users=None): the [batch, I] fp32 score rows stay within this
+NCF_FACTORS, NCF_MAX_LAYERS, NCF_MAX_D = (8, 16, 32, 64), 4, 256      # what pmgt_ncf_score covers
+NCF_MAX_USERS = 1 << 20                          # PMGT_NCF_MAX_USERS: users per pmgt_ncf_score call
+
+
+# ---- host side: pure numpy ------------------------------------------------------------------------------------------------------------------
+def check_k(k) -> int:
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an integer in [1, {TOPK_MAX_K}]")
+    return int(k)
+
+
+def check_csr(indptr, items, user_num: int, item_num: int):
+    """(indptr int64 [user_num + 1], items int32) validated as pmgt_topk_rows expects its CSR: indptr non-decreasing from 0 to len(items), items in
+    [0, item_num)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    items64 = np.ascontiguousarray(items, dtype=np.int64)
+    if indptr.shape != (user_num + 1,) or items64.ndim != 1:
+        raise ValueError(f"exclude: indptr {indptr.shape} must be [user_num + 1 = {user_num + 1}] and items one-dimensional")
+    if indptr[0] != 0 or indptr[-1] != len(items64) or (np.diff(indptr) < 0).any():
+        raise ValueError("exclude: indptr must be non-decreasing from 0 to len(items)")
+    if len(items64) and (items64.min() < 0 or items64.max() >= item_num):
+        raise ValueError(f"exclude: excluded items in [{int(items64.min())}, {int(items64.max())}] outside the model's [0, {item_num})")
+    return indptr, items64.astype(np.int32)
+
+
+def exclusion_csr(exclude, user_num: int, item_num: int):
+    """The exclusion CSR over user ids from `exclude`: None (nothing excluded), an iterable of (user, item) pairs -- typically the training
+    interactions --, or a ready (indptr, items) pair of arrays.  -> (indptr int64 [user_num + 1], items int32), each list sorted by item."""
+    if exclude is None:
+        return np.zeros(user_num + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in exclude) \
+            and len(exclude[0]) == user_num + 1:
+        return check_csr(exclude[0], exclude[1], user_num, item_num)
+    pairs = np.asarray(list(exclude) if not isinstance(exclude, np.ndarray) else exclude)
+    if pairs.size == 0:
+        return np.zeros(user_num + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError(f"exclude: expected (user, item) integer pairs, got an array of shape {pairs.shape} and dtype {pairs.dtype}")
+    pairs = pairs.astype(np.int64)
+    if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= user_num:
+        raise ValueError(f"exclude: users in [{int(pairs[:, 0].min())}, {int(pairs[:, 0].max())}] outside the model's [0, {user_num})")
+    if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= item_num:
+        raise ValueError(f"exclude: excluded items in [{int(pairs[:, 1].min())}, {int(pairs[:, 1].max())}] outside the model's [0, {item_num})")
+    order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+    indptr = np.zeros(user_num + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pairs[:, 0], minlength=user_num), out=indptr[1:])
+    return indptr, pairs[order, 1].astype(np.int32)
+
+
+def topk_host(scores, k: int, indptr=None, items=None, users=None):
+    """The yardstick of pmgt_topk_rows, pure numpy: per row of scores [n, I] the k best eligible items by a STABLE argsort on descending
+    `score_key` (NaN first, -0.0 and 0.0 tie; among equal keys the lower item index first).  Item j is excluded for row r iff it is in the
+    list indptr[users[r]] .. indptr[users[r] + 1] of `items` (indptr None: everything is eligible).
+    -> (items int32 [n, k], scores fp32 [n, k], flags uint32 [n]): -1 / -inf past the eligible count; flag bit 0 = a NaN among the eligible
+    scores, bit 1 = fewer than k eligible items."""
+    k = check_k(k)
+    x = np.ascontiguousarray(scores, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError(f"topk_host: scores {x.shape} must be [n, I] with I >= 1")
+    n, n_items = x.shape
+    eligible = np.ones((n, n_items), dtype=bool)
+    if indptr is not None:
+        users = np.asarray(users, dtype=np.int64)
+        for r in range(n):
+            eligible[r, np.asarray(items[indptr[users[r]]: indptr[users[r] + 1]], dtype=np.int64)] = False
+    # descending by key, stable: ascending in (2^32 - 1 - key); the excluded behind every eligible item
+    inv = np.where(eligible, np.int64(0xFFFFFFFF) - score_key(x).reshape(n, n_items).astype(np.int64), np.int64(1) << 32)
+    order = np.argsort(inv, axis=1, kind="stable")
+    count = eligible.sum(axis=1)
+    out_items = np.full((n, k), -1, dtype=np.int32)
+    out_scores = np.full((n, k), -np.inf, dtype=np.float32)
+    kk = min(k, n_items)
+    live = np.arange(kk)[None, :] < count[:, None]
+    out_items[:, :kk] = np.where(live, order[:, :kk], -1)
+    out_scores[:, :kk] = np.where(live, np.take_along_axis(x, order[:, :kk], axis=1), np.float32(-np.inf))
+    flags = ((np.isnan(x) & eligible).any(axis=1) * TOPK_FLAG_NAN + (count < k) * TOPK_FLAG_SHORT).astype(np.uint32)
+    return out_items, out_scores, flags
+
+
+def head_shape(weights: dict):
+    """(factor_num, num_layers, kind, d) of a head given as a state_dict-keyed mapping."""
+    num_layers = 0
+    while f"mlp_layers.{num_layers}.linear.weight" in weights:
+        num_layers += 1
+    if num_layers < 1:
+        raise ValueError("the head has no mlp_layers.0.linear.weight")
+    d = int(weights["mlp_user_embeddings.weight"].shape[1])
+    kind = "NeuMF-end" if weights.get("gmf_user_embeddings.weight") is not None else "MLP"
+    return d >> (num_layers - 1), num_layers, kind, d
+
+
+def ncf_head_host(weights: dict, users, table, dtype=np.float64) -> np.ndarray:
+    """PMGT_NCF.head in eval mode on plain arrays, every user of `users` against every row of `table` [I, d] -> logits [len(users), I] in
+    `dtype`.  `weights` is keyed like the model's state_dict ("mlp_user_embeddings.weight", "mlp_layers.<i>.linear.weight" / ".bias",
+    "predict_layer.weight" / ".bias" and, for NeuMF-end, "gmf_user_embeddings.weight" / "gmf_item_embeddings.weight"); arrays or CPU
+    tensors.  The formula as the torch head states it: layer 0 on the UNSPLIT concatenation [user ; item]."""
+    w = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
+    _, num_layers, kind, d = head_shape(w)
+    users = np.asarray(users, dtype=np.int64)
+    table = np.asarray(table).astype(dtype)
+    n, n_items = len(users), len(table)
+    out = np.empty((n, n_items), dtype=dtype)
+    per = max(1, (1 << 22) // (n_items * 2 * d))             # users per chunk of pair rows: about 4 M elements of layer 0's input
+    for lo in range(0, n, per):
+        u = users[lo: lo + per]
+        m = len(u)
+        h = np.concatenate([np.repeat(w["mlp_user_embeddings.weight"][u], n_items, axis=0), np.tile(table, (m, 1))], axis=1)
+        for i in range(num_layers):
+            h = np.maximum(h @ w[f"mlp_layers.{i}.linear.weight"].T + w[f"mlp_layers.{i}.linear.bias"], 0)
+        if kind == "NeuMF-end":
+            gmf = np.repeat(w["gmf_user_embeddings.weight"][u], n_items, axis=0) * np.tile(w["gmf_item_embeddings.weight"][:n_items], (m, 1))
+            h = np.concatenate([gmf, h], axis=1)
+        out[lo: lo + m] = (h @ w["predict_layer.weight"].T + w["predict_layer.bias"]).reshape(m, n_items)
+    return out
+
+
+def check_head_covered(factor_num: int, num_layers: int, kind: str) -> None:
+    """ValueError naming the limit when pmgt_ncf_score does not cover the head."""
+    if kind not in ("MLP", "NeuMF-end"):
+        raise ValueError(f"ncf_score: model kind {kind!r}, covered: 'MLP', 'NeuMF-end'")
+    if factor_num not in NCF_FACTORS:
+        raise ValueError(f"ncf_score: factor_num = {factor_num}, covered: {NCF_FACTORS}")
+    if not 1 <= num_layers <= NCF_MAX_LAYERS:
+        raise ValueError(f"ncf_score: num_layers = {num_layers} outside [1, {NCF_MAX_LAYERS}]")
+    if factor_num << (num_layers - 1) > NCF_MAX_D:
+        raise ValueError(f"ncf_score: d = factor_num * 2^(num_layers - 1) = {factor_num << (num_layers - 1)} above {NCF_MAX_D}")
+
+
+# ---- device side ------------------------------------------------------------------------------------------------------------------------------
+def _stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class NcfScorer:
+    """The fused head over one item table: NcfScorer(weights, table) splits layer 0 and computes the per-item half Pi = table W0e^T + b0
+    once; score(users) computes the per-user half Pu = U_mlp[users] W0u^T (a torch matmul: plumbing) and launches pmgt_ncf_score.
+    `weights`: the head's parameters as contiguous fp32 DEVICE tensors keyed like the state_dict (a PMGT_NCF's own state_dict serves);
+    `table` [I, d] fp32 on the same device.  Nothing in here copies to the host or waits for the device."""
+
+    def __init__(self, weights: dict, table):
+        import torch
+        from . import _lib
+        self.lib = _lib.hip()
+        self.factor, self.num_layers, self.kind, self.d = head_shape(weights)
+        check_head_covered(self.factor, self.num_layers, self.kind)
+        need = ["mlp_user_embeddings.weight", "predict_layer.weight", "predict_layer.bias"]
+        need += [f"mlp_layers.{i}.linear.{p}" for i in range(self.num_layers) for p in ("weight", "bias")]
+        need += ["gmf_user_embeddings.weight", "gmf_item_embeddings.weight"] if self.kind == "NeuMF-end" else []
+        self.w = {}
+        for key in need:
+            t = weights[key]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != table.device or not t.is_cuda:
+                raise ValueError(f"ncf_score: {key} must be an fp32 tensor on the table's device")
+            self.w[key] = t.detach().contiguous()
+        if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != self.d or table.shape[0] < 1:
+            raise ValueError(f"ncf_score: the item table {tuple(table.shape)} must be fp32 [I >= 1, d = {self.d}]")
+        self.n_items = int(table.shape[0])
+        self.user_num = int(self.w["mlp_user_embeddings.weight"].shape[0])
+        w0 = self.w["mlp_layers.0.linear.weight"]
+        if tuple(w0.shape) != (self.d, 2 * self.d):
+            raise ValueError(f"ncf_score: mlp_layers.0.linear.weight {tuple(w0.shape)} must be [{self.d}, {2 * self.d}]")
+        if self.kind == "NeuMF-end" and self.w["gmf_item_embeddings.weight"].shape[0] < self.n_items:
+            raise ValueError("ncf_score: gmf_item_embeddings.weight has fewer rows than the item table")
+        self._w0u_t = w0[:, :self.d].t().contiguous()
+        self.pi = torch.addmm(self.w["mlp_layers.0.linear.bias"], table, w0[:, self.d:].t()).contiguous()
+        h = _lib.NcfHeadC()
+        h.factor_num, h.num_layers, h.kind, h.user_num = self.factor, self.num_layers, _lib.NCF_KINDS.index(self.kind), self.user_num
+        for i in range(1, self.num_layers):
+            h.weight[i] = self.w[f"mlp_layers.{i}.linear.weight"].data_ptr()
+            h.bias[i] = self.w[f"mlp_layers.{i}.linear.bias"].data_ptr()
+        h.predict_weight, h.predict_bias = self.w["predict_layer.weight"].data_ptr(), self.w["predict_layer.bias"].data_ptr()
+        if self.kind == "NeuMF-end":
+            h.gmf_user, h.gmf_item = self.w["gmf_user_embeddings.weight"].data_ptr(), self.w["gmf_item_embeddings.weight"].data_ptr()
+        self._head = h
+
+    def score(self, users, out=None):
+        """users int64 [n] on the device (ids in [0, user_num): the caller checks them on the host) -> scores fp32 [n, row_stride] with the logit
+        of (users[r], item j) at [r, j]; `out` (fp32, contiguous, [>= n, row_stride >= I]) is written in place and entries [r, I ..) are left."""
+        import torch
+        from . import _lib
+        n = int(users.shape[0])
+        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.pi.device or not users.is_contiguous() or n < 1:
+            raise ValueError("ncf_score: users must be a contiguous int64 tensor [n >= 1] on the table's device")
+        if out is None:
+            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.pi.device)
+        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
+                or out.device != self.pi.device:
+            raise ValueError(f"ncf_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
+        pu = self.w["mlp_user_embeddings.weight"].index_select(0, users) @ self._w0u_t
+        _lib.check(self.lib.pmgt_ncf_score(C.byref(self._head), pu.data_ptr(), self.pi.data_ptr(), users.data_ptr(), n, self.n_items,
+                                           out.data_ptr(), int(out.shape[1]), _stream()))
+        return out
+
+
+class TopkRows:
+    """pmgt_topk_rows over score rows of `n_items` live entries, up to `max_rows` rows a call, with an optional exclusion CSR over user ids
+    (indptr int64 [user_num + 1], items int32; validated on the host by check_csr).  select(scores, users) -> (items int32 [n, k], scores
+    fp32 [n, k], flags uint32 [n]) as device tensors; enqueues one launch, never waits."""
+
+    def __init__(self, device, max_rows: int, n_items: int, k: int, indptr=None, items=None, user_num: int = 0):
+        import torch
+        from . import _lib
+        self.lib = _lib.hip()
+        self.device = torch.device(device)
+        self.k, self.max_rows, self.n_items = check_k(k), int(max_rows), int(n_items)
+        nbytes = int(self.lib.pmgt_topk_workspace_bytes(self.max_rows, self.n_items))
+        if nbytes < 0:
+            raise ValueError(f"topk_rows: {max_rows} rows of {n_items} items outside the limits (rows >= 1, items in [1, 2^31 - 2])")
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.user_num = int(user_num)
+        self._indptr = self._items = None
+        if indptr is not None:
+            indptr, items = check_csr(indptr, items, self.user_num, self.n_items)
+            self._indptr = torch.from_numpy(indptr).to(self.device)
+            self._items = torch.from_numpy(items).to(self.device)
+
+    def select(self, scores, users=None, out=None):
+        import torch
+        n, stride = int(scores.shape[0]), int(scores.shape[1])
+        if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous() or scores.device != self._ws.device \
+                or not 1 <= n <= self.max_rows or stride < self.n_items:
+            raise ValueError(f"topk_rows: scores must be a contiguous fp32 device tensor [1 .. {self.max_rows}, >= {self.n_items}]")
+        if self._indptr is not None and (users is None or users.dtype != torch.int64 or tuple(users.shape) != (n,)
+                                         or users.device != self._ws.device or not users.is_contiguous()):
+            raise ValueError("topk_rows: with an exclusion CSR, users must be a contiguous int64 device tensor [n]")
+        if out is None:
+            out = (torch.empty(n, self.k, dtype=torch.int32, device=self.device), torch.empty(n, self.k, dtype=torch.float32, device=self.device),
+                   torch.empty(n, dtype=torch.int32, device=self.device))
+        from . import _lib
+        excl = self._indptr is not None
+        _lib.check(self.lib.pmgt_topk_rows(scores.data_ptr(), stride, n, self.n_items, self.k, users.data_ptr() if excl else 0,
+                                           self._indptr.data_ptr() if excl else 0, self._items.data_ptr() if excl and len(self._items) else 0,
+                                           self.user_num if excl else 0, len(self._items) if excl else 0, self._ws.data_ptr(),
+                                           out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()))
+        return out
+
+
+def default_batch_users(n_users: int, n_items: int) -> int:
+    """The largest batch whose [batch, I] fp32 score rows stay within SCORE_WORKSPACE_BYTES (at least one user, at most what one
+    pmgt_ncf_score call takes)."""
+    return int(max(1, min(n_users, SCORE_WORKSPACE_BYTES // (4 * n_items), NCF_MAX_USERS)))
+
+
+def host_scores(model, table, users, pair_chunk: int = 1 << 18) -> np.ndarray:
+    """impl="host": `model.head` on chunks of (user, item) pair rows gathered from `table`, the full score rows [U, I] copied out."""
+    import torch
+    dev = table.device
+    n_items = int(table.shape[0])
+    item_ids = torch.arange(n_items, device=dev)
+    per = max(1, pair_chunk // n_items)
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, len(users), per):
+            u = torch.from_numpy(np.ascontiguousarray(users[lo: lo + per])).to(dev)
+            m = len(u)
+            logits = model.head(u[:, None].expand(m, n_items).reshape(-1), item_ids.repeat(m), table.repeat(m, 1))
+            rows.append(logits.view(m, n_items).cpu().numpy())
+    return np.concatenate(rows)
+
+
+def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int = None, impl: str = "device", table=None, threads: int = 8,
+              seed: int = 0):
+    """For every user of `users`, the k best items of `model`'s whole catalogue (a PMGT_NCF) that are not in the user's exclusion list
+    -> (items int64 [U, k], scores fp32 [U, k]) as numpy, best first; ties rank the lower item index first.
+    exclude: an iterable of (user, item) pairs, typically the training interactions, or a ready (indptr, items) CSR pair over user ids; it
+      is built into the CSR once.  None excludes nothing.
+    A user with FEWER THAN k eligible items gets item -1 and score -inf in the slots past them; that is not an error.
+    table: a catalogue table of encode_catalogue to reuse; None encodes it once, in eval mode, and restores the caller's train / eval mode.
+    batch_users: users per launch; None picks the largest batch whose [batch, I] fp32 score rows stay within 256 MiB.
+    impl="device": pmgt_ncf_score then pmgt_topk_rows per batch; nothing is copied to the host and nothing waits inside the loop, one copy
+      at the end fetches items, scores and flags.  impl="host": the yardstick -- `model.head` on chunks of pair rows, the full score rows
+      copied out, topk_host.
+    Raises ValueError for users or excluded ids outside the model's tables, k outside [1, 1024], a user with a NaN score among their
+    eligible items (naming how many users), and -- impl="device" only -- a head shape the kernel does not cover."""
+    if impl not in ("host", "device"):
+        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    k = check_k(k)
+    users = np.ascontiguousarray(users, dtype=np.int64)
+    if users.ndim != 1 or len(users) < 1:
+        raise ValueError(f"recommend: users {users.shape} must be [U >= 1]")
+    if users.min() < 0 or users.max() >= model.user_num:
+        raise ValueError(f"recommend: users in [{int(users.min())}, {int(users.max())}] outside the model's [0, {model.user_num})")
+    indptr, excl = exclusion_csr(exclude, model.user_num, model.item_num)
+    if impl == "device":
+        check_head_covered(model.factor_num, model.num_layers, model.model)
+    if batch_users is not None and (not isinstance(batch_users, (int, np.integer)) or batch_users < 1):
+        raise ValueError(f"recommend: batch_users = {batch_users!r} must be a positive integer or None")
+    import torch
+    from .evaluation import encode_catalogue
+    n_users, n_items = len(users), model.item_num
+    batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
+    if table is None:
+        was_training = model.training
+        model.eval()
+        try:
+            table = encode_catalogue(model, sampler, threads=threads, seed=seed)
+        finally:
+            model.train(was_training)
+    dev = model.engine.device
+    if tuple(table.shape) != (n_items, model.config.hidden_size) or table.dtype != torch.float32 or table.device != dev:
+        raise ValueError(f"recommend: table must be fp32 [{n_items}, {model.config.hidden_size}] on {dev}")
+    if impl == "host":
+        was_training = model.training
+        model.eval()
+        try:
+            s = host_scores(model, table, users)
+        finally:
+            model.train(was_training)
+        items, scores, flags = topk_host(s, k, indptr, excl, users)
+    else:
+        with torch.no_grad():
+            scorer = NcfScorer({key: v for key, v in model.state_dict().items() if not key.startswith(("bert.", "feat_embeddings."))}, table)
+            picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
+            users_d = torch.from_numpy(users).to(dev)
+            out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
+                   torch.empty(n_users, dtype=torch.int32, device=dev))
+            work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
+            for lo in range(0, n_users, batch):
+                hi = min(lo + batch, n_users)
+                scorer.score(users_d[lo:hi], out=work)
+                picker.select(work[: hi - lo], users_d[lo:hi], out=tuple(t[lo:hi] for t in out))
+            items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
+        flags = flags.view(np.uint32)
+    n_nan = int(np.count_nonzero(flags & TOPK_FLAG_NAN))
+    if n_nan:
+        raise ValueError(f"recommend: {n_nan} of {n_users} users have a NaN score among their eligible items")
+    return items.astype(np.int64), scores
