@@ -107,6 +107,26 @@ int pmgt_op_linear_ln_bwd(const void* A, int64_t lda, const void* B, int64_t ldb
                           const void* y, const float* stats, const float* gamma, const float* beta, void* dy_tmp, void* dx, void* dx_drop,
                           float drop_p, uint32_t drop_site, const uint64_t* rng, float* part, float* dgamma_dbeta_dbias,
                           uint32_t path_opts, void* stream);
+/* ---- the compacted-row forms of the last-layer shortcut (the tail of the last encoder layer on the rows the loss reads): the launch is
+ * sized for the capacity M on the host, the live row count min(M, *m_dev) is read on the device.  Rows >= the live count are neither
+ * read nor written, and no sum counts them.  Each entry calls the host functions the engine calls at `sc` (csrc/engine.hip); the dispatch
+ * of linear(), which is local to that file, is restated in ops/compact_rows.hip.  tests/test_compact_rows_gpu.py.
+ * pmgt_op_linear with A rows through a_rows (logical row m reads A + a_rows[m] * lda; NULL: none), the residual row through the same list
+ * (res_gather; needs a_rows) and m_dev: the dispatcher picks gemm_rowln, gemm_ws, gemm_wsr, gemm_wsr512 or the 128 x 128 tile, with the
+ * standalone LayerNorm launch (which takes m_dev too) where LayerNorm is not fused. */
+int pmgt_op_linear_rows(int dtype, const void* A, int64_t lda, const int64_t* a_rows, const void* B, int64_t ldb, void* C, int64_t ldc, int M,
+                        int N, int K, const float* bias, int epilogue, void* aux, int64_t ldaux, const void* residual, int64_t ldr,
+                        int res_gather, float drop_p, uint32_t drop_site, const uint64_t* rng, void* ln_out, float* ln_stats,
+                        const float* ln_gamma, const float* ln_beta, float ln_eps, const int* m_dev, uint32_t path_opts, void* stream);
+/* pmgt_op_layernorm_bwd with m_dev (x = the stored LayerNorm input); part: [ceil(M/64)][3][d] -- workgroups past the live rows write zeros */
+int pmgt_op_layernorm_bwd_rows(int dtype, const void* dy, const void* x, const float* stats, const float* gamma, void* dx,
+                               void* dx_drop, float* part, float* dgamma_dbeta, int M, int d, float in_drop_p, uint32_t in_site,
+                               float out_drop_p, uint32_t out_site, const uint64_t* rng, const int* m_dev, void* stream);
+/* pmgt_op_gemm_tn_bias with a row gather on Q, m_dev, accumulate (out and bias_out: +=) and the splits taken from m_for_splits instead of M
+ * (the engine: max(256, M / 3)): slab holds pmgt_op_gemm_tn_slab_elems(dtype, m_for_splits, N1, N2) floats, bias_slab [512][N1] */
+int pmgt_op_gemm_tn_bias_rows(int dtype, const void* P, int64_t ldp, const void* Q, int64_t ldq, const int64_t* q_rows, int M, int m_for_splits,
+                              int N1, int N2, float* slab, float* out, float* bias_slab, float* bias_out, int accumulate, const int* m_dev,
+                              uint32_t path_opts, void* stream);
 /* Fused Q|K|V|C projection + attention forward (bf16; S = 32, dh = 32, hidden 128 or 256; returns -3 otherwise):
  * x [n_seq*S, d], w [4d, d] (rows q | k | v | c), bias [4d] fp32 -> qkvc [n_seq*S, 4d], ctx [n_seq*S, d]. */
 int pmgt_op_qkvc_attention_fwd(const void* x, const void* w, const float* bias, const float* mask, void* qkvc, void* ctx,

@@ -127,6 +127,7 @@ OPS_SYMBOLS = [
     "pmgt_op_nfr_diff", "pmgt_op_loss_finish", "pmgt_op_scatter_rows", "pmgt_op_adamw", "pmgt_op_mirror",
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
     "pmgt_op_adamw_guarded", "pmgt_op_eval_append_scores", "pmgt_op_eval_small_max",
+    "pmgt_op_linear_rows", "pmgt_op_layernorm_bwd_rows", "pmgt_op_gemm_tn_bias_rows",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -219,6 +220,9 @@ def hip():
     L.pmgt_op_attention_bwd_wgrad_parts.argtypes = [i]
     L.pmgt_op_attention_bwd_wgrad_vc2_parts.argtypes = [i]
     L.pmgt_op_gemm_tn_bias.argtypes = [i, vp, i64, vp, i64, i, i, i, vp, vp, vp, vp, i, i, u32, vp]
+    L.pmgt_op_linear_rows.argtypes = [i, vp, i64, vp, vp, i64, vp, i64, i, i, i, vp, i, vp, i64, vp, i64, i, f, u32, vp, vp, vp, vp, vp, f, vp, u32, vp]
+    L.pmgt_op_layernorm_bwd_rows.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, f, u32, f, u32, vp, vp, vp]
+    L.pmgt_op_gemm_tn_bias_rows.argtypes = [i, vp, i64, vp, i64, vp, i, i, i, i, vp, vp, vp, vp, i, vp, u32, vp]
     L.pmgt_quantize_e4m3.argtypes = [vp, vp, i64, f, vp]
     L.pmgt_dequantize_e4m3.argtypes = [vp, vp, i64, f, vp]
     L.pmgt_op_quant_rows_e4m3.argtypes = [i, vp, i64, i, i, vp, i64, vp, vp]
@@ -275,7 +279,7 @@ class Ops:
     mask (include/pmgt_ops.h) gets it from `self.path` (an int, or option names through `use`), so call sites read as the
     kernel's own argument list.  Everything else passes straight through to the CDLL."""
     _BEFORE_STREAM = {"pmgt_op_gemm_nt", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_linear", "pmgt_op_linear_ln_bwd", "pmgt_op_attention_fwd",
-                      "pmgt_op_attention_bwd"}
+                      "pmgt_op_attention_bwd", "pmgt_op_linear_rows", "pmgt_op_gemm_tn_bias_rows"}
     _LAST = {"pmgt_op_gemm_tn_slab_elems"}
 
     def __init__(self, lib=None):

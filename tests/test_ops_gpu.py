@@ -4,7 +4,10 @@ restatement of pmgt/pmgt/modeling_pmgt.py:420-534 with autograd for the backward
 and optimizer kernels have theirs in test_rowops_gpu.py; the dropout hash, the NFR masking RNG (nfr_generate) and the
 compacted-row list of the last layer (build_need_rows) are compared bit for bit with a numpy restatement in
 test_dropout_rng_gpu.py, and every kernel here runs with dropout ON against fp64 with restated masks in
-test_dropout_ops_gpu.py.  Reached only end to end: the batch copies (multi_copy), the RNG step counter (advance_rng) and
+test_dropout_ops_gpu.py.  The compacted-row forms of the last-layer shortcut -- the same GEMM, LayerNorm and weight-gradient kernels with
+a device-side live row count, gathered A / residual / Q rows and splits sized from a third of the capacity (gemm_ws, gemm_wsr, gemm_wsr512,
+gemm_rowln, the tiled gemm_nt + ln_fwd, ln_bwd, gemm_tn with its bias sums) -- have theirs in test_compact_rows_gpu.py, with NaN dead rows and
+sentinel-filled outputs.  Reached only end to end: the batch copies (multi_copy), the RNG step counter (advance_rng) and
 the dtype casts."""
 import ctypes as C
 import math
