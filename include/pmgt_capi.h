@@ -360,6 +360,44 @@ int pmgt_topk_rows(const float* scores, int64_t row_stride, int64_t n, int64_t n
                    const int32_t* excluded, int64_t user_num, int64_t n_excluded, void* workspace, int32_t* out_items, float* out_scores,
                    uint32_t* out_flags, void* stream);
 
+/* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
+ * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
+ * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and
+ * the same inputs give the same bits.  With d = factor_num * 2^(num_layers - 1):
+ *   x0 = [mlp_user[u] ; table[i]],  h(l+1) = relu(W_l h_l + b_l) for l = 0 .. num_layers - 1   (W_0 UNSPLIT, [d][2 d]; dropout is 0),
+ *   z = predict_weight . [gmf_user[u] * gmf_item[i] ; h_L] + predict_bias   (PMGT_NCF_MLP: predict_weight . h_L + predict_bias),
+ *   loss = mean over the pairs of max(z, 0) - z y + log1p(exp(-|z|)),   dz = (sigmoid(z) - y) / n,   the ReLU passes where h > 0.
+ * THE PARAMETERS are ONE flat fp32 buffer, the gradients another of the same layout; pmgt_ncf_train_layout gives the offset in floats of
+ * each tensor, in this order of slots (row-major, the state_dict's shapes), -1 for a tensor the head does not have:
+ *   [0] mlp_user_embeddings.weight [user_num][d]
+ *   [1] gmf_user_embeddings.weight [user_num][factor_num]      [2] gmf_item_embeddings.weight [item_num][factor_num]      (NeuMF-end)
+ *   [3 + 2 l] mlp_layers.l.linear.weight [d >> l][2 (d >> l)]    [4 + 2 l] mlp_layers.l.linear.bias [d >> l]
+ *   [11] predict_layer.weight [factor_num] or [2 factor_num] = [gmf | mlp]      [12] predict_layer.bias [1]
+ * and returns the parameter count; the tensors are packed in slot order, the three embedding tables first.
+ * THE GRADIENT BUFFER IS WRITTEN WHOLE: embedding rows no pair touches hold +0.0.  Rows hit by several pairs are summed in pair order,
+ * the weight gradients over the pairs in one fixed order (32-pair chunks dealt to four accumulators, added as (0 + 1) + (2 + 3)).
+ * users / items int64 [n] (ids inside the tables: THE CALLER CHECKS THEM, they are read as they are), labels fp32 [n], table fp32
+ * [item_num][d], loss one device float, logits fp32 [n] or NULL; workspace: pmgt_ncf_train_workspace_bytes(...) bytes of 16-byte aligned
+ * device memory.  Covered: what pmgt_ncf_score covers (factor_num 8 / 16 / 32 / 64, 1 .. PMGT_NCF_MAX_LAYERS layers, d <= 256, both
+ * kinds), 1 <= n <= PMGT_NCF_TRAIN_MAX_PAIRS.  Refused (-2; the two sizing entries return it as their value) before anything is launched:
+ * a head or n outside these limits, a NULL or misaligned buffer (table, parameters, gradients and workspace: 16 bytes), a short workspace.
+ * Added without a bump of pmgt_abi_version(): one struct, three entries, nothing existing moved. */
+#define PMGT_NCF_TRAIN_MAX_PAIRS 65536
+#define PMGT_NCF_TRAIN_TENSORS 13
+typedef struct pmgt_ncf_train {
+    int factor_num, num_layers;
+    int kind;                                     /* PMGT_NCF_* */
+    int reserved;
+    int64_t user_num, item_num;                   /* rows of the user tables; rows of `table` and of gmf_item */
+    const float* table;                           /* frozen item embeddings [item_num][d] */
+    const float* params;                          /* the flat parameters */
+    float* grads;                                 /* the flat gradients, written whole */
+} pmgt_ncf_train;
+int64_t pmgt_ncf_train_layout(int factor_num, int num_layers, int kind, int64_t user_num, int64_t item_num, int64_t* offsets);
+int64_t pmgt_ncf_train_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n);
+int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                        float* logits, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average
  * that lives inside a captured step.  One update is, per element,

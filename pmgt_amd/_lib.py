@@ -115,6 +115,7 @@ HIP_SYMBOLS = [
     "pmgt_weight_average_update", "pmgt_weight_swap",
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
+    "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -270,6 +271,11 @@ def hip():
     L.pmgt_topk_workspace_bytes.restype = i64
     L.pmgt_topk_workspace_bytes.argtypes = [i64, i64]
     L.pmgt_topk_rows.argtypes = [vp, i64, i64, i64, i, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
+    L.pmgt_ncf_train_layout.restype = i64
+    L.pmgt_ncf_train_layout.argtypes = [i, i, i, i64, i64, vp]
+    L.pmgt_ncf_train_workspace_bytes.restype = i64
+    L.pmgt_ncf_train_workspace_bytes.argtypes = [i, i, i, i64]
+    L.pmgt_ncf_train_grad.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]      # (head: byref of ncf_train.NcfTrainC)
     _hip = L
     return L
 

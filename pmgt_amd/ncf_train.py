@@ -1,0 +1,414 @@
+"""Training of the head of a PMGT_NCF over a FROZEN item table: the reference's downstream experiment (scripts/run_ncf.sh,
+pmgt/ncf/trainer.py:183-200 with --item-init-emb-path: the exported item embeddings as a frozen table, `num_ng` fresh negatives per positive
+every epoch, BCEWithLogitsLoss, gradient clipping, AdamW, validation on nDCG / recall with early stopping).
+
+  ncf_head_grad_host   loss, logits and the gradient of every head parameter in numpy: the yardstick of the kernels
+  ng_sample            the reference's training-mode negative sampling, the same stream of draws
+  NcfHeadTrainer       the head's parameters in one flat device buffer; step() = pmgt_ncf_train_grad (two launches) + pmgt_op_adamw (three)
+  fit_ncf              epochs of sampled pairs, ranking validation, early stopping, the best head restored
+
+The pure-numpy part needs no GPU."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from .recommend import check_head_covered, head_shape
+
+NCF_TRAIN_MAX_PAIRS = 65536                      # PMGT_NCF_TRAIN_MAX_PAIRS
+NCF_TRAIN_TENSORS = 13                           # PMGT_NCF_TRAIN_TENSORS
+HEAD_PREFIXES = ("mlp_user_embeddings.", "mlp_layers.", "predict_layer.", "gmf_user_embeddings.", "gmf_item_embeddings.")
+
+
+# ---- host side: pure numpy ------------------------------------------------------------------------------------------------------------------
+def head_layout(factor_num: int, num_layers: int, kind: str, user_num: int, item_num: int):
+    """The flat parameter layout of pmgt_ncf_train_grad (include/pmgt_capi.h): -> ({state_dict key: (offset in floats, shape)} in buffer
+    order, parameter count).  The three embedding tables come first, then weight and bias per layer (layer 0 UNSPLIT, [d, 2 d]), then the
+    predict layer; every tensor but the last (predict_layer.bias, one float) has a multiple of 8 floats, so every offset is 32-byte aligned."""
+    check_head_covered(factor_num, num_layers, kind)
+    if not (isinstance(user_num, (int, np.integer)) and isinstance(item_num, (int, np.integer)) and 1 <= user_num < 2 ** 31 - 1
+            and 1 <= item_num < 2 ** 31 - 1):
+        raise ValueError(f"ncf_train: user_num = {user_num!r} and item_num = {item_num!r} must be integers in [1, 2^31 - 2]")
+    d = factor_num << (num_layers - 1)
+    shapes = [("mlp_user_embeddings.weight", (int(user_num), d))]
+    if kind == "NeuMF-end":
+        shapes += [("gmf_user_embeddings.weight", (int(user_num), factor_num)), ("gmf_item_embeddings.weight", (int(item_num), factor_num))]
+    for i in range(num_layers):
+        out = d >> i
+        shapes += [(f"mlp_layers.{i}.linear.weight", (out, 2 * out)), (f"mlp_layers.{i}.linear.bias", (out,))]
+    shapes += [("predict_layer.weight", (1, factor_num * (2 if kind == "NeuMF-end" else 1))), ("predict_layer.bias", (1,))]
+    layout, at = {}, 0
+    for key, shape in shapes:
+        layout[key] = (at, shape)
+        at += int(np.prod(shape))
+    return layout, at
+
+
+def layout_slots(layout: dict):
+    """The offsets of `layout` in the slot order of pmgt_ncf_train_layout (-1: the head has no such tensor)."""
+    slots = ["mlp_user_embeddings.weight", "gmf_user_embeddings.weight", "gmf_item_embeddings.weight"]
+    slots += [f"mlp_layers.{i}.linear.{p}" for i in range(4) for p in ("weight", "bias")] + ["predict_layer.weight", "predict_layer.bias"]
+    return [layout[k][0] if k in layout else -1 for k in slots]
+
+
+def check_pairs(users, items, labels, user_num: int, item_num: int, max_pairs: int = NCF_TRAIN_MAX_PAIRS):
+    """(users int64 [n], items int64 [n], labels fp32 [n]) as the kernels read them; ValueError for shapes that differ, n outside
+    [1, max_pairs] and ids outside the tables (the kernels read the tables by them unchecked)."""
+    users, items = np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int64)
+    labels = np.ascontiguousarray(labels, dtype=np.float32)
+    n = len(users)
+    if users.ndim != 1 or items.shape != (n,) or labels.shape != (n,):
+        raise ValueError(f"ncf_train: users {users.shape}, items {items.shape} and labels {labels.shape} must be one [n]")
+    if not 1 <= n <= max_pairs:
+        raise ValueError(f"ncf_train: n = {n} pairs outside [1, {max_pairs}]")
+    if users.min() < 0 or users.max() >= user_num:
+        raise ValueError(f"ncf_train: users in [{int(users.min())}, {int(users.max())}] outside the model's [0, {user_num})")
+    if items.min() < 0 or items.max() >= item_num:
+        raise ValueError(f"ncf_train: items in [{int(items.min())}, {int(items.max())}] outside the table's [0, {item_num})")
+    return users, items, labels
+
+
+def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64):
+    """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
+    `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
+    model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
+    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order."""
+    w = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
+    factor, num_layers, kind, d = head_shape(w)
+    table = np.asarray(table).astype(dtype)
+    users, items, y = check_pairs(users, items, labels, len(w["mlp_user_embeddings.weight"]), len(table), max_pairs=1 << 40)
+    y = y.astype(dtype)
+    n = len(users)
+    one = dtype(1)
+    hs = [np.concatenate([w["mlp_user_embeddings.weight"][users], table[items]], axis=1)]
+    for i in range(num_layers):
+        hs.append(np.maximum(hs[-1] @ w[f"mlp_layers.{i}.linear.weight"].T + w[f"mlp_layers.{i}.linear.bias"], 0))
+    feat = hs[-1]
+    if kind == "NeuMF-end":
+        gu, gi = w["gmf_user_embeddings.weight"][users], w["gmf_item_embeddings.weight"][items]
+        feat = np.concatenate([gu * gi, feat], axis=1)
+    wp = w["predict_layer.weight"].reshape(-1)
+    z = feat @ wp + w["predict_layer.bias"][0]
+    e = np.exp(-np.abs(z))
+    loss = (np.maximum(z, 0) - z * y + np.log1p(e)).sum(dtype=dtype) / dtype(n)
+    dl = (np.where(z >= 0, one / (one + e), e / (one + e)) - y) / dtype(n)
+    grads = {"predict_layer.weight": (dl @ feat).reshape(1, -1), "predict_layer.bias": dl.sum(dtype=dtype).reshape(1)}
+    dfeat = dl[:, None] * wp[None, :]
+    if kind == "NeuMF-end":
+        dg, dh = dfeat[:, :factor], dfeat[:, factor:]
+        grads["gmf_user_embeddings.weight"] = np.zeros_like(w["gmf_user_embeddings.weight"])
+        grads["gmf_item_embeddings.weight"] = np.zeros_like(w["gmf_item_embeddings.weight"])
+        np.add.at(grads["gmf_user_embeddings.weight"], users, dg * gi)
+        np.add.at(grads["gmf_item_embeddings.weight"], items, dg * gu)
+    else:
+        dh = dfeat
+    for i in reversed(range(num_layers)):
+        dz = dh * (hs[i + 1] > 0)
+        grads[f"mlp_layers.{i}.linear.weight"] = dz.T @ hs[i]
+        grads[f"mlp_layers.{i}.linear.bias"] = dz.sum(axis=0, dtype=dtype)
+        dh = dz @ w[f"mlp_layers.{i}.linear.weight"]
+    grads["mlp_user_embeddings.weight"] = np.zeros_like(w["mlp_user_embeddings.weight"])
+    np.add.at(grads["mlp_user_embeddings.weight"], users, dh[:, :d])
+    assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype
+    return dtype(loss), z, grads
+
+
+def ng_sample(pairs, num_user: int, num_item: int, num_ng: int, seed: int, chunk: int = 1024):
+    """The training pairs of one epoch as the reference draws them (NCFDataset(pairs, ..., is_training=True).ng_sample() after
+    np.random.seed(seed), pmgt/ncf/datasets.py:85-101): the positives first, in the given order, then for each positive `num_ng` negatives,
+    each `RandomState(seed).randint(num_item)` redrawn while the item is one of the user's items
+    -> (users int64 [P (1 + num_ng)], items int64, labels fp32).
+    The draws are taken `chunk` at a time (randint(n, size=k) is the stream of k scalar calls) and handed to the open slots in order; a
+    rejected draw is consumed and its slot takes the next one, so no draw is skipped or reordered."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) < 1 or num_ng < 0:
+        raise ValueError(f"ng_sample: {len(pairs)} pairs and num_ng = {num_ng}: expected at least one pair and num_ng >= 0")
+    if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= num_user or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= num_item:
+        raise ValueError(f"ng_sample: pairs outside [0, {num_user}) x [0, {num_item})")
+    keys = np.unique(pairs[:, 0] * np.int64(num_item) + pairs[:, 1])
+    if num_ng > 0 and np.bincount(keys // num_item).max() >= num_item:
+        raise ValueError("ng_sample: a user holds every item: no negative exists for them")
+    rs = np.random.RandomState(seed)
+    slot_users = np.repeat(pairs[:, 0], num_ng)
+    n_slots = len(slot_users)
+    neg = np.empty(n_slots, dtype=np.int64)
+    s = 0
+    while s < n_slots:
+        m = min(int(chunk), n_slots - s)
+        draws = rs.randint(num_item, size=m).astype(np.int64)
+        t = 0
+        while t < m:
+            k = m - t                                          # (s + k <= n_slots: s grew by at most t since the chunk began)
+            cand = slot_users[s: s + k] * np.int64(num_item) + draws[t:]
+            at = np.minimum(np.searchsorted(keys, cand), len(keys) - 1)
+            bad = keys[at] == cand
+            r = int(np.argmax(bad)) if bad.any() else k
+            neg[s: s + r] = draws[t: t + r]
+            s += r
+            t += r + (1 if r < k else 0)                       # the rejected draw is used up
+    users = np.concatenate([pairs[:, 0], slot_users])
+    items = np.concatenate([pairs[:, 1], neg])
+    labels = np.concatenate([np.ones(len(pairs), dtype=np.float32), np.zeros(n_slots, dtype=np.float32)])
+    return users, items, labels
+
+
+# ---- device side ------------------------------------------------------------------------------------------------------------------------------
+def _stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class NcfTrainC(C.Structure):
+    """pmgt_ncf_train (include/pmgt_capi.h)."""
+    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("reserved", C.c_int), ("user_num", C.c_int64),
+                ("item_num", C.c_int64), ("table", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p)]
+
+
+class NcfHeadGrad:
+    """pmgt_ncf_train_grad over one flat parameter buffer and one frozen table: __call__(users, items, labels) writes `grads` whole and
+    returns (loss [1], logits [n]) as device tensors.  Two launches; nothing is copied to the host, nothing waits.  `params` and `grads` are
+    fp32 device tensors of head_layout's parameter count; the workspace grows to the largest n seen (never inside a capture: call
+    reserve(n) first)."""
+
+    def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads):
+        import torch
+        from . import _lib
+        self.lib = _lib.hip()
+        self.layout, self.count = head_layout(factor_num, num_layers, kind, user_num, int(table.shape[0]) if table.dim() == 2 else 0)
+        self.d = factor_num << (num_layers - 1)
+        if not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != self.d or not table.is_contiguous():
+            raise ValueError(f"ncf_train: the item table {tuple(table.shape)} must be a contiguous fp32 device tensor [I, d = {self.d}]")
+        for name, t in (("params", params), ("grads", grads)):
+            if t.dtype != torch.float32 or t.device != table.device or tuple(t.shape) != (self.count,) or not t.is_contiguous():
+                raise ValueError(f"ncf_train: {name} must be a contiguous fp32 tensor [{self.count}] on the table's device")
+        self.table, self.params, self.grads = table, params, grads
+        self.shape = (factor_num, num_layers, _lib.NCF_KINDS.index(kind))
+        self.user_num, self.item_num = int(user_num), int(table.shape[0])
+        h = NcfTrainC()
+        h.factor_num, h.num_layers, h.kind = self.shape
+        h.user_num, h.item_num = self.user_num, self.item_num
+        h.table, h.params, h.grads = table.data_ptr(), params.data_ptr(), grads.data_ptr()
+        self._head = h
+        offs = (C.c_int64 * NCF_TRAIN_TENSORS)()
+        count = int(self.lib.pmgt_ncf_train_layout(*self.shape, self.user_num, self.item_num, offs))
+        if count != self.count or list(offs) != layout_slots(self.layout):
+            raise RuntimeError("ncf_train: the library's parameter layout differs from head_layout")
+        self._ws, self._ws_pairs = None, 0
+
+    def reserve(self, n: int) -> None:
+        import torch
+        if n <= self._ws_pairs:
+            return
+        nbytes = int(self.lib.pmgt_ncf_train_workspace_bytes(*self.shape, int(n)))
+        if nbytes < 0:
+            raise ValueError(f"ncf_train: n = {n} pairs outside [1, {NCF_TRAIN_MAX_PAIRS}]")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ncf_train: the workspace cannot grow inside a capture; call reserve(n) first")
+        self._ws, self._ws_pairs = torch.empty(nbytes, dtype=torch.uint8, device=self.table.device), int(n)
+
+    def __call__(self, users, items, labels, loss=None, logits=None):
+        import torch
+        from . import _lib
+        n = int(users.shape[0])
+        dev = self.table.device
+        for t, dt in ((users, torch.int64), (items, torch.int64), (labels, torch.float32)):
+            if t.dtype != dt or tuple(t.shape) != (n,) or t.device != dev or not t.is_contiguous():
+                raise ValueError("ncf_train: users, items (int64) and labels (fp32) must be contiguous [n] tensors on the table's device")
+        self.reserve(n)
+        loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
+        logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
+        _lib.check(self.lib.pmgt_ncf_train_grad(C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(),
+                                                logits.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()))
+        return loss, logits
+
+
+def head_state(model) -> dict:
+    """The head's entries of a PMGT_NCF's state_dict (what head_layout names)."""
+    return {k: v for k, v in model.state_dict().items() if k.startswith(HEAD_PREFIXES)}
+
+
+class NcfHeadTrainer:
+    """AdamW on the head of `model` (a PMGT_NCF) over the frozen item table `table` [item_num, d] (encode_catalogue's, or exported
+    embeddings uploaded), all on the device.  The head's parameters move into ONE flat fp32 buffer and the model's nn.Parameters are
+    re-pointed at views of it, so model.head, state_dict, recommend and evaluate_ranking see the trained weights with no copy.  The trainer
+    owns the gradient buffer, exp_avg, exp_avg_sq and the device step counter; weights and embeddings decay, biases do not
+    (pmgt/base_trainer.py get_optimizer).  max_grad_norm None or 0: no clipping."""
+
+    def __init__(self, model, table, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = None):
+        import torch
+        import torch.nn as nn
+        if model.emb_dropout.p != 0 or any(layer.dropout.p != 0 for layer in model.mlp_layers):
+            raise ValueError("ncf_train: dropout in the head is not covered (emb_dropout and every layer's dropout must be 0)")
+        check_head_covered(model.factor_num, model.num_layers, model.model)
+        dev = model.mlp_user_embeddings.weight.device
+        d = model.factor_num << (model.num_layers - 1)
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (model.item_num, d) or table.device != dev:
+            raise ValueError(f"ncf_train: the item table must be an fp32 tensor [{model.item_num}, {d}] on {dev}")
+        self.model, self.table = model, table.detach().contiguous()
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = float(max_grad_norm or 0.0)
+        self.layout, self.count = head_layout(model.factor_num, model.num_layers, model.model, model.user_num, model.item_num)
+        self.params = torch.empty(self.count, dtype=torch.float32, device=dev)
+        self.grads = torch.zeros_like(self.params)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.decay = torch.zeros(self.count, dtype=torch.uint8, device=dev)
+        self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
+        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
+        named = dict(model.named_parameters())
+        with torch.no_grad():
+            for key, (off, shape) in self.layout.items():
+                view = self.params[off: off + int(np.prod(shape))].view(shape)
+                view.copy_(named[key].detach())
+                mod = model.get_submodule(key.rsplit(".", 1)[0])
+                setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
+                if not key.endswith(".bias"):
+                    self.decay[off: off + int(np.prod(shape))] = 1
+        self.grad_fn = NcfHeadGrad(model.factor_num, model.num_layers, model.model, model.user_num, self.table, self.params, self.grads)
+        self._graph = self._static = None
+
+    def views(self, flat) -> dict:
+        """{state_dict key: view of `flat`} for a buffer of the layout (params, grads, exp_avg, ...)."""
+        return {k: flat[off: off + int(np.prod(shape))].view(shape) for k, (off, shape) in self.layout.items()}
+
+    def step(self, users, items, labels, loss=None):
+        """One optimizer step on the pairs (device tensors: int64 [n], int64 [n], fp32 [n]; ids inside the tables, check_pairs checks them on
+        the host) -> the loss before the step as a device tensor [1].  Five launches enqueued; no host copy, no synchronisation."""
+        from . import _lib
+        loss, _ = self.grad_fn(users, items, labels, loss=loss, logits=self._logits(int(users.shape[0])))
+        _lib.check(self.grad_fn.lib.pmgt_op_adamw(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                  self.exp_avg_sq.data_ptr(), self.decay.data_ptr(), self.count, self.lr, self.weight_decay,
+                                                  self.betas[0], self.betas[1], self.eps, self.max_grad_norm, self.step_count.data_ptr(),
+                                                  self._scal.data_ptr(), self._part.data_ptr(), _stream()))
+        return loss
+
+    def _logits(self, n: int):
+        import torch
+        if getattr(self, "_logit_buf", None) is None or self._logit_buf.numel() < n:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ncf_train: buffers cannot grow inside a capture")
+            self._logit_buf = torch.empty(n, dtype=torch.float32, device=self.params.device)
+        return self._logit_buf[:n]
+
+    def capture(self, n: int):
+        """Captures step() on `n` pairs into a graph over static input buffers -> (users, items, labels, loss): write a batch into the first
+        three, replay(), read the last.  One stream.  Every buffer is created before the capture, and one warm-up step runs eagerly on the
+        zeroed static batch (the kernels are loaded outside the capture) with the parameters, the moments and the step counter put back
+        afterwards: capturing leaves the trainer's state as it was."""
+        import torch
+        if not 1 <= int(n) <= NCF_TRAIN_MAX_PAIRS:
+            raise ValueError(f"ncf_train: n = {n} pairs outside [1, {NCF_TRAIN_MAX_PAIRS}]")
+        dev = self.params.device
+        self._static = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                        torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        self.grad_fn.reserve(n)
+        self._logits(n)
+        saved = self.state_dict()
+        self.step(*self._static[:3], loss=self._static[3])
+        self.load_state_dict(saved)
+        torch.cuda.synchronize(dev)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.step(*self._static[:3], loss=self._static[3])
+        return self._static
+
+    def replay(self):
+        if self._graph is None:
+            raise RuntimeError("ncf_train: capture(n) comes before replay()")
+        self._graph.replay()
+        return self._static[3]
+
+    def state_dict(self) -> dict:
+        return {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+                "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        import torch
+        if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
+            raise ValueError("ncf_train: the state was saved for another head (the layouts differ)")
+        with torch.no_grad():
+            self.params.copy_(sd["params"])
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+            self.step_count.copy_(sd["step"])
+
+
+def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, num_ng: int = 1, seed: int = 0, early_criterion: str = "n20",
+            patience: int = 10, ckpt_dir: str = None, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
+            max_grad_norm: float = 5.0, batch_users: int = 256, log=None):
+    """Trains the head of `model` on the interaction list `train_pairs` [(user, item)] over the frozen `table`, the reference's downstream
+    fit: every epoch draws ng_sample(seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's users, items and
+    labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device and are read once
+    per epoch.  Validation ranks `valid` = (users [U], candidates [U, C], labels [U, C], counts [U]) (datasets.ranking_candidates) with
+    rank_users + RankingMetrics -> n10, n20, r10, r20, loss; early_criterion: "n20", "r20" or "loss" (EarlyStopping / BestCheckpoint of
+    fit_loop.py).  The best epoch's head is restored into the model at the end (and kept as a file in ckpt_dir when given).
+    -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
+    import torch
+    from .evaluation import rank_users
+    from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, monitor_of
+    from .metrics import RankingMetrics
+    if early_criterion not in ("n20", "r20", "loss"):
+        raise ValueError(f"early_criterion={early_criterion!r}: expected 'n20', 'r20' or 'loss'")
+    if not 1 <= int(batch_size) <= NCF_TRAIN_MAX_PAIRS or max_epochs < 1:
+        raise ValueError(f"fit_ncf: batch_size = {batch_size} outside [1, {NCF_TRAIN_MAX_PAIRS}] or max_epochs = {max_epochs} below 1")
+    pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
+    check_pairs(pairs[:, 0], pairs[:, 1], np.ones(len(pairs), np.float32), model.user_num, model.item_num, max_pairs=1 << 40)
+    v_users, v_cand = np.ascontiguousarray(valid[0], dtype=np.int64), np.ascontiguousarray(valid[1], dtype=np.int64)
+    v_labels, v_counts = np.ascontiguousarray(valid[2], dtype=np.float32), np.ascontiguousarray(valid[3], dtype=np.int32)
+    n_valid, width = v_cand.shape
+    if v_users.shape != (n_valid,) or v_labels.shape != (n_valid, width) or v_counts.shape != (n_valid,) or n_valid < 1:
+        raise ValueError("fit_ncf: valid must be (users [U], candidates [U, C], labels [U, C], counts [U])")
+    if v_users.min() < 0 or v_users.max() >= model.user_num or v_cand.min() < 0 or v_cand.max() >= model.item_num:
+        raise ValueError("fit_ncf: validation users or candidates outside the model's tables")
+    trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
+    dev = trainer.params.device
+    on_dev = [torch.from_numpy(a).to(dev) for a in (v_users, v_cand, v_labels, v_counts)]
+    metrics = RankingMetrics(dev, n_valid, (10, 20))
+    monitor, mode = monitor_of(early_criterion)
+    stopper = EarlyStopping(monitor, patience, mode)
+    keeper = BestCheckpoint(ckpt_dir or "", monitor, mode)
+    if ckpt_dir:
+        os.makedirs(ckpt_dir, exist_ok=True)
+    best_params, history = None, []
+    was_training = model.training
+    model.eval()
+    try:
+        for epoch in range(int(max_epochs)):
+            users, items, labels = ng_sample(pairs, model.user_num, model.item_num, num_ng, seed + epoch)
+            order = epoch_order(len(users), seed, epoch)
+            users_d, items_d, labels_d = (torch.from_numpy(np.ascontiguousarray(a[order])).to(dev) for a in (users, items, labels))
+            n_steps = (len(order) + batch_size - 1) // batch_size
+            losses = torch.empty(n_steps, 1, dtype=torch.float32, device=dev)
+            for s in range(n_steps):
+                lo, hi = s * batch_size, min((s + 1) * batch_size, len(order))
+                trainer.step(users_d[lo:hi], items_d[lo:hi], labels_d[lo:hi], loss=losses[s])
+            metrics.reset()
+            rank_users(model, trainer.table, *on_dev, sink=metrics.update, batch_users=batch_users)
+            st = metrics.statistic()                             # (reads the device: the epoch's one wait)
+            if st["n_unwritten"] or st["n_nan"]:
+                raise ValueError(f"fit_ncf: epoch {epoch}: {st['n_nan']} validation users have a NaN logit")
+            # a user without a positive candidate counts 0 towards nDCG and recall here (result() would refuse them)
+            row = {"epoch": epoch, "train_loss": float(losses.double().mean().item())}
+            row.update({f"n{k}": st["ndcg"][k] / st["n_users"] for k in (10, 20)})
+            row.update({f"r{k}": st["recall"][k] / st["n_users"] for k in (10, 20)})
+            row["loss"] = st["loss"] / st["n_users"]
+            write, remove = keeper.update(epoch, row[early_criterion])
+            row["best"] = write is not None
+            if write is not None:
+                best_params = trainer.params.detach().clone()
+                if ckpt_dir:
+                    torch.save({"epoch": epoch, "head": {k: v.detach().cpu() for k, v in head_state(model).items()}, "metrics": dict(row)}, write)
+                    if remove and os.path.exists(remove):
+                        os.remove(remove)
+            history.append(row)
+            if log is not None:
+                log(row)
+            if stopper.update(row[early_criterion], epoch):
+                break
+        if best_params is not None:
+            with torch.no_grad():
+                trainer.params.copy_(best_params)
+    finally:
+        model.train(was_training)
+    return history

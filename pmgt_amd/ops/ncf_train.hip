@@ -1,0 +1,545 @@
+// Training of the head of PMGT_NCF over a FROZEN item table (pmgt_ncf_train_grad of include/pmgt_capi.h; the head: pmgt/pmgt_ncf/models.py:91-105,
+// the step it serves: pmgt/ncf/trainer.py:183-200): loss, logits and the gradient of the mean BCE-with-logits loss with respect to every
+// parameter of the head, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for ncf_score.hip's reason: the measured step
+// launches nothing of this.  fp32 end to end; every matrix product runs on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32).
+//
+// EVERYTHING IS PAIR-MAJOR.  Activations act_l [n][out_l], pre-activation gradients dz_l [n][out_l] and the per-pair embedding gradients sit in
+// the caller's workspace as plain row-major matrices, one row per pair.  The three products are then
+//   forward   Y^T [out, pair] = W [out, in] X^T          A = W[m][k]: 16 contiguous k per lane (4 x 16-byte loads), B = X[pair][k]: the same
+//   data      dX^T [in, pair] = W^T [in, out] dZ^T       A = W[k][m]: one coalesced row segment per k-step,          B = dZ[pair][k]: 16 per lane
+//   weight    dW [out, in]    = dZ^T [out, pair] X       A = dZ[pair][m], B = X[pair][c]: both one coalesced row segment per k-step
+// with the PAIR on the lane in the first two (result register g of lane half h = feature rho(g) + 4 h, so a lane stores four 16-byte pieces
+// of its pair's row) and the pairs as the contraction index of the third.  A 32-wide chunk of k is split 16 | 16 between the lane halves:
+// k-step s multiplies k0 + s (half 0) and k0 + 16 + s (half 1).  Widths below 32 are zero-padded by the guards of the loads.
+//
+// LAUNCH 1, ncf_train_pairs_kernel, three roles by block index:
+//   tile   32 pairs a workgroup of 4 waves (the waves share out the 32-feature blocks of a layer): gathers [U_mlp[u] ; table[i]] on the fly,
+//          runs the layers, the GMF product and the predict layer, the stable loss max(z, 0) - z y + log1p(exp(-|z|)) and
+//          dlogit = (sigmoid(z) - y) / n, then walks back: dz_l = (W_(l+1)^T dz_(l+1)) * (act_l > 0) down to the user half of layer 0's input.
+//          Between layers the rows go through the workspace; a workgroup reads only what it wrote itself, behind a barrier.
+//   rank   the position of every pair in the STABLE order by user id (and, NeuMF-end, by item id): rank = the number of pairs with a smaller
+//          (id, pair index); counted, not sorted: n <= 65 536 and the ids of a block of 256 pairs go through LDS once per 256 ranks.
+//   zero   the gradient rows of the embedding tables, whole (the optimizer is dense).
+// LAUNCH 2, ncf_train_grads_kernel, two roles:
+//   weight one workgroup per 32 x 32 block of a layer's dW; its 4 waves take the 32-pair chunks c = w, w + 4, ... IN ORDER and the four
+//          accumulators are added as (w0 + w1) + (w2 + w3).  A layer has one more block column whose B operand is the constant column
+//          (1, 0, ..., 0): its column 0 is the bias gradient.  The predict layer is the pseudo-layer with dz = [dlogit, loss_pair]: row 0 gives
+//          d predict_layer.weight and .bias, row 1 of the constant column the loss sum.
+//   rows   one wave per position of the stable order; the wave at the start of a run of equal ids adds the run's per-pair rows in pair order
+//          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.
+// DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+#include "../csrc/common.h"
+#include "../../include/pmgt_capi.h"
+
+namespace pmgt {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+static constexpr int NT_THREADS = 256, NT_WAVES = 4, NT_TILE = 32, NT_MAX_LAYERS = PMGT_NCF_MAX_LAYERS, NT_MAX_D = 256;
+static constexpr int NT_ZERO_BLOCKS = 1024, NT_MAX_TASKS = NT_MAX_LAYERS + 1;
+
+struct NtLayer {
+    const float* w;      // [out][2 out]
+    const float* b;      // [out]
+    float* act;          // workspace [n][out]: relu(W x + b)
+    float* dz;           // workspace [n][out]: d loss / d (W x + b)
+    int out;
+};
+
+struct NtPairsArgs {
+    NtLayer layer[NT_MAX_LAYERS];
+    const float *u_mlp, *table, *gu, *gi, *wp, *bp;
+    const int64_t *users, *items;
+    const float* labels;
+    float *du, *gprod, *ggu, *ggi, *pz;      // workspace: [n][d], [n][F] x 3, [n][2] = (dlogit, loss of the pair)
+    int *order_u, *order_i;                  // workspace: the pairs in stable order by user / item id
+    float* logits;                           // [n] or NULL
+    float* zero_base;                        // the embedding gradients
+    int64_t zero_vec4;                       // ... in 16-byte pieces
+    int n, d, factor, num_layers, neumf, tiles, rank_blocks, zero_blocks;
+};
+
+// a matrix [n][w1 + w2] given by one or two row sources, each read by the pair index itself (idx NULL) or through an id list
+struct NtSrc {
+    const float* p1;
+    const int64_t* idx1;
+    int w1;
+    const float* p2;
+    const int64_t* idx2;
+    int w2;
+};
+
+struct NtTask {
+    const float* a;      // dz [n][m]
+    NtSrc b;             // the layer's input [n][k]
+    float* gw;           // [m][k]
+    float* gb;           // [m]
+    int m, col_blocks, first, predict;      // col_blocks counts the constant column's block
+};
+
+struct NtGradsArgs {
+    NtTask task[NT_MAX_TASKS];
+    const int64_t *users, *items;
+    const int *order_u, *order_i;
+    const float *du, *ggu, *ggi;
+    float *g_u_mlp, *g_gu, *g_gi, *loss;
+    int n, d, factor, neumf, ntasks, weight_blocks, row_blocks;      // row_blocks per kind (user, item)
+};
+
+__device__ __forceinline__ int rho(int g) { return (g & 3) + 8 * (g >> 2); }
+__device__ __forceinline__ float4 ld4(const float* p, bool ok) {
+    return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }      // provably uniform
+
+// act[pair][0 .. M) = relu(W [M][K] x + bias); x = [r1[0 .. w1) ; r2[0 .. K - w1)], the lane's own pair row(s)
+__device__ __forceinline__ void forward_layer(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* r1, int w1,
+                                              const float* r2, bool valid, float* act_row, int wave, int lane) {
+    const int p = lane & 31, h = lane >> 5;
+    for (int mb = wave; mb * 32 < M; mb += NT_WAVES) {
+        f32x16 acc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int f = mb * 32 + rho(g) + 4 * h;
+            acc[g] = f < M ? bias[f] : 0.f;
+        }
+        const int m = mb * 32 + p;
+        const float* wrow = W + (int64_t)m * K;
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            float4 a[4], x[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = k0 + 16 * h + 4 * j;
+                a[j] = ld4(wrow + k, m < M && k < K);
+                x[j] = ld4(k < w1 ? r1 + k : r2 + (k - w1), valid && k < K);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(elem(a[j], e), elem(x[j], e), acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int f = mb * 32 + 8 * q + 4 * h;
+            float4 v;
+            v.x = acc[4 * q] < 0.f ? 0.f : acc[4 * q];      // (keeps a NaN, as ncf_score.hip does)
+            v.y = acc[4 * q + 1] < 0.f ? 0.f : acc[4 * q + 1];
+            v.z = acc[4 * q + 2] < 0.f ? 0.f : acc[4 * q + 2];
+            v.w = acc[4 * q + 3] < 0.f ? 0.f : acc[4 * q + 3];
+            if (valid && f < M) *reinterpret_cast<float4*>(act_row + f) = v;
+        }
+    }
+}
+
+// dx[pair][c] = sum_o W[o][c] dz[pair][o] for c in [0, C), W [M][K] with C <= K; times (mask_row[c] > 0) when mask_row
+__device__ __forceinline__ void backward_layer(const float* __restrict__ W, int M, int K, int C, const float* dz_row, const float* mask_row,
+                                               bool valid, float* dx_row, int wave, int lane) {
+    const int p = lane & 31, h = lane >> 5;
+    for (int cb = wave; cb * 32 < C; cb += NT_WAVES) {
+        f32x16 acc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+        const int c = cb * 32 + p;
+        for (int o0 = 0; o0 < M; o0 += 32) {
+            float4 z[4];
+            float a[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = ld4(dz_row + o0 + 16 * h + 4 * j, valid && o0 + 16 * h + 4 * j < M);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                const int o = o0 + 16 * h + s;
+                a[s] = (c < C && o < M) ? W[(int64_t)o * K + c] : 0.f;
+            }
+#pragma unroll
+            for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], elem(z[s >> 2], s & 3), acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int f = cb * 32 + 8 * q + 4 * h;
+            const bool ok = valid && f < C;
+            float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+            if (mask_row) {
+                const float4 hm = ld4(mask_row + f, ok);
+                v.x = hm.x > 0.f ? v.x : 0.f;
+                v.y = hm.y > 0.f ? v.y : 0.f;
+                v.z = hm.z > 0.f ? v.z : 0.f;
+                v.w = hm.w > 0.f ? v.w : 0.f;
+            }
+            if (ok) *reinterpret_cast<float4*>(dx_row + f) = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a) {
+    __shared__ float s_dl[NT_TILE];
+    __shared__ int64_t s_ids[NT_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
+    int bid = blockIdx.x;
+    if (bid >= a.tiles + 2 * a.rank_blocks) {                // ---- zero: the embedding gradients, whole
+        float4* z = reinterpret_cast<float4*>(a.zero_base);
+        for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * NT_THREADS + tid; i < a.zero_vec4; i += (int64_t)a.zero_blocks * NT_THREADS)
+            z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    if (bid >= a.tiles) {                                    // ---- rank: the stable order by id, counted
+        bid -= a.tiles;
+        const int kind = bid / a.rank_blocks;
+        const int64_t* ids = kind ? a.items : a.users;
+        int* order = kind ? a.order_i : a.order_u;
+        const int p = (bid - kind * a.rank_blocks) * NT_THREADS + tid;
+        const int64_t mine = p < n ? ids[p] : 0;
+        int rank = 0;
+        for (int q0 = 0; q0 < n; q0 += NT_THREADS) {
+            __syncthreads();
+            s_ids[tid] = q0 + tid < n ? ids[q0 + tid] : 0;
+            __syncthreads();
+            const int cnt = min(NT_THREADS, n - q0);
+            for (int j = 0; j < cnt; ++j) {
+                const int64_t v = s_ids[j];
+                rank += (v < mine || (v == mine && q0 + j < p)) ? 1 : 0;
+            }
+        }
+        if (p < n) order[rank] = p;
+        return;
+    }
+    // ---- tile: forward and data gradient of 32 pairs
+    const int d = a.d, F = a.factor, L = a.num_layers;
+    const int pl = lane & 31, h = lane >> 5;
+    const int pair = bid * NT_TILE + pl;
+    const bool valid = pair < n;
+    const int64_t uid = valid ? a.users[pair] : 0, iid = valid ? a.items[pair] : 0;
+    const float* urow = a.u_mlp + uid * d;
+    const float* irow = a.table + iid * d;
+    forward_layer(a.layer[0].w, a.layer[0].b, d, 2 * d, urow, d, irow, valid, a.layer[0].act + (int64_t)pair * d, wave, lane);
+    __syncthreads();
+    for (int l = 1; l < L; ++l) {
+        const int M = a.layer[l].out;
+        forward_layer(a.layer[l].w, a.layer[l].b, M, 2 * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, 2 * M, nullptr, valid,
+                      a.layer[l].act + (int64_t)pair * M, wave, lane);
+        __syncthreads();
+    }
+    const float* feat = a.layer[L - 1].act;                  // [n][F]
+    const float* wp_mlp = a.wp + (a.neumf ? F : 0);
+    if (wave == 0) {                                         // predict layer, loss, dlogit: a pair on lanes p and p + 32, half the factors each
+        float s = 0.f;
+        if (valid) {
+            const int half = F >> 1;
+            if (a.neumf) {
+                const float* gu = a.gu + uid * F;
+                const float* gi = a.gi + iid * F;
+                for (int f = h * half; f < (h + 1) * half; ++f) {
+                    const float g = gu[f] * gi[f];
+                    a.gprod[(int64_t)pair * F + f] = g;
+                    s = fmaf(a.wp[f], g, s);
+                }
+            }
+            const float* hl = feat + (int64_t)pair * F;
+            for (int f = h * half; f < (h + 1) * half; ++f) s = fmaf(wp_mlp[f], hl[f], s);
+        }
+        s += __shfl_xor(s, 32, 64);
+        if (h == 0) {
+            float dl = 0.f;
+            if (valid) {
+                const float z = s + a.bp[0], y = a.labels[pair];
+                const float e = expf(-fabsf(z));
+                const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                dl = (sig - y) / (float)n;
+                if (a.logits) a.logits[pair] = z;
+                a.pz[(int64_t)pair * 2] = dl;
+                a.pz[(int64_t)pair * 2 + 1] = fmaxf(z, 0.f) - z * y + log1pf(e);
+            }
+            s_dl[pl] = dl;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < NT_TILE * F; e += NT_THREADS) {    // dz of the last layer and the per-pair GMF gradients
+        const int pp = e / F, f = e - pp * F, pr = bid * NT_TILE + pp;
+        if (pr >= n) continue;
+        const float dl = s_dl[pp];
+        const int64_t at = (int64_t)pr * F + f;
+        a.layer[L - 1].dz[at] = feat[at] > 0.f ? dl * wp_mlp[f] : 0.f;
+        if (a.neumf) {
+            const float dg = dl * a.wp[f];
+            a.ggu[at] = dg * a.gi[a.items[pr] * F + f];
+            a.ggi[at] = dg * a.gu[a.users[pr] * F + f];
+        }
+    }
+    __syncthreads();
+    for (int l = L - 1; l >= 1; --l) {
+        const int M = a.layer[l].out;
+        backward_layer(a.layer[l].w, M, 2 * M, 2 * M, a.layer[l].dz + (int64_t)pair * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, valid,
+                       a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane);
+        __syncthreads();
+    }
+    backward_layer(a.layer[0].w, d, 2 * d, d, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.du + (int64_t)pair * d, wave, lane);
+}
+
+__device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
+    if (c < s.w1) {
+        const int64_t row = s.idx1 ? s.idx1[pair] : pair;
+        return s.p1[row * s.w1 + c];
+    }
+    const int64_t row = s.idx2 ? s.idx2[pair] : pair;
+    return s.p2[row * s.w2 + (c - s.w1)];
+}
+
+__global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs a) {
+    __shared__ float s_acc[NT_WAVES][16][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
+    int bid = blockIdx.x;
+    if (bid >= a.weight_blocks) {                            // ---- rows: segment sums of the per-pair embedding gradients in pair order
+        bid -= a.weight_blocks;
+        const int kind = bid / a.row_blocks;
+        const int s = (bid - kind * a.row_blocks) * NT_WAVES + wave;
+        if (s >= n) return;
+        const int64_t* ids = kind ? a.items : a.users;
+        const int* order = kind ? a.order_i : a.order_u;
+        const int64_t id = ids[order[s]];
+        if (s > 0 && ids[order[s - 1]] == id) return;        // (uniform per wave) not the start of a run
+        const int d = a.d, F = a.factor;
+        const int width = kind ? F : d + (a.neumf ? F : 0);
+        for (int c = lane; c < width; c += 64) {
+            const float* src;
+            float* dst;
+            int w, cc;
+            if (kind) { src = a.ggi; dst = a.g_gi; w = F; cc = c; }
+            else if (c < d) { src = a.du; dst = a.g_u_mlp; w = d; cc = c; }
+            else { src = a.ggu; dst = a.g_gu; w = F; cc = c - d; }
+            float sum = 0.f;
+            for (int t = s; t < n; ++t) {
+                const int pr = order[t];
+                if (ids[pr] != id) break;
+                sum += src[(int64_t)pr * w + cc];
+            }
+            dst[id * w + cc] = sum;
+        }
+        return;
+    }
+    // ---- weight: one 32 x 32 block of dW = dz^T x, the pairs in order
+    int ti = 0;
+    for (int i = 1; i < a.ntasks; ++i)
+        if (bid >= a.task[i].first) ti = i;
+    const NtTask& t = a.task[ti];
+    const int local = bid - t.first, M = t.m, K = t.b.w1 + t.b.w2;
+    const int mb = local / t.col_blocks, nb = local - mb * t.col_blocks;
+    const bool ones = nb == t.col_blocks - 1;
+    const int p = lane & 31, h = lane >> 5, m = mb * 32 + p, c = nb * 32 + p;
+    f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+    for (int ch = wave; ch * 32 < n; ch += NT_WAVES) {
+        float av[16], bv[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int pair = ch * 32 + 16 * h + s;
+            const bool ok = pair < n;
+            av[s] = (ok && m < M) ? t.a[(int64_t)pair * M + m] : 0.f;
+            bv[s] = ones ? (p == 0 ? 1.f : 0.f) : ((ok && c < K) ? src_at(t.b, pair, c) : 0.f);
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g) s_acc[wave][g][lane] = acc[g];
+    __syncthreads();
+    const int gq = tid >> 6;
+#pragma unroll
+    for (int gg = 0; gg < 4; ++gg) {
+        const int g = gq * 4 + gg;
+        const float v = (s_acc[0][g][lane] + s_acc[1][g][lane]) + (s_acc[2][g][lane] + s_acc[3][g][lane]);
+        const int mo = mb * 32 + rho(g) + 4 * h;
+        if (t.predict) {
+            if (mo == 0) {
+                if (ones) { if (p == 0) t.gb[0] = v; }
+                else if (c < K) t.gw[c] = v;
+            } else if (mo == 1 && ones && p == 0) {
+                a.loss[0] = v / (float)n;
+            }
+        } else if (mo < M) {
+            if (ones) { if (p == 0) t.gb[mo] = v; }
+            else if (c < K) t.gw[(int64_t)mo * K + c] = v;
+        }
+    }
+}
+
+struct NtShape {
+    int F, L, d, neumf;
+    int64_t user_num, item_num;
+};
+
+static int nt_shape(int factor_num, int num_layers, int kind, int64_t user_num, int64_t item_num, const char* who, NtShape* s) {
+    PMGT_CHECK(factor_num == 8 || factor_num == 16 || factor_num == 32 || factor_num == 64, -2, "%s: factor_num = %d, covered: 8, 16, 32, 64", who,
+               factor_num);
+    PMGT_CHECK(num_layers >= 1 && num_layers <= NT_MAX_LAYERS, -2, "%s: num_layers = %d outside [1, %d]", who, num_layers, NT_MAX_LAYERS);
+    const int d = factor_num << (num_layers - 1);
+    PMGT_CHECK(d <= NT_MAX_D, -2, "%s: d = factor_num * 2^(num_layers - 1) = %d above %d", who, d, NT_MAX_D);
+    PMGT_CHECK(kind == PMGT_NCF_MLP || kind == PMGT_NCF_NEUMF_END, -2, "%s: unknown model kind %d", who, kind);
+    PMGT_CHECK(user_num >= 1 && user_num <= 0x7FFFFFFELL, -2, "%s: user_num = %lld outside [1, 2^31 - 2]", who, (long long)user_num);
+    PMGT_CHECK(item_num >= 1 && item_num <= 0x7FFFFFFELL, -2, "%s: item_num = %lld outside [1, 2^31 - 2]", who, (long long)item_num);
+    *s = NtShape{factor_num, num_layers, d, kind == PMGT_NCF_NEUMF_END, user_num, item_num};
+    return 0;
+}
+
+// the flat parameter layout: off[PMGT_NCF_TRAIN_TENSORS] in floats (-1 = the head has no such tensor) -> the parameter count
+static int64_t nt_layout(const NtShape& s, int64_t* off) {
+    int64_t at = 0;
+    for (int i = 0; i < PMGT_NCF_TRAIN_TENSORS; ++i) off[i] = -1;
+    off[0] = at, at += s.user_num * s.d;
+    if (s.neumf) {
+        off[1] = at, at += s.user_num * s.F;
+        off[2] = at, at += s.item_num * s.F;
+    }
+    for (int l = 0; l < s.L; ++l) {
+        const int64_t out = s.d >> l;
+        off[3 + 2 * l] = at, at += out * 2 * out;
+        off[4 + 2 * l] = at, at += out;
+    }
+    off[3 + 2 * NT_MAX_LAYERS] = at, at += s.neumf ? 2 * s.F : s.F;
+    off[4 + 2 * NT_MAX_LAYERS] = at, at += 1;
+    return at;
+}
+
+// the workspace in floats: act_l and dz_l [n][d >> l], du [n][d], gprod / ggu / ggi [n][F], pz [n][2], then the two orders (int [n] each)
+static int64_t nt_workspace_floats(const NtShape& s, int64_t n) {
+    int64_t w = 0;
+    for (int l = 0; l < s.L; ++l) w += 2 * n * (s.d >> l);
+    w += n * s.d + 3 * n * s.F;
+    w += (2 * n + 3) / 4 * 4;
+    w += 2 * ((n + 3) / 4 * 4);
+    return w;
+}
+
+}  // namespace pmgt
+
+using namespace pmgt;
+
+extern "C" {
+
+int64_t pmgt_ncf_train_layout(int factor_num, int num_layers, int kind, int64_t user_num, int64_t item_num, int64_t* offsets) {
+    NtShape s;
+    if (int rc = nt_shape(factor_num, num_layers, kind, user_num, item_num, "pmgt_ncf_train_layout", &s)) return rc;
+    int64_t off[PMGT_NCF_TRAIN_TENSORS];
+    const int64_t count = nt_layout(s, off);
+    if (offsets)
+        for (int i = 0; i < PMGT_NCF_TRAIN_TENSORS; ++i) offsets[i] = off[i];
+    return count;
+}
+
+int64_t pmgt_ncf_train_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n) {
+    NtShape s;
+    if (int rc = nt_shape(factor_num, num_layers, kind, 1, 1, "pmgt_ncf_train_workspace_bytes", &s)) return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "pmgt_ncf_train_workspace_bytes: n = %lld pairs outside [1, %d]", (long long)n,
+               PMGT_NCF_TRAIN_MAX_PAIRS);
+    return nt_workspace_floats(s, n) * (int64_t)sizeof(float);
+}
+
+int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                        float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+    PMGT_CHECK(head != nullptr, -2, "pmgt_ncf_train_grad: NULL head");
+    NtShape s;
+    if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, "pmgt_ncf_train_grad", &s)) return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "pmgt_ncf_train_grad: n = %lld pairs outside [1, %d]", (long long)n,
+               PMGT_NCF_TRAIN_MAX_PAIRS);
+    PMGT_CHECK(head->table && head->params && head->grads && users && items && labels && loss && workspace, -2, "pmgt_ncf_train_grad: NULL buffer");
+    PMGT_CHECK((((uintptr_t)head->table | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace) & 15) == 0, -2,
+               "pmgt_ncf_train_grad: the table, the parameters, the gradients and the workspace must be 16-byte aligned");
+    PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
+               "pmgt_ncf_train_grad: misaligned buffer");
+    const int64_t need = nt_workspace_floats(s, n) * (int64_t)sizeof(float);
+    PMGT_CHECK(workspace_bytes >= need, -2, "pmgt_ncf_train_grad: workspace of %lld bytes below the %lld needed", (long long)workspace_bytes,
+               (long long)need);
+    int64_t off[PMGT_NCF_TRAIN_TENSORS];
+    nt_layout(s, off);
+    const float* P = head->params;
+    float* G = head->grads;
+    float* ws = (float*)workspace;
+    const int F = s.F, L = s.L, d = s.d;
+    const int OFF_WP = 3 + 2 * NT_MAX_LAYERS, OFF_BP = 4 + 2 * NT_MAX_LAYERS;
+
+    NtPairsArgs pa = {};
+    NtGradsArgs ga = {};
+    for (int l = 0; l < L; ++l) {
+        const int out = d >> l;
+        pa.layer[l].w = P + off[3 + 2 * l];
+        pa.layer[l].b = P + off[4 + 2 * l];
+        pa.layer[l].out = out;
+        pa.layer[l].act = ws, ws += n * out;
+        pa.layer[l].dz = ws, ws += n * out;
+    }
+    pa.du = ws, ws += n * d;
+    pa.gprod = ws, ws += n * F;
+    pa.ggu = ws, ws += n * F;
+    pa.ggi = ws, ws += n * F;
+    pa.pz = ws, ws += (2 * n + 3) / 4 * 4;
+    pa.order_u = (int*)ws, ws += (n + 3) / 4 * 4;
+    pa.order_i = (int*)ws;
+    pa.u_mlp = P + off[0];
+    pa.table = head->table;
+    pa.gu = s.neumf ? P + off[1] : nullptr;
+    pa.gi = s.neumf ? P + off[2] : nullptr;
+    pa.wp = P + off[OFF_WP];
+    pa.bp = P + off[OFF_BP];
+    pa.users = users;
+    pa.items = items;
+    pa.labels = labels;
+    pa.logits = logits;
+    pa.zero_base = G;
+    pa.zero_vec4 = off[3] / 4;                               // the embedding tables come first; every size is a multiple of 8 floats
+    pa.n = (int)n, pa.d = d, pa.factor = F, pa.num_layers = L, pa.neumf = s.neumf;
+    pa.tiles = (int)cdiv64(n, NT_TILE);
+    pa.rank_blocks = (int)cdiv64(n, NT_THREADS);
+    pa.zero_blocks = (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(pa.zero_vec4, NT_THREADS));
+
+    int first = 0;
+    for (int l = 0; l < L; ++l) {
+        const int out = d >> l;
+        NtTask& t = ga.task[l];
+        t.a = pa.layer[l].dz;
+        t.m = out;
+        if (l == 0) t.b = NtSrc{pa.u_mlp, users, d, pa.table, items, d};
+        else t.b = NtSrc{pa.layer[l - 1].act, nullptr, 2 * out, nullptr, nullptr, 0};
+        t.gw = G + off[3 + 2 * l];
+        t.gb = G + off[4 + 2 * l];
+        t.col_blocks = (2 * out + 31) / 32 + 1;
+        t.first = first;
+        t.predict = 0;
+        first += (out + 31) / 32 * t.col_blocks;
+    }
+    {
+        NtTask& t = ga.task[L];
+        t.a = pa.pz;
+        t.m = 2;
+        if (s.neumf) t.b = NtSrc{pa.gprod, nullptr, F, pa.layer[L - 1].act, nullptr, F};
+        else t.b = NtSrc{pa.layer[L - 1].act, nullptr, F, nullptr, nullptr, 0};
+        t.gw = G + off[OFF_WP];
+        t.gb = G + off[OFF_BP];
+        t.col_blocks = ((s.neumf ? 2 * F : F) + 31) / 32 + 1;
+        t.first = first;
+        t.predict = 1;
+        first += t.col_blocks;
+    }
+    ga.ntasks = L + 1;
+    ga.weight_blocks = first;
+    ga.row_blocks = (int)cdiv64(n, NT_WAVES);
+    ga.users = users, ga.items = items;
+    ga.order_u = pa.order_u, ga.order_i = pa.order_i;
+    ga.du = pa.du, ga.ggu = pa.ggu, ga.ggi = pa.ggi;
+    ga.g_u_mlp = G + off[0];
+    ga.g_gu = s.neumf ? G + off[1] : nullptr;
+    ga.g_gi = s.neumf ? G + off[2] : nullptr;
+    ga.loss = loss;
+    ga.n = (int)n, ga.d = d, ga.factor = F, ga.neumf = s.neumf;
+
+    hipStream_t st = (hipStream_t)stream;
+    const int kinds = s.neumf ? 2 : 1;                       // MLP has no table indexed by item: its item order is computed and not read
+    const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
+    hipLaunchKernelGGL(ncf_train_pairs_kernel, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
+    PMGT_LAUNCH_OK();
+    const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks);
+    hipLaunchKernelGGL(ncf_train_grads_kernel, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
+    PMGT_LAUNCH_OK();
+    return 0;
+}
+
+}  // extern "C"
