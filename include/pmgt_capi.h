@@ -389,7 +389,7 @@ typedef struct pmgt_ncf_train {
     int kind;                                     /* PMGT_NCF_* */
     int reserved;
     int64_t user_num, item_num;                   /* rows of the user tables; rows of `table` and of gmf_item */
-    const float* table;                           /* frozen item embeddings [item_num][d] */
+    const float* table;                           /* item embeddings [item_num][d]; only read */
     const float* params;                          /* the flat parameters */
     float* grads;                                 /* the flat gradients, written whole */
 } pmgt_ncf_train;
@@ -397,6 +397,19 @@ int64_t pmgt_ncf_train_layout(int factor_num, int num_layers, int kind, int64_t 
 int64_t pmgt_ncf_train_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n);
 int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                         float* logits, void* workspace, int64_t workspace_bytes, void* stream);
+/* THE ITEM TABLE TRAINED WITH THE HEAD (pmgt/ncf/trainer.py:168-179: embed_item_MLP is initialised from the exported embeddings and keeps
+ * requires_grad unless --freeze-item-init-emb is passed; scripts/run_ncf.sh does not pass it).  pmgt_ncf_train_grad_table takes the
+ * arguments of pmgt_ncf_train_grad plus table_grad fp32 [item_num][d], 16-byte aligned; it does all that entry does -- loss, logits and
+ * the head's gradients have the same bits -- and writes d loss / d table WHOLE: rows no pair touches hold +0.0, rows hit by several
+ * pairs are summed in pair order (the rule of gmf_item_embeddings, for both kinds: an MLP head has no GMF rows, only the table's).  The
+ * data gradient of layer 0 then covers all 2 d columns of W_0, one row [2 d] per pair in the workspace, which is larger by n d floats:
+ * pmgt_ncf_train_table_workspace_bytes.  Still two launches, no atomic, no sync, no allocation; `table` is only read, so `table` and
+ * table_grad may lie behind the head in the caller's flat parameter and gradient buffers (one optimizer call then steps both).  Refused
+ * (-2) before anything is launched: what pmgt_ncf_train_grad refuses, a NULL or misaligned table_grad, a workspace below that size.
+ * Added without a bump of pmgt_abi_version(): two entries, nothing existing moved. */
+int64_t pmgt_ncf_train_table_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n);
+int pmgt_ncf_train_grad_table(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                              float* loss, float* logits, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average

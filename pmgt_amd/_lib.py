@@ -116,6 +116,7 @@ HIP_SYMBOLS = [
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
+    "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -276,6 +277,9 @@ def hip():
     L.pmgt_ncf_train_workspace_bytes.restype = i64
     L.pmgt_ncf_train_workspace_bytes.argtypes = [i, i, i, i64]
     L.pmgt_ncf_train_grad.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]      # (head: byref of ncf_train.NcfTrainC)
+    L.pmgt_ncf_train_table_workspace_bytes.restype = i64
+    L.pmgt_ncf_train_table_workspace_bytes.argtypes = [i, i, i, i64]
+    L.pmgt_ncf_train_grad_table.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
     _hip = L
     return L
 

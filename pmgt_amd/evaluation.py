@@ -243,7 +243,7 @@ def rank_users(model, table: torch.Tensor, users: torch.Tensor, candidates: torc
 
 
 def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 20), batch_users: int = 256, metrics: str = "host",
-                     threads: int = 8, seed: int = 0, per_user: bool = False):
+                     threads: int = 8, seed: int = 0, per_user: bool = False, table=None):
     """Top-N recommendation quality of a PMGT_NCF (the reference's test_step / test_epoch_end, pmgt/ncf/trainer.py:202-254): the catalogue
     is encoded ONCE in eval mode (encode_catalogue), every user's candidates (pmgt_amd.datasets.ranking_candidates) are scored by the
     model's head on rows gathered from that table, and the scores are ranked per user -> {"n<k>", "r<k>" for k in ks, "loss"}: mean nDCG@k,
@@ -252,7 +252,9 @@ def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 
     metrics="device": they stay on the device (pmgt_amd.metrics.RankingMetrics, HIP); the loop copies nothing back and never waits, one
     small copy at the end fetches the sums.  Per-user nDCG, recall and n_pos are equal on both paths; the per-user loss may differ in its
     last bits (fp32 summation order) and the means by U * 2^-52 (summation order).
-    per_user=True: returns (result, per-user dict) -- ndcg[k], recall[k], loss, n_pos as numpy arrays."""
+    per_user=True: returns (result, per-user dict) -- ndcg[k], recall[k], loss, n_pos as numpy arrays.
+    table: a ready item table (fp32 [item_num, d] on the model's device: encode_catalogue's, or one trained with the head by
+    fit_ncf(train_table=True)) to score against instead of encoding the catalogue, as for recommend; `sampler` is then not used."""
     from .metrics import RankingMetrics, check_ks
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
@@ -272,10 +274,14 @@ def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 
     if counts.min() < 1 or counts.max() > Cn or Cn > 4096:
         raise ValueError(f"evaluate_ranking: counts must lie in [1, C = {Cn}] and C in [1, 4096]")
     dev = model.engine.device
+    if table is not None and (not isinstance(table, torch.Tensor) or tuple(table.shape) != (model.item_num, model.config.hidden_size)
+                              or table.dtype != torch.float32 or table.device != dev):
+        raise ValueError(f"evaluate_ranking: table must be an fp32 tensor [{model.item_num}, {model.config.hidden_size}] on {dev}")
     was_training = model.training
     model.eval()
     try:
-        table = encode_catalogue(model, sampler, threads=threads, seed=seed)
+        if table is None:
+            table = encode_catalogue(model, sampler, threads=threads, seed=seed)
         on_dev = [torch.from_numpy(a).to(dev) for a in (users, candidates, labels, counts)]
         if metrics == "device":
             rm = RankingMetrics(dev, U, ks)

@@ -1,11 +1,15 @@
-"""Training of the head of a PMGT_NCF over a FROZEN item table: the reference's downstream experiment (scripts/run_ncf.sh,
-pmgt/ncf/trainer.py:183-200 with --item-init-emb-path: the exported item embeddings as a frozen table, `num_ng` fresh negatives per positive
-every epoch, BCEWithLogitsLoss, gradient clipping, AdamW, validation on nDCG / recall with early stopping).
+"""Training of the head of a PMGT_NCF over an item table: the reference's downstream experiment (scripts/run_ncf.sh,
+pmgt/ncf/trainer.py:183-200 with --item-init-emb-path: the exported item embeddings as the table, `num_ng` fresh negatives per positive
+every epoch, BCEWithLogitsLoss, gradient clipping, AdamW, validation on nDCG / recall with early stopping).  The table is FROZEN by default
+(--freeze-item-init-emb); with train_table=True it is INITIALISED from the embeddings and TRAINED WITH THE HEAD, which is what run_ncf.sh and
+every config/hpo/train_ncf_*_params.json do (pmgt/ncf/trainer.py:168-179, "freeze_item_init_emb": false).
 
-  ncf_head_grad_host   loss, logits and the gradient of every head parameter in numpy: the yardstick of the kernels
+  ncf_head_grad_host   loss, logits and the gradient of every head parameter (and of the table) in numpy: the yardstick of the kernels
   ng_sample            the reference's training-mode negative sampling, the same stream of draws
-  NcfHeadTrainer       the head's parameters in one flat device buffer; step() = pmgt_ncf_train_grad (two launches) + pmgt_op_adamw (three)
-  fit_ncf              epochs of sampled pairs, ranking validation, early stopping, the best head restored
+  normalize_item_table row-wise L2 normalisation of the exported embeddings (--normalize-item-init-emb)
+  NcfHeadTrainer       the head's parameters (and the table) in one flat device buffer; step() = pmgt_ncf_train_grad or
+                       pmgt_ncf_train_grad_table (two launches) + pmgt_op_adamw (three)
+  fit_ncf              epochs of sampled pairs, ranking validation, early stopping, the best head (and table) restored
 
 The pure-numpy part needs no GPU."""
 import ctypes as C
@@ -44,6 +48,20 @@ def head_layout(factor_num: int, num_layers: int, kind: str, user_num: int, item
     return layout, at
 
 
+TABLE_KEY = "item_table"                         # the trained table's name in the layouts, the gradients and the checkpoints
+
+
+def table_layout(factor_num: int, num_layers: int, kind: str, user_num: int, item_num: int):
+    """The flat buffer of a trainer that trains the item table: head_layout followed by TABLE_KEY [item_num, d], its offset rounded up to a
+    multiple of 8 floats (the head ends with the one float of predict_layer.bias; the table's rows stay 32-byte aligned)
+    -> (layout, count of the whole buffer).  The pad floats between the head and the table belong to no named tensor."""
+    layout, count = head_layout(factor_num, num_layers, kind, user_num, item_num)
+    off = (count + 7) // 8 * 8
+    d = factor_num << (num_layers - 1)
+    layout[TABLE_KEY] = (off, (int(item_num), d))
+    return layout, off + int(item_num) * d
+
+
 def layout_slots(layout: dict):
     """The offsets of `layout` in the slot order of pmgt_ncf_train_layout (-1: the head has no such tensor)."""
     slots = ["mlp_user_embeddings.weight", "gmf_user_embeddings.weight", "gmf_item_embeddings.weight"]
@@ -68,11 +86,12 @@ def check_pairs(users, items, labels, user_num: int, item_num: int, max_pairs: i
     return users, items, labels
 
 
-def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64):
+def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False):
     """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
     `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
     model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
-    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order."""
+    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order.
+    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule."""
     w = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
     factor, num_layers, kind, d = head_shape(w)
     table = np.asarray(table).astype(dtype)
@@ -109,6 +128,9 @@ def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.floa
         dh = dz @ w[f"mlp_layers.{i}.linear.weight"]
     grads["mlp_user_embeddings.weight"] = np.zeros_like(w["mlp_user_embeddings.weight"])
     np.add.at(grads["mlp_user_embeddings.weight"], users, dh[:, :d])
+    if table_grad:
+        grads[TABLE_KEY] = np.zeros_like(table)
+        np.add.at(grads[TABLE_KEY], items, dh[:, d:])
     assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype
     return dtype(loss), z, grads
 
@@ -152,6 +174,24 @@ def ng_sample(pairs, num_user: int, num_item: int, num_ng: int, seed: int, chunk
     return users, items, labels
 
 
+def normalize_item_table(table):
+    """Row-wise L2 normalisation of an item table [I, d] as sklearn.preprocessing.normalize does it (what --normalize-item-init-emb applies to
+    the exported embeddings, load_node_init_emb, pmgt/pmgt/utils.py:37-38): norms = sqrt(einsum("ij,ij->i", X, X)) in the table's dtype, a
+    norm below 10 eps counts as 1 (sklearn's _handle_zeros_in_scale: the zero row stays zero), X / norms[:, None].  numpy in, numpy out; a torch tensor comes back as a tensor of the
+    same dtype on the same device (the arithmetic runs on the host: the table is normalised once, before training)."""
+    if hasattr(table, "detach"):
+        import torch
+        out = normalize_item_table(table.detach().cpu().numpy())
+        return torch.from_numpy(out).to(table.device)
+    x = np.array(table, copy=True)
+    if x.ndim != 2 or x.dtype.kind != "f":
+        raise ValueError(f"normalize_item_table: expected a floating-point matrix [I, d], got {x.dtype} {x.shape}")
+    norms = np.sqrt(np.einsum("ij,ij->i", x, x))
+    norms[norms < 10 * np.finfo(norms.dtype).eps] = 1.0
+    x /= norms[:, np.newaxis]
+    return x
+
+
 # ---- device side ------------------------------------------------------------------------------------------------------------------------------
 def _stream():
     import torch
@@ -168,9 +208,10 @@ class NcfHeadGrad:
     """pmgt_ncf_train_grad over one flat parameter buffer and one frozen table: __call__(users, items, labels) writes `grads` whole and
     returns (loss [1], logits [n]) as device tensors.  Two launches; nothing is copied to the host, nothing waits.  `params` and `grads` are
     fp32 device tensors of head_layout's parameter count; the workspace grows to the largest n seen (never inside a capture: call
-    reserve(n) first)."""
+    reserve(n) first).  With `table_grad`, a contiguous fp32 device tensor of the table's shape, the entry is pmgt_ncf_train_grad_table:
+    d loss / d table is written whole into it as well (the table is trained); `table` and `table_grad` may be views into larger buffers."""
 
-    def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads):
+    def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads, table_grad=None):
         import torch
         from . import _lib
         self.lib = _lib.hip()
@@ -181,7 +222,10 @@ class NcfHeadGrad:
         for name, t in (("params", params), ("grads", grads)):
             if t.dtype != torch.float32 or t.device != table.device or tuple(t.shape) != (self.count,) or not t.is_contiguous():
                 raise ValueError(f"ncf_train: {name} must be a contiguous fp32 tensor [{self.count}] on the table's device")
-        self.table, self.params, self.grads = table, params, grads
+        if table_grad is not None and (table_grad.dtype != torch.float32 or table_grad.device != table.device
+                                       or table_grad.shape != table.shape or not table_grad.is_contiguous()):
+            raise ValueError(f"ncf_train: table_grad must be a contiguous fp32 tensor {tuple(table.shape)} on the table's device")
+        self.table, self.params, self.grads, self.table_grad = table, params, grads, table_grad
         self.shape = (factor_num, num_layers, _lib.NCF_KINDS.index(kind))
         self.user_num, self.item_num = int(user_num), int(table.shape[0])
         h = NcfTrainC()
@@ -199,7 +243,8 @@ class NcfHeadGrad:
         import torch
         if n <= self._ws_pairs:
             return
-        nbytes = int(self.lib.pmgt_ncf_train_workspace_bytes(*self.shape, int(n)))
+        sizing = self.lib.pmgt_ncf_train_workspace_bytes if self.table_grad is None else self.lib.pmgt_ncf_train_table_workspace_bytes
+        nbytes = int(sizing(*self.shape, int(n)))
         if nbytes < 0:
             raise ValueError(f"ncf_train: n = {n} pairs outside [1, {NCF_TRAIN_MAX_PAIRS}]")
         if torch.cuda.is_current_stream_capturing():
@@ -217,8 +262,11 @@ class NcfHeadGrad:
         self.reserve(n)
         loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
         logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
-        _lib.check(self.lib.pmgt_ncf_train_grad(C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(),
-                                                logits.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()))
+        front = (C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(), logits.data_ptr())
+        if self.table_grad is None:
+            _lib.check(self.lib.pmgt_ncf_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _stream()))
+        else:
+            _lib.check(self.lib.pmgt_ncf_train_grad_table(*front, self.table_grad.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()))
         return loss, logits
 
 
@@ -232,10 +280,16 @@ class NcfHeadTrainer:
     embeddings uploaded), all on the device.  The head's parameters move into ONE flat fp32 buffer and the model's nn.Parameters are
     re-pointed at views of it, so model.head, state_dict, recommend and evaluate_ranking see the trained weights with no copy.  The trainer
     owns the gradient buffer, exp_avg, exp_avg_sq and the device step counter; weights and embeddings decay, biases do not
-    (pmgt/base_trainer.py get_optimizer).  max_grad_norm None or 0: no clipping."""
+    (pmgt/base_trainer.py get_optimizer).  max_grad_norm None or 0: no clipping.
+    train_table=True: the table is a parameter, initialised from `table` (which is copied, not kept) and trained with the head.  The flat
+    buffer is then table_layout's: the head, a pad up to a multiple of 8 floats, the table.  `trainer.table` is a VIEW of it -- rank_users
+    and recommend(table=trainer.table) read the trained rows with no copy --, the kernel's table and table_grad pointers point into the
+    flat parameters and gradients, and the one pmgt_op_adamw call over the whole buffer clips head and table by ONE global norm and steps
+    both: still five launches.  The table decays like every weight (get_optimizer exempts only biases and LayerNorm).  The pad floats are 0
+    in the parameters, the gradients and the moments, their decay mask is 0, and nothing writes them."""
 
     def __init__(self, model, table, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: float = None):
+                 max_grad_norm: float = None, train_table: bool = False):
         import torch
         import torch.nn as nn
         if model.emb_dropout.p != 0 or any(layer.dropout.p != 0 for layer in model.mlp_layers):
@@ -245,11 +299,12 @@ class NcfHeadTrainer:
         d = model.factor_num << (model.num_layers - 1)
         if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (model.item_num, d) or table.device != dev:
             raise ValueError(f"ncf_train: the item table must be an fp32 tensor [{model.item_num}, {d}] on {dev}")
-        self.model, self.table = model, table.detach().contiguous()
+        self.model, self.train_table = model, bool(train_table)
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
         self.max_grad_norm = float(max_grad_norm or 0.0)
-        self.layout, self.count = head_layout(model.factor_num, model.num_layers, model.model, model.user_num, model.item_num)
-        self.params = torch.empty(self.count, dtype=torch.float32, device=dev)
+        dims = (model.factor_num, model.num_layers, model.model, model.user_num, model.item_num)
+        self.layout, self.count = table_layout(*dims) if self.train_table else head_layout(*dims)
+        self.params = torch.zeros(self.count, dtype=torch.float32, device=dev)
         self.grads = torch.zeros_like(self.params)
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
         self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -260,12 +315,18 @@ class NcfHeadTrainer:
         with torch.no_grad():
             for key, (off, shape) in self.layout.items():
                 view = self.params[off: off + int(np.prod(shape))].view(shape)
-                view.copy_(named[key].detach())
-                mod = model.get_submodule(key.rsplit(".", 1)[0])
-                setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
+                if key == TABLE_KEY:
+                    view.copy_(table.detach())
+                else:
+                    view.copy_(named[key].detach())
+                    mod = model.get_submodule(key.rsplit(".", 1)[0])
+                    setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
                 if not key.endswith(".bias"):
                     self.decay[off: off + int(np.prod(shape))] = 1
-        self.grad_fn = NcfHeadGrad(model.factor_num, model.num_layers, model.model, model.user_num, self.table, self.params, self.grads)
+        head_count = head_layout(*dims)[1]                  # (the whole buffer when the table is frozen)
+        self.table = self.views(self.params)[TABLE_KEY] if self.train_table else table.detach().contiguous()
+        self.grad_fn = NcfHeadGrad(model.factor_num, model.num_layers, model.model, model.user_num, self.table, self.params[:head_count],
+                                   self.grads[:head_count], table_grad=self.views(self.grads)[TABLE_KEY] if self.train_table else None)
         self._graph = self._static = None
 
     def views(self, flat) -> dict:
@@ -320,13 +381,16 @@ class NcfHeadTrainer:
         return self._static[3]
 
     def state_dict(self) -> dict:
+        """The flat parameters, both moments, the step counter and the layout; a trained table is inside the parameters and named by the
+        layout, so a state saved frozen is refused by a trainer that trains the table, and the other way round."""
         return {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
                 "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
 
     def load_state_dict(self, sd: dict) -> None:
         import torch
         if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
-            raise ValueError("ncf_train: the state was saved for another head (the layouts differ)")
+            raise ValueError("ncf_train: the state was saved for another head, or with the table frozen / trained the other way "
+                             "(the layouts differ)")
         with torch.no_grad():
             self.params.copy_(sd["params"])
             self.exp_avg.copy_(sd["exp_avg"])
@@ -336,13 +400,17 @@ class NcfHeadTrainer:
 
 def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, num_ng: int = 1, seed: int = 0, early_criterion: str = "n20",
             patience: int = 10, ckpt_dir: str = None, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-            max_grad_norm: float = 5.0, batch_users: int = 256, log=None):
+            max_grad_norm: float = 5.0, batch_users: int = 256, log=None, train_table: bool = False):
     """Trains the head of `model` on the interaction list `train_pairs` [(user, item)] over the frozen `table`, the reference's downstream
     fit: every epoch draws ng_sample(seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's users, items and
     labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device and are read once
     per epoch.  Validation ranks `valid` = (users [U], candidates [U, C], labels [U, C], counts [U]) (datasets.ranking_candidates) with
     rank_users + RankingMetrics -> n10, n20, r10, r20, loss; early_criterion: "n20", "r20" or "loss" (EarlyStopping / BestCheckpoint of
     fit_loop.py).  The best epoch's head is restored into the model at the end (and kept as a file in ckpt_dir when given).
+    train_table=True (what scripts/run_ncf.sh does: the table is initialised from the embeddings and trained with the head,
+    NcfHeadTrainer(train_table=True)): validation ranks over the trained table, the best epoch's table is kept and restored with the head,
+    the checkpoint file gains the key "item_table", and at the end the best table is copied back into the caller's `table` tensor IN PLACE:
+    `table` IS OVERWRITTEN -- recommend(table=table) and evaluate_ranking(table=table) then read the trained rows.
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
     import torch
     from .evaluation import rank_users
@@ -361,7 +429,8 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
         raise ValueError("fit_ncf: valid must be (users [U], candidates [U, C], labels [U, C], counts [U])")
     if v_users.min() < 0 or v_users.max() >= model.user_num or v_cand.min() < 0 or v_cand.max() >= model.item_num:
         raise ValueError("fit_ncf: validation users or candidates outside the model's tables")
-    trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
+    trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
+                             train_table=train_table)
     dev = trainer.params.device
     on_dev = [torch.from_numpy(a).to(dev) for a in (v_users, v_cand, v_labels, v_counts)]
     metrics = RankingMetrics(dev, n_valid, (10, 20))
@@ -398,7 +467,10 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
             if write is not None:
                 best_params = trainer.params.detach().clone()
                 if ckpt_dir:
-                    torch.save({"epoch": epoch, "head": {k: v.detach().cpu() for k, v in head_state(model).items()}, "metrics": dict(row)}, write)
+                    ckpt = {"epoch": epoch, "head": {k: v.detach().cpu() for k, v in head_state(model).items()}, "metrics": dict(row)}
+                    if train_table:
+                        ckpt[TABLE_KEY] = trainer.table.detach().cpu()
+                    torch.save(ckpt, write)
                     if remove and os.path.exists(remove):
                         os.remove(remove)
             history.append(row)
@@ -406,9 +478,11 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
                 log(row)
             if stopper.update(row[early_criterion], epoch):
                 break
-        if best_params is not None:
-            with torch.no_grad():
-                trainer.params.copy_(best_params)
+        with torch.no_grad():
+            if best_params is not None:
+                trainer.params.copy_(best_params)            # (head and table: one buffer)
+            if train_table:
+                table.copy_(trainer.table)
     finally:
         model.train(was_training)
     return history

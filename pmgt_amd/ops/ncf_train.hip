@@ -1,6 +1,7 @@
-// Training of the head of PMGT_NCF over a FROZEN item table (pmgt_ncf_train_grad of include/pmgt_capi.h; the head: pmgt/pmgt_ncf/models.py:91-105,
-// the step it serves: pmgt/ncf/trainer.py:183-200): loss, logits and the gradient of the mean BCE-with-logits loss with respect to every
-// parameter of the head, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for ncf_score.hip's reason: the measured step
+// Training of the head of PMGT_NCF over an item table, FROZEN (pmgt_ncf_train_grad of include/pmgt_capi.h) or TRAINED WITH THE HEAD
+// (pmgt_ncf_train_grad_table; the head: pmgt/pmgt_ncf/models.py:91-105, the step it serves: pmgt/ncf/trainer.py:183-200, the table's
+// requires_grad_: pmgt/ncf/trainer.py:168-179): loss, logits and the gradient of the mean BCE-with-logits loss with respect to every
+// parameter of the head -- and, for the second entry, to the table --, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for ncf_score.hip's reason: the measured step
 // launches nothing of this.  fp32 end to end; every matrix product runs on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32).
 //
 // EVERYTHING IS PAIR-MAJOR.  Activations act_l [n][out_l], pre-activation gradients dz_l [n][out_l] and the per-pair embedding gradients sit in
@@ -15,18 +16,21 @@
 // LAUNCH 1, ncf_train_pairs_kernel, three roles by block index:
 //   tile   32 pairs a workgroup of 4 waves (the waves share out the 32-feature blocks of a layer): gathers [U_mlp[u] ; table[i]] on the fly,
 //          runs the layers, the GMF product and the predict layer, the stable loss max(z, 0) - z y + log1p(exp(-|z|)) and
-//          dlogit = (sigmoid(z) - y) / n, then walks back: dz_l = (W_(l+1)^T dz_(l+1)) * (act_l > 0) down to the user half of layer 0's input.
+//          dlogit = (sigmoid(z) - y) / n, then walks back: dz_l = (W_(l+1)^T dz_(l+1)) * (act_l > 0) down to the user half of layer 0's input
+//          (frozen table: dx [n][d]) or to all of it (trained table: dx [n][2 d], the item half behind the user half; a column block is
+//          computed on its own, so the user half has the same bits either way).
 //          Between layers the rows go through the workspace; a workgroup reads only what it wrote itself, behind a barrier.
 //   rank   the position of every pair in the STABLE order by user id (and, NeuMF-end, by item id): rank = the number of pairs with a smaller
 //          (id, pair index); counted, not sorted: n <= 65 536 and the ids of a block of 256 pairs go through LDS once per 256 ranks.
-//   zero   the gradient rows of the embedding tables, whole (the optimizer is dense).
+//   zero   the gradient rows of the embedding tables, whole (the optimizer is dense), and as a second range the table's gradient.
 // LAUNCH 2, ncf_train_grads_kernel, two roles:
 //   weight one workgroup per 32 x 32 block of a layer's dW; its 4 waves take the 32-pair chunks c = w, w + 4, ... IN ORDER and the four
 //          accumulators are added as (w0 + w1) + (w2 + w3).  A layer has one more block column whose B operand is the constant column
 //          (1, 0, ..., 0): its column 0 is the bias gradient.  The predict layer is the pseudo-layer with dz = [dlogit, loss_pair]: row 0 gives
 //          d predict_layer.weight and .bias, row 1 of the constant column the loss sum.
 //   rows   one wave per position of the stable order; the wave at the start of a run of equal ids adds the run's per-pair rows in pair order
-//          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.
+//          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.  The item kind sums the GMF item rows (NeuMF-end)
+//          and, for a trained table, the item half of dx by the same rule.
 // DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
 #include "../csrc/common.h"
 #include "../../include/pmgt_capi.h"
@@ -51,11 +55,13 @@ struct NtPairsArgs {
     const float *u_mlp, *table, *gu, *gi, *wp, *bp;
     const int64_t *users, *items;
     const float* labels;
-    float *du, *gprod, *ggu, *ggi, *pz;      // workspace: [n][d], [n][F] x 3, [n][2] = (dlogit, loss of the pair)
+    float *dx, *gprod, *ggu, *ggi, *pz;      // workspace: [n][d] (trained table: [n][2 d]), [n][F] x 3, [n][2] = (dlogit, loss of the pair)
     int *order_u, *order_i;                  // workspace: the pairs in stable order by user / item id
     float* logits;                           // [n] or NULL
     float* zero_base;                        // the embedding gradients
     int64_t zero_vec4;                       // ... in 16-byte pieces
+    float* zero2_base;                       // the table's gradient (trained table), a second range
+    int64_t zero2_vec4;                      // ... in 16-byte pieces; 0: no second range
     int n, d, factor, num_layers, neumf, tiles, rank_blocks, zero_blocks;
 };
 
@@ -81,8 +87,8 @@ struct NtGradsArgs {
     NtTask task[NT_MAX_TASKS];
     const int64_t *users, *items;
     const int *order_u, *order_i;
-    const float *du, *ggu, *ggi;
-    float *g_u_mlp, *g_gu, *g_gi, *loss;
+    const float *dx, *ggu, *ggi;
+    float *g_u_mlp, *g_gu, *g_gi, *g_table, *loss;                   // g_table: the trained table's gradient, else NULL
     int n, d, factor, neumf, ntasks, weight_blocks, row_blocks;      // row_blocks per kind (user, item)
 };
 
@@ -171,6 +177,8 @@ __device__ __forceinline__ void backward_layer(const float* __restrict__ W, int 
     }
 }
 
+// TABLE: the item table is trained (the frozen instantiation is the kernel as it was: the widths below fold to d)
+template <bool TABLE>
 __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a) {
     __shared__ float s_dl[NT_TILE];
     __shared__ int64_t s_ids[NT_THREADS];
@@ -178,8 +186,12 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     int bid = blockIdx.x;
     if (bid >= a.tiles + 2 * a.rank_blocks) {                // ---- zero: the embedding gradients, whole
         float4* z = reinterpret_cast<float4*>(a.zero_base);
-        for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * NT_THREADS + tid; i < a.zero_vec4; i += (int64_t)a.zero_blocks * NT_THREADS)
-            z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4* z2 = reinterpret_cast<float4*>(a.zero2_base);
+        const int64_t total = a.zero_vec4 + (TABLE ? a.zero2_vec4 : 0);
+        for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * NT_THREADS + tid; i < total; i += (int64_t)a.zero_blocks * NT_THREADS) {
+            if (!TABLE || i < a.zero_vec4) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else z2[i - a.zero_vec4] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         return;
     }
     if (bid >= a.tiles) {                                    // ---- rank: the stable order by id, counted
@@ -272,7 +284,8 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
                        a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane);
         __syncthreads();
     }
-    backward_layer(a.layer[0].w, d, 2 * d, d, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.du + (int64_t)pair * d, wave, lane);
+    const int dxw = TABLE ? 2 * d : d;                       // the columns of layer 0's input that dx covers
+    backward_layer(a.layer[0].w, d, 2 * d, dxw, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.dx + (int64_t)pair * dxw, wave, lane);
 }
 
 __device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
@@ -284,6 +297,7 @@ __device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
     return s.p2[row * s.w2 + (c - s.w1)];
 }
 
+template <bool TABLE>
 __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs a) {
     __shared__ float s_acc[NT_WAVES][16][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
@@ -298,19 +312,24 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
         const int64_t id = ids[order[s]];
         if (s > 0 && ids[order[s - 1]] == id) return;        // (uniform per wave) not the start of a run
         const int d = a.d, F = a.factor;
-        const int width = kind ? F : d + (a.neumf ? F : 0);
+        const int Fg = a.neumf ? F : 0;                      // the GMF rows of this kind
+        const int dxw = TABLE ? 2 * d : d;
+        const int width = kind ? Fg + (TABLE ? d : 0) : d + Fg;
         for (int c = lane; c < width; c += 64) {
-            const float* src;
-            float* dst;
-            int w, cc;
-            if (kind) { src = a.ggi; dst = a.g_gi; w = F; cc = c; }
-            else if (c < d) { src = a.du; dst = a.g_u_mlp; w = d; cc = c; }
-            else { src = a.ggu; dst = a.g_gu; w = F; cc = c - d; }
+            const float* src;                                // the per-pair rows, `sw` floats apart
+            float* dst;                                      // the table's rows, `w` floats wide
+            int sw, w, cc;
+            if (kind) {
+                if (c < Fg) { src = a.ggi; dst = a.g_gi; sw = w = F; cc = c; }
+                else { src = a.dx + d; dst = a.g_table; sw = dxw; w = d; cc = c - Fg; }
+            }
+            else if (c < d) { src = a.dx; dst = a.g_u_mlp; sw = dxw; w = d; cc = c; }
+            else { src = a.ggu; dst = a.g_gu; sw = w = F; cc = c - d; }
             float sum = 0.f;
             for (int t = s; t < n; ++t) {
                 const int pr = order[t];
                 if (ids[pr] != id) break;
-                sum += src[(int64_t)pr * w + cc];
+                sum += src[(int64_t)pr * sw + cc];
             }
             dst[id * w + cc] = sum;
         }
@@ -400,11 +419,12 @@ static int64_t nt_layout(const NtShape& s, int64_t* off) {
     return at;
 }
 
-// the workspace in floats: act_l and dz_l [n][d >> l], du [n][d], gprod / ggu / ggi [n][F], pz [n][2], then the two orders (int [n] each)
-static int64_t nt_workspace_floats(const NtShape& s, int64_t n) {
+// the workspace in floats: act_l and dz_l [n][d >> l], dx [n][d] (trained table: [n][2 d]), gprod / ggu / ggi [n][F], pz [n][2], then the
+// two orders (int [n] each)
+static int64_t nt_workspace_floats(const NtShape& s, int64_t n, bool table) {
     int64_t w = 0;
     for (int l = 0; l < s.L; ++l) w += 2 * n * (s.d >> l);
-    w += n * s.d + 3 * n * s.F;
+    w += n * s.d * (table ? 2 : 1) + 3 * n * s.F;
     w += (2 * n + 3) / 4 * 4;
     w += 2 * ((n + 3) / 4 * 4);
     return w;
@@ -426,29 +446,32 @@ int64_t pmgt_ncf_train_layout(int factor_num, int num_layers, int kind, int64_t 
     return count;
 }
 
-int64_t pmgt_ncf_train_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n) {
+}  // extern "C"
+
+namespace pmgt {
+
+static int64_t nt_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n, bool table, const char* who) {
     NtShape s;
-    if (int rc = nt_shape(factor_num, num_layers, kind, 1, 1, "pmgt_ncf_train_workspace_bytes", &s)) return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "pmgt_ncf_train_workspace_bytes: n = %lld pairs outside [1, %d]", (long long)n,
-               PMGT_NCF_TRAIN_MAX_PAIRS);
-    return nt_workspace_floats(s, n) * (int64_t)sizeof(float);
+    if (int rc = nt_shape(factor_num, num_layers, kind, 1, 1, who, &s)) return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_NCF_TRAIN_MAX_PAIRS);
+    return nt_workspace_floats(s, n, table) * (int64_t)sizeof(float);
 }
 
-int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
-                        float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
-    PMGT_CHECK(head != nullptr, -2, "pmgt_ncf_train_grad: NULL head");
+// both gradient entries; want_table: the table is trained and table_grad [item_num][d] is written whole
+static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                   float* loss, float* logits, bool want_table, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream) {
+    PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
     NtShape s;
-    if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, "pmgt_ncf_train_grad", &s)) return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "pmgt_ncf_train_grad: n = %lld pairs outside [1, %d]", (long long)n,
-               PMGT_NCF_TRAIN_MAX_PAIRS);
-    PMGT_CHECK(head->table && head->params && head->grads && users && items && labels && loss && workspace, -2, "pmgt_ncf_train_grad: NULL buffer");
-    PMGT_CHECK((((uintptr_t)head->table | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace) & 15) == 0, -2,
-               "pmgt_ncf_train_grad: the table, the parameters, the gradients and the workspace must be 16-byte aligned");
+    if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, who, &s)) return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_NCF_TRAIN_MAX_PAIRS);
+    PMGT_CHECK(head->table && head->params && head->grads && users && items && labels && loss && workspace, -2, "%s: NULL buffer", who);
+    PMGT_CHECK(!want_table || table_grad, -2, "%s: NULL table_grad", who);
+    PMGT_CHECK((((uintptr_t)head->table | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace | (uintptr_t)table_grad) & 15) == 0,
+               -2, "%s: the table, the parameters, the gradients (the table's included) and the workspace must be 16-byte aligned", who);
     PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
-               "pmgt_ncf_train_grad: misaligned buffer");
-    const int64_t need = nt_workspace_floats(s, n) * (int64_t)sizeof(float);
-    PMGT_CHECK(workspace_bytes >= need, -2, "pmgt_ncf_train_grad: workspace of %lld bytes below the %lld needed", (long long)workspace_bytes,
-               (long long)need);
+               "%s: misaligned buffer", who);
+    const int64_t need = nt_workspace_floats(s, n, want_table) * (int64_t)sizeof(float);
+    PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
     int64_t off[PMGT_NCF_TRAIN_TENSORS];
     nt_layout(s, off);
     const float* P = head->params;
@@ -467,7 +490,8 @@ int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const 
         pa.layer[l].act = ws, ws += n * out;
         pa.layer[l].dz = ws, ws += n * out;
     }
-    pa.du = ws, ws += n * d;
+    const int dxw = want_table ? 2 * d : d;
+    pa.dx = ws, ws += n * dxw;
     pa.gprod = ws, ws += n * F;
     pa.ggu = ws, ws += n * F;
     pa.ggi = ws, ws += n * F;
@@ -486,10 +510,12 @@ int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const 
     pa.logits = logits;
     pa.zero_base = G;
     pa.zero_vec4 = off[3] / 4;                               // the embedding tables come first; every size is a multiple of 8 floats
+    pa.zero2_base = table_grad;
+    pa.zero2_vec4 = want_table ? s.item_num * d / 4 : 0;     // (d is a multiple of 8)
     pa.n = (int)n, pa.d = d, pa.factor = F, pa.num_layers = L, pa.neumf = s.neumf;
     pa.tiles = (int)cdiv64(n, NT_TILE);
     pa.rank_blocks = (int)cdiv64(n, NT_THREADS);
-    pa.zero_blocks = (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(pa.zero_vec4, NT_THREADS));
+    pa.zero_blocks = (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(pa.zero_vec4 + pa.zero2_vec4, NT_THREADS));
 
     int first = 0;
     for (int l = 0; l < L; ++l) {
@@ -524,22 +550,47 @@ int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const 
     ga.row_blocks = (int)cdiv64(n, NT_WAVES);
     ga.users = users, ga.items = items;
     ga.order_u = pa.order_u, ga.order_i = pa.order_i;
-    ga.du = pa.du, ga.ggu = pa.ggu, ga.ggi = pa.ggi;
+    ga.dx = pa.dx, ga.ggu = pa.ggu, ga.ggi = pa.ggi;
     ga.g_u_mlp = G + off[0];
     ga.g_gu = s.neumf ? G + off[1] : nullptr;
     ga.g_gi = s.neumf ? G + off[2] : nullptr;
+    ga.g_table = want_table ? table_grad : nullptr;
     ga.loss = loss;
     ga.n = (int)n, ga.d = d, ga.factor = F, ga.neumf = s.neumf;
 
     hipStream_t st = (hipStream_t)stream;
-    const int kinds = s.neumf ? 2 : 1;                       // MLP has no table indexed by item: its item order is computed and not read
+    const int kinds = (s.neumf || want_table) ? 2 : 1;       // MLP over a frozen table has no rows indexed by item: its item order is not read
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
-    hipLaunchKernelGGL(ncf_train_pairs_kernel, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
+    if (want_table) hipLaunchKernelGGL(ncf_train_pairs_kernel<true>, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
+    else hipLaunchKernelGGL(ncf_train_pairs_kernel<false>, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
     PMGT_LAUNCH_OK();
     const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks);
-    hipLaunchKernelGGL(ncf_train_grads_kernel, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
+    if (want_table) hipLaunchKernelGGL(ncf_train_grads_kernel<true>, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
+    else hipLaunchKernelGGL(ncf_train_grads_kernel<false>, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
     PMGT_LAUNCH_OK();
     return 0;
+}
+
+}  // namespace pmgt
+
+extern "C" {
+
+int64_t pmgt_ncf_train_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n) {
+    return nt_workspace_bytes(factor_num, num_layers, kind, n, false, "pmgt_ncf_train_workspace_bytes");
+}
+
+int64_t pmgt_ncf_train_table_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n) {
+    return nt_workspace_bytes(factor_num, num_layers, kind, n, true, "pmgt_ncf_train_table_workspace_bytes");
+}
+
+int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                        float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+    return nt_grad("pmgt_ncf_train_grad", head, users, items, labels, n, loss, logits, false, nullptr, workspace, workspace_bytes, stream);
+}
+
+int pmgt_ncf_train_grad_table(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                              float* logits, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream) {
+    return nt_grad("pmgt_ncf_train_grad_table", head, users, items, labels, n, loss, logits, true, table_grad, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
