@@ -378,8 +378,8 @@ int pmgt_topk_rows(const float* scores, int64_t row_stride, int64_t n, int64_t n
  * the weight gradients over the pairs in one fixed order (32-pair chunks dealt to four accumulators, added as (0 + 1) + (2 + 3)).
  * users / items int64 [n] (ids inside the tables: THE CALLER CHECKS THEM, they are read as they are), labels fp32 [n], table fp32
  * [item_num][d], loss one device float, logits fp32 [n] or NULL; workspace: pmgt_ncf_train_workspace_bytes(...) bytes of 16-byte aligned
- * device memory.  Covered: what pmgt_ncf_score covers (factor_num 8 / 16 / 32 / 64, 1 .. PMGT_NCF_MAX_LAYERS layers, d <= 256, both
- * kinds), 1 <= n <= PMGT_NCF_TRAIN_MAX_PAIRS.  Refused (-2; the two sizing entries return it as their value) before anything is launched:
+ * device memory.  Covered: the heads pmgt_ncf_score covers (one rule, stated there), 1 <= n <= PMGT_NCF_TRAIN_MAX_PAIRS.
+ * Refused (-2; the two sizing entries return it as their value) before anything is launched:
  * a head or n outside these limits, a NULL or misaligned buffer (table, parameters, gradients and workspace: 16 bytes), a short workspace.
  * Added without a bump of pmgt_abi_version(): one struct, three entries, nothing existing moved. */
 #define PMGT_NCF_TRAIN_MAX_PAIRS 65536

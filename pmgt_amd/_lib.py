@@ -85,8 +85,16 @@ class NcfHeadC(C.Structure):
                 ("gmf_user", C.c_void_p), ("gmf_item", C.c_void_p), ("user_num", C.c_int64)]
 
 
+class NcfTrainC(C.Structure):
+    """pmgt_ncf_train (include/pmgt_capi.h)."""
+    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("reserved", C.c_int), ("user_num", C.c_int64),
+                ("item_num", C.c_int64), ("table", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p)]
+
+
 NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
 NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
+NCF_FACTORS, NCF_MAX_D = (8, 16, 32, 64), 256      # the covered heads (pmgt_ncf_score's comment): factor_num, d = factor_num * 2^(num_layers - 1)
+NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS = 65536, 13      # PMGT_NCF_TRAIN_*
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
@@ -276,10 +284,10 @@ def hip():
     L.pmgt_ncf_train_layout.argtypes = [i, i, i, i64, i64, vp]
     L.pmgt_ncf_train_workspace_bytes.restype = i64
     L.pmgt_ncf_train_workspace_bytes.argtypes = [i, i, i, i64]
-    L.pmgt_ncf_train_grad.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]      # (head: byref of ncf_train.NcfTrainC)
+    L.pmgt_ncf_train_grad.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, i64, vp]
     L.pmgt_ncf_train_table_workspace_bytes.restype = i64
     L.pmgt_ncf_train_table_workspace_bytes.argtypes = [i, i, i, i64]
-    L.pmgt_ncf_train_grad_table.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
+    L.pmgt_ncf_train_grad_table.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
     _hip = L
     return L
 
@@ -315,6 +323,12 @@ class Ops:
 def ops():
     """A fresh Ops view of libpmgt_hip.so (path options start at 0)."""
     return Ops()
+
+
+def stream():
+    """The current torch stream as the `void* stream` argument of an entry."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def check(rc):

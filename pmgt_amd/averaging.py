@@ -140,10 +140,6 @@ class WeightAverage:
         """What a captured step freezes of the averaging."""
         return (self.mode, self.decay, self.warmup)
 
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def init_from_params(self) -> None:
         """swa_init (pmgt/utils/train.py:39-50): the average is the current parameters, models_num = 1 / n_upd = 0.  In place."""
         self.avg.copy_(self.engine.params)
@@ -161,12 +157,12 @@ class WeightAverage:
         else:
             cfg = _lib.AvgStepC(1, int(self.warmup), self.decay, self.state.data_ptr(), None if skip_flag is None else skip_flag.data_ptr(),
                                 0.0, 0.0)
-        _lib.check(self.lib.pmgt_weight_average_update(self.avg.data_ptr(), eng.params.data_ptr(), eng.n_params, C.byref(cfg), self._stream()))
+        _lib.check(self.lib.pmgt_weight_average_update(self.avg.data_ptr(), eng.params.data_ptr(), eng.n_params, C.byref(cfg), _lib.stream()))
 
     def swap(self) -> None:
         """Exchanges the contents of the average and the parameter buffer (swap_swa_params' effect, pmgt/utils/train.py:72-85)."""
         from . import _lib
-        _lib.check(self.lib.pmgt_weight_swap(self.avg.data_ptr(), self.engine.params.data_ptr(), self.engine.n_params, self._stream()))
+        _lib.check(self.lib.pmgt_weight_swap(self.avg.data_ptr(), self.engine.params.data_ptr(), self.engine.n_params, _lib.stream()))
 
     def count(self) -> int:
         """models_num ("swa", a host int) or n_upd ("ema": one small device -> host read)."""

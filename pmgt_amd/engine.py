@@ -19,9 +19,6 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
 
 class Engine:
     """Flat fp32 parameters/gradients, frozen feature tables, RNG state and scratch for one GPU."""
@@ -188,7 +185,7 @@ class Engine:
                 scale = np.float32(amax) / np.float32(448.0) if amax > 0 else np.float32(1.0)
                 inv = np.float32(448.0) / np.float32(amax) if amax > 0 else np.float32(1.0)
                 q = torch.empty(t.shape, dtype=torch.uint8, device=self.device)
-                _lib.check(self.lib.pmgt_quantize_e4m3(_ptr(t), _ptr(q), t.numel(), float(inv), _stream()))
+                _lib.check(self.lib.pmgt_quantize_e4m3(_ptr(t), _ptr(q), t.numel(), float(inv), _lib.stream()))
                 tabs.append(q)
                 scales.append(float(scale))
             else:
@@ -204,7 +201,7 @@ class Engine:
         out = []
         for q, sc in zip(self.tables, self.table_scale):
             o = torch.empty(q.shape, dtype=torch.float32, device=self.device)
-            _lib.check(self.lib.pmgt_dequantize_e4m3(_ptr(q), _ptr(o), q.numel(), sc, _stream()))
+            _lib.check(self.lib.pmgt_dequantize_e4m3(_ptr(q), _ptr(o), q.numel(), sc, _lib.stream()))
             out.append(o)
         return out
 
@@ -212,7 +209,7 @@ class Engine:
         """fp32 device tensor -> engine dtype through the library's own cast kernel."""
         x = x.to(self.device, torch.float32).contiguous()
         out = torch.empty(x.shape, dtype=self.torch_dtype, device=self.device)
-        _lib.check(self.lib.pmgt_cast_from_f32(self.dtype_code, _ptr(x), _ptr(out), x.numel(), _stream()))
+        _lib.check(self.lib.pmgt_cast_from_f32(self.dtype_code, _ptr(x), _ptr(out), x.numel(), _lib.stream()))
         return out
 
     def _tensors(self, grad_buffer: Optional[torch.Tensor] = None):
@@ -303,7 +300,7 @@ class Engine:
                 (_lib.FLAG_ACCUMULATE if accumulate else 0)
         tc = self._tensors(grad_buffer)
         _lib.check(self.lib.pmgt_pretrain_step(self.h, C.byref(tc), C.byref(bc), C.byref(oc), _ptr(ws), ws.numel(),
-                                               flags, _stream()))
+                                               flags, _lib.stream()))
         self._raise_hook_error()
         return dict(loss=loss[0], gsr=loss[1], nfr=loss[2], losses=loss, logits=logits, last_hidden_state=hidden,
                     nfr_count=count)
@@ -326,11 +323,11 @@ class Engine:
         if ids is not None:
             ids = ids.to(self.device).contiguous()
             _lib.check(self.lib.pmgt_encode_ids(self.h, C.byref(tc), _ptr(ids), _ptr(m), n_seq, S, _ptr(last), _ptr(hs),
-                                                _ptr(pr), _ptr(ws), ws.numel(), _stream()))
+                                                _ptr(pr), _ptr(ws), ws.numel(), _lib.stream()))
         else:
             dev, fp = self._feat_args(feats)
             _lib.check(self.lib.pmgt_encode_feats(self.h, C.byref(tc), fp, _ptr(m), n_seq, S, _ptr(last),
-                                                  _ptr(hs), _ptr(pr), _ptr(ws), ws.numel(), _stream()))
+                                                  _ptr(hs), _ptr(pr), _ptr(ws), ws.numel(), _lib.stream()))
         return last, hs, pr
 
     # ---- PMGTModel.forward with activations kept for a backward driven by the caller's head ------------------
@@ -352,7 +349,7 @@ class Engine:
         tc = self._tensors()
         flags = _lib.FLAG_TRAINING if training else 0
         _lib.check(self.lib.pmgt_encode_train(self.h, C.byref(tc), _ptr(ids), fp, _ptr(m), n_seq, S, _ptr(last),
-                                              _ptr(ws), nbytes, flags, _stream()))
+                                              _ptr(ws), nbytes, flags, _lib.stream()))
         return last, dict(ws=ws, feats=dev, feat_ptrs=fp, n_seq=n_seq, S=S, flags=flags)
 
     def encode_backward(self, state: dict, d_last: torch.Tensor, accumulate: bool = False,
@@ -364,7 +361,7 @@ class Engine:
         flags = state["flags"] | (_lib.FLAG_ACCUMULATE if accumulate else 0)
         ws = state["ws"]
         _lib.check(self.lib.pmgt_encode_backward(self.h, C.byref(tc), state["feat_ptrs"], _ptr(d_last),
-                                                 state["n_seq"], state["S"], _ptr(ws), ws.numel(), flags, _stream()))
+                                                 state["n_seq"], state["S"], _ptr(ws), ws.numel(), flags, _lib.stream()))
         self._raise_hook_error()
 
     # ---- clip + AdamW ----------------------------------------------------------------------------------
@@ -423,12 +420,12 @@ class Engine:
                                   self.step_log_i.data_ptr() if rows else None, rows, None if loss is None else loss.data_ptr(),
                                   1 if guard.get("skip_nonfinite") else 0)
             _lib.check(self.lib.pmgt_optimizer_step_guarded(self.h, C.byref(tc), C.byref(ac), None if sc is None else C.byref(sc),
-                                                            C.byref(gd), _stream()))
+                                                            C.byref(gd), _lib.stream()))
             return
         if sc is not None:
-            _lib.check(self.lib.pmgt_optimizer_step_scheduled(self.h, C.byref(tc), C.byref(ac), C.byref(sc), _stream()))
+            _lib.check(self.lib.pmgt_optimizer_step_scheduled(self.h, C.byref(tc), C.byref(ac), C.byref(sc), _lib.stream()))
             return
-        _lib.check(self.lib.pmgt_optimizer_step(self.h, C.byref(tc), C.byref(ac), _stream()))
+        _lib.check(self.lib.pmgt_optimizer_step(self.h, C.byref(tc), C.byref(ac), _lib.stream()))
 
     # ---- everything a training step mutates, as plain data (Trainer.state_dict / pmgt_amd.io carry it to disk) --------------
     def step_counters(self) -> dict:

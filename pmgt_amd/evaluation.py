@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from .datasets import MODE_EVAL, MODE_INFERENCE
+from .ncf_head import check_ids, check_item_table
 from .parallel import gather_predictions, world
 
 
@@ -242,6 +243,20 @@ def rank_users(model, table: torch.Tensor, users: torch.Tensor, candidates: torc
         sink(logits.contiguous(), labels[lo:hi], counts[lo:hi], lo)
 
 
+def check_candidates(model, users, candidates, labels, counts, who: str):
+    """The four arrays as rank_users reads them; ValueError in `who`'s name for shapes that differ, counts or C out of range, and ids outside
+    `model`'s tables (which would only show up as a device-side fault in the gather)."""
+    users, candidates = np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(candidates, dtype=np.int64)
+    labels, counts = np.ascontiguousarray(labels, dtype=np.float32), np.ascontiguousarray(counts, dtype=np.int32)
+    if candidates.ndim != 2 or users.shape != candidates.shape[:1] or labels.shape != candidates.shape or counts.shape != users.shape or len(users) < 1:
+        raise ValueError(f"{who}: users {users.shape}, candidates {candidates.shape}, labels {labels.shape}, counts {counts.shape} must be [U], [U, C] x 2, [U]")
+    check_ids("users", users, model.user_num, who)
+    check_ids("candidates", candidates, model.item_num, who)
+    if counts.min() < 1 or counts.max() > candidates.shape[1] or candidates.shape[1] > 4096:
+        raise ValueError(f"{who}: counts must lie in [1, C = {candidates.shape[1]}] and C in [1, 4096]")
+    return users, candidates, labels, counts
+
+
 def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 20), batch_users: int = 256, metrics: str = "host",
                      threads: int = 8, seed: int = 0, per_user: bool = False, table=None):
     """Top-N recommendation quality of a PMGT_NCF (the reference's test_step / test_epoch_end, pmgt/ncf/trainer.py:202-254): the catalogue
@@ -259,24 +274,10 @@ def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
     ks = check_ks(ks)
-    users, candidates = np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(candidates, dtype=np.int64)
-    labels, counts = np.ascontiguousarray(labels, dtype=np.float32), np.ascontiguousarray(counts, dtype=np.int32)
-    U, Cn = candidates.shape
-    if users.shape != (U,) or labels.shape != (U, Cn) or counts.shape != (U,) or U < 1:
-        raise ValueError(f"evaluate_ranking: users {users.shape}, candidates {candidates.shape}, labels {labels.shape}, counts {counts.shape} "
-                         "must be [U], [U, C], [U, C], [U]")
-    # an id outside the model's tables would only show up as a device-side fault in the gather: refuse it here
-    if users.min() < 0 or users.max() >= model.user_num:
-        raise ValueError(f"evaluate_ranking: users in [{int(users.min())}, {int(users.max())}] outside the model's [0, {model.user_num})")
-    if candidates.min() < 0 or candidates.max() >= model.item_num:
-        raise ValueError(f"evaluate_ranking: candidates in [{int(candidates.min())}, {int(candidates.max())}] outside the model's "
-                         f"[0, {model.item_num})")
-    if counts.min() < 1 or counts.max() > Cn or Cn > 4096:
-        raise ValueError(f"evaluate_ranking: counts must lie in [1, C = {Cn}] and C in [1, 4096]")
+    users, candidates, labels, counts = check_candidates(model, users, candidates, labels, counts, "evaluate_ranking")
     dev = model.engine.device
-    if table is not None and (not isinstance(table, torch.Tensor) or tuple(table.shape) != (model.item_num, model.config.hidden_size)
-                              or table.dtype != torch.float32 or table.device != dev):
-        raise ValueError(f"evaluate_ranking: table must be an fp32 tensor [{model.item_num}, {model.config.hidden_size}] on {dev}")
+    if table is not None:
+        check_item_table(table, model.item_num, model.config.hidden_size, dev, "evaluate_ranking")
     was_training = model.training
     model.eval()
     try:
@@ -284,7 +285,7 @@ def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 
             table = encode_catalogue(model, sampler, threads=threads, seed=seed)
         on_dev = [torch.from_numpy(a).to(dev) for a in (users, candidates, labels, counts)]
         if metrics == "device":
-            rm = RankingMetrics(dev, U, ks)
+            rm = RankingMetrics(dev, len(users), ks)
             rank_users(model, table, *on_dev, sink=rm.update, batch_users=batch_users)
             result = rm.result()
             return (result, rm.per_user()) if per_user else result

@@ -20,9 +20,6 @@ MAX_CAPACITY = 1 << 26
 ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."       # roc_auc_score's text
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
 
 class ValidationMetrics:
     """`capacity` prediction slots on `device`.  reset() -> update(...) per batch -> result().  The cursor (next free slot) and the number of
@@ -54,7 +51,7 @@ class ValidationMetrics:
         return n
 
     def reset(self) -> None:
-        _lib.check(self.lib.pmgt_eval_reset(self._ws.data_ptr(), self.capacity, _stream()))
+        _lib.check(self.lib.pmgt_eval_reset(self._ws.data_ptr(), self.capacity, _lib.stream()))
         self.cursor = 0
         self.n_targets = 0
 
@@ -69,7 +66,7 @@ class ValidationMetrics:
         if int(labels.numel()) != n:
             raise ValueError(f"ValidationMetrics: {n} predictions with {int(labels.numel())} labels")
         _lib.check(fn(self._ws.data_ptr(), self.capacity, values.data_ptr(), labels.data_ptr(), 0 if loss is None else loss.data_ptr(), off, n,
-                      int(n_targets), _stream()))
+                      int(n_targets), _lib.stream()))
         self.cursor = max(self.cursor, off + n)
         self.n_targets += int(n_targets)
 
@@ -94,7 +91,7 @@ class ValidationMetrics:
         """Runs the reduce and returns its integers: twoU, n_pos, n_neg, nan (reads the device)."""
         if self.cursor < 1:
             raise ValueError("ValidationMetrics: no prediction was added")
-        _lib.check(self.lib.pmgt_eval_reduce(self._ws.data_ptr(), self.capacity, self.cursor, _stream()))
+        _lib.check(self.lib.pmgt_eval_reduce(self._ws.data_ptr(), self.capacity, self.cursor, _lib.stream()))
         acc, u = self._header()
         return dict(acc=acc, twoU=u[1], n_pos=u[2], n_neg=u[3], nan=u[4], n=u[5])
 
@@ -166,7 +163,7 @@ class RankingMetrics:
 
     def reset(self) -> None:
         _lib.check(self.lib.pmgt_rank_reset(self._ws.data_ptr(), self.max_users, self._ks_c, len(self.ks), self._disc.ctypes.data,
-                                            self._idcg.ctypes.data, _stream()))
+                                            self._idcg.ctypes.data, _lib.stream()))
         self.cursor = 0
 
     def update(self, logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor = None, offset: int = None) -> None:
@@ -188,14 +185,14 @@ class RankingMetrics:
                                    or tuple(counts.shape) != (n,)):
             raise ValueError("RankingMetrics: counts must be a contiguous int32 tensor [n_users] on the metrics' device")
         _lib.check(self.lib.pmgt_rank_append(self._ws.data_ptr(), self.max_users, logits.data_ptr(), labels.data_ptr(),
-                                             0 if counts is None else counts.data_ptr(), stride, off, n, _stream()))
+                                             0 if counts is None else counts.data_ptr(), stride, off, n, _lib.stream()))
         self.cursor = max(self.cursor, off + n)
 
     def statistic(self) -> dict:
         """Runs the reduce and returns the header: the sums per k, the loss sum and the three counts (reads the device)."""
         if self.cursor < 1:
             raise ValueError("RankingMetrics: no user was added")
-        _lib.check(self.lib.pmgt_rank_reduce(self._ws.data_ptr(), self.max_users, self.cursor, _stream()))
+        _lib.check(self.lib.pmgt_rank_reduce(self._ws.data_ptr(), self.max_users, self.cursor, _lib.stream()))
         h = self._ws[:RANK_HEADER_BYTES].cpu().numpy()        # the one device-to-host copy
         f, u = h.view(np.float64), h.view(np.uint64)
         return dict(ndcg={k: float(f[i]) for i, k in enumerate(self.ks)}, recall={k: float(f[RANK_MAX_KS + i]) for i, k in enumerate(self.ks)},

@@ -4,137 +4,25 @@ every epoch, BCEWithLogitsLoss, gradient clipping, AdamW, validation on nDCG / r
 (--freeze-item-init-emb); with train_table=True it is INITIALISED from the embeddings and TRAINED WITH THE HEAD, which is what run_ncf.sh and
 every config/hpo/train_ncf_*_params.json do (pmgt/ncf/trainer.py:168-179, "freeze_item_init_emb": false).
 
-  ncf_head_grad_host   loss, logits and the gradient of every head parameter (and of the table) in numpy: the yardstick of the kernels
   ng_sample            the reference's training-mode negative sampling, the same stream of draws
   normalize_item_table row-wise L2 normalisation of the exported embeddings (--normalize-item-init-emb)
   NcfHeadTrainer       the head's parameters (and the table) in one flat device buffer; step() = pmgt_ncf_train_grad or
                        pmgt_ncf_train_grad_table (two launches) + pmgt_op_adamw (three)
   fit_ncf              epochs of sampled pairs, ranking validation, early stopping, the best head (and table) restored
 
-The pure-numpy part needs no GPU."""
+The pure-numpy part needs no GPU; the head (head_layout, table_layout, check_pairs, the yardstick ncf_head_grad_host) is stated in ncf_head.py."""
 import ctypes as C
 import os
 
 import numpy as np
 
-from .recommend import check_head_covered, head_shape
-
-NCF_TRAIN_MAX_PAIRS = 65536                      # PMGT_NCF_TRAIN_MAX_PAIRS
-NCF_TRAIN_TENSORS = 13                           # PMGT_NCF_TRAIN_TENSORS
-HEAD_PREFIXES = ("mlp_user_embeddings.", "mlp_layers.", "predict_layer.", "gmf_user_embeddings.", "gmf_item_embeddings.")
+from . import _lib
+from ._lib import NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS, NcfTrainC  # noqa: F401
+from .ncf_head import (HEAD_PREFIXES, TABLE_KEY, check_head_covered, check_item_table, check_pairs, head_layout, head_shape,  # noqa: F401
+                       head_state, layout_slots, ncf_head_grad_host, table_layout)
 
 
 # ---- host side: pure numpy ------------------------------------------------------------------------------------------------------------------
-def head_layout(factor_num: int, num_layers: int, kind: str, user_num: int, item_num: int):
-    """The flat parameter layout of pmgt_ncf_train_grad (include/pmgt_capi.h): -> ({state_dict key: (offset in floats, shape)} in buffer
-    order, parameter count).  The three embedding tables come first, then weight and bias per layer (layer 0 UNSPLIT, [d, 2 d]), then the
-    predict layer; every tensor but the last (predict_layer.bias, one float) has a multiple of 8 floats, so every offset is 32-byte aligned."""
-    check_head_covered(factor_num, num_layers, kind)
-    if not (isinstance(user_num, (int, np.integer)) and isinstance(item_num, (int, np.integer)) and 1 <= user_num < 2 ** 31 - 1
-            and 1 <= item_num < 2 ** 31 - 1):
-        raise ValueError(f"ncf_train: user_num = {user_num!r} and item_num = {item_num!r} must be integers in [1, 2^31 - 2]")
-    d = factor_num << (num_layers - 1)
-    shapes = [("mlp_user_embeddings.weight", (int(user_num), d))]
-    if kind == "NeuMF-end":
-        shapes += [("gmf_user_embeddings.weight", (int(user_num), factor_num)), ("gmf_item_embeddings.weight", (int(item_num), factor_num))]
-    for i in range(num_layers):
-        out = d >> i
-        shapes += [(f"mlp_layers.{i}.linear.weight", (out, 2 * out)), (f"mlp_layers.{i}.linear.bias", (out,))]
-    shapes += [("predict_layer.weight", (1, factor_num * (2 if kind == "NeuMF-end" else 1))), ("predict_layer.bias", (1,))]
-    layout, at = {}, 0
-    for key, shape in shapes:
-        layout[key] = (at, shape)
-        at += int(np.prod(shape))
-    return layout, at
-
-
-TABLE_KEY = "item_table"                         # the trained table's name in the layouts, the gradients and the checkpoints
-
-
-def table_layout(factor_num: int, num_layers: int, kind: str, user_num: int, item_num: int):
-    """The flat buffer of a trainer that trains the item table: head_layout followed by TABLE_KEY [item_num, d], its offset rounded up to a
-    multiple of 8 floats (the head ends with the one float of predict_layer.bias; the table's rows stay 32-byte aligned)
-    -> (layout, count of the whole buffer).  The pad floats between the head and the table belong to no named tensor."""
-    layout, count = head_layout(factor_num, num_layers, kind, user_num, item_num)
-    off = (count + 7) // 8 * 8
-    d = factor_num << (num_layers - 1)
-    layout[TABLE_KEY] = (off, (int(item_num), d))
-    return layout, off + int(item_num) * d
-
-
-def layout_slots(layout: dict):
-    """The offsets of `layout` in the slot order of pmgt_ncf_train_layout (-1: the head has no such tensor)."""
-    slots = ["mlp_user_embeddings.weight", "gmf_user_embeddings.weight", "gmf_item_embeddings.weight"]
-    slots += [f"mlp_layers.{i}.linear.{p}" for i in range(4) for p in ("weight", "bias")] + ["predict_layer.weight", "predict_layer.bias"]
-    return [layout[k][0] if k in layout else -1 for k in slots]
-
-
-def check_pairs(users, items, labels, user_num: int, item_num: int, max_pairs: int = NCF_TRAIN_MAX_PAIRS):
-    """(users int64 [n], items int64 [n], labels fp32 [n]) as the kernels read them; ValueError for shapes that differ, n outside
-    [1, max_pairs] and ids outside the tables (the kernels read the tables by them unchecked)."""
-    users, items = np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int64)
-    labels = np.ascontiguousarray(labels, dtype=np.float32)
-    n = len(users)
-    if users.ndim != 1 or items.shape != (n,) or labels.shape != (n,):
-        raise ValueError(f"ncf_train: users {users.shape}, items {items.shape} and labels {labels.shape} must be one [n]")
-    if not 1 <= n <= max_pairs:
-        raise ValueError(f"ncf_train: n = {n} pairs outside [1, {max_pairs}]")
-    if users.min() < 0 or users.max() >= user_num:
-        raise ValueError(f"ncf_train: users in [{int(users.min())}, {int(users.max())}] outside the model's [0, {user_num})")
-    if items.min() < 0 or items.max() >= item_num:
-        raise ValueError(f"ncf_train: items in [{int(items.min())}, {int(items.max())}] outside the table's [0, {item_num})")
-    return users, items, labels
-
-
-def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False):
-    """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
-    `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
-    model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
-    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order.
-    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule."""
-    w = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
-    factor, num_layers, kind, d = head_shape(w)
-    table = np.asarray(table).astype(dtype)
-    users, items, y = check_pairs(users, items, labels, len(w["mlp_user_embeddings.weight"]), len(table), max_pairs=1 << 40)
-    y = y.astype(dtype)
-    n = len(users)
-    one = dtype(1)
-    hs = [np.concatenate([w["mlp_user_embeddings.weight"][users], table[items]], axis=1)]
-    for i in range(num_layers):
-        hs.append(np.maximum(hs[-1] @ w[f"mlp_layers.{i}.linear.weight"].T + w[f"mlp_layers.{i}.linear.bias"], 0))
-    feat = hs[-1]
-    if kind == "NeuMF-end":
-        gu, gi = w["gmf_user_embeddings.weight"][users], w["gmf_item_embeddings.weight"][items]
-        feat = np.concatenate([gu * gi, feat], axis=1)
-    wp = w["predict_layer.weight"].reshape(-1)
-    z = feat @ wp + w["predict_layer.bias"][0]
-    e = np.exp(-np.abs(z))
-    loss = (np.maximum(z, 0) - z * y + np.log1p(e)).sum(dtype=dtype) / dtype(n)
-    dl = (np.where(z >= 0, one / (one + e), e / (one + e)) - y) / dtype(n)
-    grads = {"predict_layer.weight": (dl @ feat).reshape(1, -1), "predict_layer.bias": dl.sum(dtype=dtype).reshape(1)}
-    dfeat = dl[:, None] * wp[None, :]
-    if kind == "NeuMF-end":
-        dg, dh = dfeat[:, :factor], dfeat[:, factor:]
-        grads["gmf_user_embeddings.weight"] = np.zeros_like(w["gmf_user_embeddings.weight"])
-        grads["gmf_item_embeddings.weight"] = np.zeros_like(w["gmf_item_embeddings.weight"])
-        np.add.at(grads["gmf_user_embeddings.weight"], users, dg * gi)
-        np.add.at(grads["gmf_item_embeddings.weight"], items, dg * gu)
-    else:
-        dh = dfeat
-    for i in reversed(range(num_layers)):
-        dz = dh * (hs[i + 1] > 0)
-        grads[f"mlp_layers.{i}.linear.weight"] = dz.T @ hs[i]
-        grads[f"mlp_layers.{i}.linear.bias"] = dz.sum(axis=0, dtype=dtype)
-        dh = dz @ w[f"mlp_layers.{i}.linear.weight"]
-    grads["mlp_user_embeddings.weight"] = np.zeros_like(w["mlp_user_embeddings.weight"])
-    np.add.at(grads["mlp_user_embeddings.weight"], users, dh[:, :d])
-    if table_grad:
-        grads[TABLE_KEY] = np.zeros_like(table)
-        np.add.at(grads[TABLE_KEY], items, dh[:, d:])
-    assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype
-    return dtype(loss), z, grads
-
-
 def ng_sample(pairs, num_user: int, num_item: int, num_ng: int, seed: int, chunk: int = 1024):
     """The training pairs of one epoch as the reference draws them (NCFDataset(pairs, ..., is_training=True).ng_sample() after
     np.random.seed(seed), pmgt/ncf/datasets.py:85-101): the positives first, in the given order, then for each positive `num_ng` negatives,
@@ -193,17 +81,6 @@ def normalize_item_table(table):
 
 
 # ---- device side ------------------------------------------------------------------------------------------------------------------------------
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class NcfTrainC(C.Structure):
-    """pmgt_ncf_train (include/pmgt_capi.h)."""
-    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("reserved", C.c_int), ("user_num", C.c_int64),
-                ("item_num", C.c_int64), ("table", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p)]
-
-
 class NcfHeadGrad:
     """pmgt_ncf_train_grad over one flat parameter buffer and one frozen table: __call__(users, items, labels) writes `grads` whole and
     returns (loss [1], logits [n]) as device tensors.  Two launches; nothing is copied to the host, nothing waits.  `params` and `grads` are
@@ -213,12 +90,12 @@ class NcfHeadGrad:
 
     def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads, table_grad=None):
         import torch
-        from . import _lib
         self.lib = _lib.hip()
         self.layout, self.count = head_layout(factor_num, num_layers, kind, user_num, int(table.shape[0]) if table.dim() == 2 else 0)
         self.d = factor_num << (num_layers - 1)
-        if not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != self.d or not table.is_contiguous():
-            raise ValueError(f"ncf_train: the item table {tuple(table.shape)} must be a contiguous fp32 device tensor [I, d = {self.d}]")
+        check_item_table(table, None, self.d, None, "ncf_train")
+        if not table.is_contiguous():
+            raise ValueError("ncf_train: the item table must be contiguous")
         for name, t in (("params", params), ("grads", grads)):
             if t.dtype != torch.float32 or t.device != table.device or tuple(t.shape) != (self.count,) or not t.is_contiguous():
                 raise ValueError(f"ncf_train: {name} must be a contiguous fp32 tensor [{self.count}] on the table's device")
@@ -228,11 +105,7 @@ class NcfHeadGrad:
         self.table, self.params, self.grads, self.table_grad = table, params, grads, table_grad
         self.shape = (factor_num, num_layers, _lib.NCF_KINDS.index(kind))
         self.user_num, self.item_num = int(user_num), int(table.shape[0])
-        h = NcfTrainC()
-        h.factor_num, h.num_layers, h.kind = self.shape
-        h.user_num, h.item_num = self.user_num, self.item_num
-        h.table, h.params, h.grads = table.data_ptr(), params.data_ptr(), grads.data_ptr()
-        self._head = h
+        self._head = NcfTrainC(*self.shape, 0, self.user_num, self.item_num, table.data_ptr(), params.data_ptr(), grads.data_ptr())
         offs = (C.c_int64 * NCF_TRAIN_TENSORS)()
         count = int(self.lib.pmgt_ncf_train_layout(*self.shape, self.user_num, self.item_num, offs))
         if count != self.count or list(offs) != layout_slots(self.layout):
@@ -253,7 +126,6 @@ class NcfHeadGrad:
 
     def __call__(self, users, items, labels, loss=None, logits=None):
         import torch
-        from . import _lib
         n = int(users.shape[0])
         dev = self.table.device
         for t, dt in ((users, torch.int64), (items, torch.int64), (labels, torch.float32)):
@@ -264,15 +136,10 @@ class NcfHeadGrad:
         logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
         front = (C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(), logits.data_ptr())
         if self.table_grad is None:
-            _lib.check(self.lib.pmgt_ncf_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _stream()))
+            _lib.check(self.lib.pmgt_ncf_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
         else:
-            _lib.check(self.lib.pmgt_ncf_train_grad_table(*front, self.table_grad.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()))
+            _lib.check(self.lib.pmgt_ncf_train_grad_table(*front, self.table_grad.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
         return loss, logits
-
-
-def head_state(model) -> dict:
-    """The head's entries of a PMGT_NCF's state_dict (what head_layout names)."""
-    return {k: v for k, v in model.state_dict().items() if k.startswith(HEAD_PREFIXES)}
 
 
 class NcfHeadTrainer:
@@ -296,9 +163,7 @@ class NcfHeadTrainer:
             raise ValueError("ncf_train: dropout in the head is not covered (emb_dropout and every layer's dropout must be 0)")
         check_head_covered(model.factor_num, model.num_layers, model.model)
         dev = model.mlp_user_embeddings.weight.device
-        d = model.factor_num << (model.num_layers - 1)
-        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (model.item_num, d) or table.device != dev:
-            raise ValueError(f"ncf_train: the item table must be an fp32 tensor [{model.item_num}, {d}] on {dev}")
+        check_item_table(table, model.item_num, model.factor_num << (model.num_layers - 1), dev, "ncf_train")
         self.model, self.train_table = model, bool(train_table)
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
         self.max_grad_norm = float(max_grad_norm or 0.0)
@@ -336,12 +201,11 @@ class NcfHeadTrainer:
     def step(self, users, items, labels, loss=None):
         """One optimizer step on the pairs (device tensors: int64 [n], int64 [n], fp32 [n]; ids inside the tables, check_pairs checks them on
         the host) -> the loss before the step as a device tensor [1].  Five launches enqueued; no host copy, no synchronisation."""
-        from . import _lib
         loss, _ = self.grad_fn(users, items, labels, loss=loss, logits=self._logits(int(users.shape[0])))
         _lib.check(self.grad_fn.lib.pmgt_op_adamw(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
                                                   self.exp_avg_sq.data_ptr(), self.decay.data_ptr(), self.count, self.lr, self.weight_decay,
                                                   self.betas[0], self.betas[1], self.eps, self.max_grad_norm, self.step_count.data_ptr(),
-                                                  self._scal.data_ptr(), self._part.data_ptr(), _stream()))
+                                                  self._scal.data_ptr(), self._part.data_ptr(), _lib.stream()))
         return loss
 
     def _logits(self, n: int):
@@ -413,7 +277,7 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
     `table` IS OVERWRITTEN -- recommend(table=table) and evaluate_ranking(table=table) then read the trained rows.
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
     import torch
-    from .evaluation import rank_users
+    from .evaluation import check_candidates, rank_users
     from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, monitor_of
     from .metrics import RankingMetrics
     if early_criterion not in ("n20", "r20", "loss"):
@@ -422,18 +286,12 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
         raise ValueError(f"fit_ncf: batch_size = {batch_size} outside [1, {NCF_TRAIN_MAX_PAIRS}] or max_epochs = {max_epochs} below 1")
     pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
     check_pairs(pairs[:, 0], pairs[:, 1], np.ones(len(pairs), np.float32), model.user_num, model.item_num, max_pairs=1 << 40)
-    v_users, v_cand = np.ascontiguousarray(valid[0], dtype=np.int64), np.ascontiguousarray(valid[1], dtype=np.int64)
-    v_labels, v_counts = np.ascontiguousarray(valid[2], dtype=np.float32), np.ascontiguousarray(valid[3], dtype=np.int32)
-    n_valid, width = v_cand.shape
-    if v_users.shape != (n_valid,) or v_labels.shape != (n_valid, width) or v_counts.shape != (n_valid,) or n_valid < 1:
-        raise ValueError("fit_ncf: valid must be (users [U], candidates [U, C], labels [U, C], counts [U])")
-    if v_users.min() < 0 or v_users.max() >= model.user_num or v_cand.min() < 0 or v_cand.max() >= model.item_num:
-        raise ValueError("fit_ncf: validation users or candidates outside the model's tables")
+    valid = check_candidates(model, *valid, "fit_ncf: validation")
     trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
                              train_table=train_table)
     dev = trainer.params.device
-    on_dev = [torch.from_numpy(a).to(dev) for a in (v_users, v_cand, v_labels, v_counts)]
-    metrics = RankingMetrics(dev, n_valid, (10, 20))
+    on_dev = [torch.from_numpy(a).to(dev) for a in valid]
+    metrics = RankingMetrics(dev, len(valid[0]), (10, 20))
     monitor, mode = monitor_of(early_criterion)
     stopper = EarlyStopping(monitor, patience, mode)
     keeper = BestCheckpoint(ckpt_dir or "", monitor, mode)

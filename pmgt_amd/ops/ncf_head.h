@@ -1,0 +1,25 @@
+// What ncf_score.hip and ncf_train.hip share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU, the covered heads.
+#pragma once
+#include "../csrc/common.h"
+#include "../../include/pmgt_capi.h"
+
+namespace pmgt {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+static constexpr int NCF_MAX_D = 256;      // the widest layer-0 half: d = factor_num * 2^(num_layers - 1)
+
+// relu that keeps a NaN (fmaxf would return 0 and hide a broken table from the NaN check of the selection)
+__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
+__device__ __forceinline__ int rho(int g) { return (g & 3) + 8 * (g >> 2); }
+
+// the covered heads -> 0 and *d, or -2 with the error set in the name of the entry `who`
+inline int ncf_head_check(int factor_num, int num_layers, int kind, const char* who, int* d) {
+    PMGT_CHECK(factor_num == 8 || factor_num == 16 || factor_num == 32 || factor_num == 64, -2, "%s: factor_num = %d, covered: 8, 16, 32, 64", who, factor_num);
+    PMGT_CHECK(num_layers >= 1 && num_layers <= PMGT_NCF_MAX_LAYERS, -2, "%s: num_layers = %d outside [1, %d]", who, num_layers, PMGT_NCF_MAX_LAYERS);
+    *d = factor_num << (num_layers - 1);
+    PMGT_CHECK(*d <= NCF_MAX_D, -2, "%s: d = factor_num * 2^(num_layers - 1) = %d above %d", who, *d, NCF_MAX_D);
+    PMGT_CHECK(kind == PMGT_NCF_MLP || kind == PMGT_NCF_NEUMF_END, -2, "%s: unknown model kind %d", who, kind);
+    return 0;
+}
+
+}  // namespace pmgt

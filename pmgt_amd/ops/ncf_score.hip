@@ -20,16 +20,13 @@
 // LDS buffer in chunks of 32 k-columns ([out][33] floats: 16.5 KiB for the 128 x 256 layer whose 128 KiB would not fit beside the tile); the
 // next chunk's global loads are issued before the MFMAs of the current one and stored after them.
 // num_layers = 1 has no layer past the split one: relu(Pu + Pi) goes straight into the predict dot product (a VALU kernel, one pair a thread).
-#include "../csrc/common.h"
-#include "../../include/pmgt_capi.h"
+#include "ncf_head.h"
 
 namespace pmgt {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 static constexpr int NCF_THREADS = 256, NCF_WAVES = 4, NCF_ITEMS = 32;      // one workgroup: 4 waves, 32 items
 static constexpr int NCF_CHUNK = 32, NCF_CHUNK_STRIDE = NCF_CHUNK + 1;      // k-columns of one weight chunk, its LDS row stride
-static constexpr int NCF_MAX_D = 256, NCF_MAX_LAYERS = PMGT_NCF_MAX_LAYERS;
+static constexpr int NCF_MAX_LAYERS = PMGT_NCF_MAX_LAYERS;
 
 struct NcfArgs {
     const float* w[NCF_MAX_LAYERS];      // [i]: mlp_layers[i].linear.weight [d >> i][d >> (i - 1)]; [0] is never read (the caller's split)
@@ -45,10 +42,6 @@ struct NcfArgs {
     int64_t row_stride, user_num;
     int n, n_items, d, factor, num_layers, item_tiles;
 };
-
-// relu that keeps a NaN (fmaxf would return 0 and hide a broken table from the NaN check of the selection)
-__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
-__device__ __forceinline__ int rho(int g) { return (g & 3) + 8 * (g >> 2); }
 
 // rows [0, 32 NBO) x k-columns [k0, k0 + 32) of W [M][K], zero past M and K: global -> registers, registers -> LDS [m][33]
 template <int NBO> __device__ __forceinline__ void chunk_fetch(float (&st)[NBO * 4], const float* __restrict__ W, int M, int K, int k0, int tid) {
@@ -285,11 +278,8 @@ extern "C" int pmgt_ncf_score(const pmgt_ncf_head* head, const float* pu, const 
                               float* scores, int64_t row_stride, void* stream) {
     PMGT_CHECK(head != nullptr, -2, "pmgt_ncf_score: NULL head");
     const int F = head->factor_num, L = head->num_layers;
-    PMGT_CHECK(F == 8 || F == 16 || F == 32 || F == 64, -2, "pmgt_ncf_score: factor_num = %d, covered: 8, 16, 32, 64", F);
-    PMGT_CHECK(L >= 1 && L <= NCF_MAX_LAYERS, -2, "pmgt_ncf_score: num_layers = %d outside [1, %d]", L, NCF_MAX_LAYERS);
-    const int d = F << (L - 1);
-    PMGT_CHECK(d <= NCF_MAX_D, -2, "pmgt_ncf_score: d = factor_num * 2^(num_layers - 1) = %d above %d", d, NCF_MAX_D);
-    PMGT_CHECK(head->kind == PMGT_NCF_MLP || head->kind == PMGT_NCF_NEUMF_END, -2, "pmgt_ncf_score: unknown model kind %d", head->kind);
+    int d;
+    if (int rc = ncf_head_check(F, L, head->kind, "pmgt_ncf_score", &d)) return rc;
     const bool neumf = head->kind == PMGT_NCF_NEUMF_END;
     PMGT_CHECK(n >= 1 && n <= PMGT_NCF_MAX_USERS, -2, "pmgt_ncf_score: n = %lld users outside [1, %d]", (long long)n, PMGT_NCF_MAX_USERS);
     PMGT_CHECK(n_items >= 1 && n_items <= 0x7FFFFFFELL, -2, "pmgt_ncf_score: %lld items outside [1, 2^31 - 2]", (long long)n_items);

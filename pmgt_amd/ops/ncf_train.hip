@@ -32,14 +32,11 @@
 //          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.  The item kind sums the GMF item rows (NeuMF-end)
 //          and, for a trained table, the item half of dx by the same rule.
 // DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
-#include "../csrc/common.h"
-#include "../../include/pmgt_capi.h"
+#include "ncf_head.h"
 
 namespace pmgt {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-static constexpr int NT_THREADS = 256, NT_WAVES = 4, NT_TILE = 32, NT_MAX_LAYERS = PMGT_NCF_MAX_LAYERS, NT_MAX_D = 256;
+static constexpr int NT_THREADS = 256, NT_WAVES = 4, NT_TILE = 32, NT_MAX_LAYERS = PMGT_NCF_MAX_LAYERS;
 static constexpr int NT_ZERO_BLOCKS = 1024, NT_MAX_TASKS = NT_MAX_LAYERS + 1;
 
 struct NtLayer {
@@ -92,7 +89,6 @@ struct NtGradsArgs {
     int n, d, factor, neumf, ntasks, weight_blocks, row_blocks;      // row_blocks per kind (user, item)
 };
 
-__device__ __forceinline__ int rho(int g) { return (g & 3) + 8 * (g >> 2); }
 __device__ __forceinline__ float4 ld4(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
@@ -129,10 +125,10 @@ __device__ __forceinline__ void forward_layer(const float* __restrict__ W, const
         for (int q = 0; q < 4; ++q) {
             const int f = mb * 32 + 8 * q + 4 * h;
             float4 v;
-            v.x = acc[4 * q] < 0.f ? 0.f : acc[4 * q];      // (keeps a NaN, as ncf_score.hip does)
-            v.y = acc[4 * q + 1] < 0.f ? 0.f : acc[4 * q + 1];
-            v.z = acc[4 * q + 2] < 0.f ? 0.f : acc[4 * q + 2];
-            v.w = acc[4 * q + 3] < 0.f ? 0.f : acc[4 * q + 3];
+            v.x = relu_keep_nan(acc[4 * q]);
+            v.y = relu_keep_nan(acc[4 * q + 1]);
+            v.z = relu_keep_nan(acc[4 * q + 2]);
+            v.w = relu_keep_nan(acc[4 * q + 3]);
             if (valid && f < M) *reinterpret_cast<float4*>(act_row + f) = v;
         }
     }
@@ -388,12 +384,8 @@ struct NtShape {
 };
 
 static int nt_shape(int factor_num, int num_layers, int kind, int64_t user_num, int64_t item_num, const char* who, NtShape* s) {
-    PMGT_CHECK(factor_num == 8 || factor_num == 16 || factor_num == 32 || factor_num == 64, -2, "%s: factor_num = %d, covered: 8, 16, 32, 64", who,
-               factor_num);
-    PMGT_CHECK(num_layers >= 1 && num_layers <= NT_MAX_LAYERS, -2, "%s: num_layers = %d outside [1, %d]", who, num_layers, NT_MAX_LAYERS);
-    const int d = factor_num << (num_layers - 1);
-    PMGT_CHECK(d <= NT_MAX_D, -2, "%s: d = factor_num * 2^(num_layers - 1) = %d above %d", who, d, NT_MAX_D);
-    PMGT_CHECK(kind == PMGT_NCF_MLP || kind == PMGT_NCF_NEUMF_END, -2, "%s: unknown model kind %d", who, kind);
+    int d;
+    if (int rc = ncf_head_check(factor_num, num_layers, kind, who, &d)) return rc;
     PMGT_CHECK(user_num >= 1 && user_num <= 0x7FFFFFFELL, -2, "%s: user_num = %lld outside [1, 2^31 - 2]", who, (long long)user_num);
     PMGT_CHECK(item_num >= 1 && item_num <= 0x7FFFFFFELL, -2, "%s: item_num = %lld outside [1, 2^31 - 2]", who, (long long)item_num);
     *s = NtShape{factor_num, num_layers, d, kind == PMGT_NCF_NEUMF_END, user_num, item_num};

@@ -5,18 +5,17 @@ materialising pair rows (pmgt_ncf_score), and a second kernel selects per row (p
 
 THE ORDER is that of the ranking metrics: descending `score_key`, and among equal keys THE LOWER ITEM INDEX FIRST.
 
-The pure-numpy part (topk_host, ncf_head_host, exclusion_csr) needs no GPU and is the yardstick of the kernels."""
+The pure-numpy part (topk_host, exclusion_csr) needs no GPU; the head (its shape, the covered heads, ncf_head_host) is stated in ncf_head.py."""
 import ctypes as C
 
 import numpy as np
 
+from . import _lib
+from ._lib import NCF_FACTORS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_MAX_USERS, TOPK_FLAG_NAN, TOPK_FLAG_SHORT, TOPK_MAX_K  # noqa: F401
 from .evaluation import score_key
+from .ncf_head import check_head_covered, check_ids, check_item_table, head_shape, head_state, ncf_head_host  # noqa: F401
 
-TOPK_MAX_K = 1024                                # PMGT_TOPK_MAX_K
-TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1, 2            # PMGT_TOPK_FLAG_*
 SCORE_WORKSPACE_BYTES = 256 << 20                # recommend(batch_users=None): the [batch, I] fp32 score rows stay within this
-NCF_FACTORS, NCF_MAX_LAYERS, NCF_MAX_D = (8, 16, 32, 64), 4, 256      # what pmgt_ncf_score covers
-NCF_MAX_USERS = 1 << 20                          # PMGT_NCF_MAX_USERS: users per pmgt_ncf_score call
 
 
 # ---- host side: pure numpy ------------------------------------------------------------------------------------------------------------------
@@ -35,29 +34,24 @@ def check_csr(indptr, items, user_num: int, item_num: int):
         raise ValueError(f"exclude: indptr {indptr.shape} must be [user_num + 1 = {user_num + 1}] and items one-dimensional")
     if indptr[0] != 0 or indptr[-1] != len(items64) or (np.diff(indptr) < 0).any():
         raise ValueError("exclude: indptr must be non-decreasing from 0 to len(items)")
-    if len(items64) and (items64.min() < 0 or items64.max() >= item_num):
-        raise ValueError(f"exclude: excluded items in [{int(items64.min())}, {int(items64.max())}] outside the model's [0, {item_num})")
+    check_ids("excluded items", items64, item_num, "exclude")
     return indptr, items64.astype(np.int32)
 
 
 def exclusion_csr(exclude, user_num: int, item_num: int):
     """The exclusion CSR over user ids from `exclude`: None (nothing excluded), an iterable of (user, item) pairs -- typically the training
     interactions --, or a ready (indptr, items) pair of arrays.  -> (indptr int64 [user_num + 1], items int32), each list sorted by item."""
-    if exclude is None:
-        return np.zeros(user_num + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
     if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in exclude) \
             and len(exclude[0]) == user_num + 1:
         return check_csr(exclude[0], exclude[1], user_num, item_num)
-    pairs = np.asarray(list(exclude) if not isinstance(exclude, np.ndarray) else exclude)
+    pairs = np.asarray(exclude if isinstance(exclude, np.ndarray) else list(exclude or ()))
     if pairs.size == 0:
         return np.zeros(user_num + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
     if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
         raise ValueError(f"exclude: expected (user, item) integer pairs, got an array of shape {pairs.shape} and dtype {pairs.dtype}")
     pairs = pairs.astype(np.int64)
-    if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= user_num:
-        raise ValueError(f"exclude: users in [{int(pairs[:, 0].min())}, {int(pairs[:, 0].max())}] outside the model's [0, {user_num})")
-    if pairs[:, 1].min() < 0 or pairs[:, 1].max() >= item_num:
-        raise ValueError(f"exclude: excluded items in [{int(pairs[:, 1].min())}, {int(pairs[:, 1].max())}] outside the model's [0, {item_num})")
+    check_ids("users", pairs[:, 0], user_num, "exclude")
+    check_ids("excluded items", pairs[:, 1], item_num, "exclude")
     order = np.lexsort((pairs[:, 1], pairs[:, 0]))
     indptr = np.zeros(user_num + 1, dtype=np.int64)
     np.cumsum(np.bincount(pairs[:, 0], minlength=user_num), out=indptr[1:])
@@ -94,61 +88,7 @@ def topk_host(scores, k: int, indptr=None, items=None, users=None):
     return out_items, out_scores, flags
 
 
-def head_shape(weights: dict):
-    """(factor_num, num_layers, kind, d) of a head given as a state_dict-keyed mapping."""
-    num_layers = 0
-    while f"mlp_layers.{num_layers}.linear.weight" in weights:
-        num_layers += 1
-    if num_layers < 1:
-        raise ValueError("the head has no mlp_layers.0.linear.weight")
-    d = int(weights["mlp_user_embeddings.weight"].shape[1])
-    kind = "NeuMF-end" if weights.get("gmf_user_embeddings.weight") is not None else "MLP"
-    return d >> (num_layers - 1), num_layers, kind, d
-
-
-def ncf_head_host(weights: dict, users, table, dtype=np.float64) -> np.ndarray:
-    """PMGT_NCF.head in eval mode on plain arrays, every user of `users` against every row of `table` [I, d] -> logits [len(users), I] in
-    `dtype`.  `weights` is keyed like the model's state_dict ("mlp_user_embeddings.weight", "mlp_layers.<i>.linear.weight" / ".bias",
-    "predict_layer.weight" / ".bias" and, for NeuMF-end, "gmf_user_embeddings.weight" / "gmf_item_embeddings.weight"); arrays or CPU
-    tensors.  The formula as the torch head states it: layer 0 on the UNSPLIT concatenation [user ; item]."""
-    w = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
-    _, num_layers, kind, d = head_shape(w)
-    users = np.asarray(users, dtype=np.int64)
-    table = np.asarray(table).astype(dtype)
-    n, n_items = len(users), len(table)
-    out = np.empty((n, n_items), dtype=dtype)
-    per = max(1, (1 << 22) // (n_items * 2 * d))             # users per chunk of pair rows: about 4 M elements of layer 0's input
-    for lo in range(0, n, per):
-        u = users[lo: lo + per]
-        m = len(u)
-        h = np.concatenate([np.repeat(w["mlp_user_embeddings.weight"][u], n_items, axis=0), np.tile(table, (m, 1))], axis=1)
-        for i in range(num_layers):
-            h = np.maximum(h @ w[f"mlp_layers.{i}.linear.weight"].T + w[f"mlp_layers.{i}.linear.bias"], 0)
-        if kind == "NeuMF-end":
-            gmf = np.repeat(w["gmf_user_embeddings.weight"][u], n_items, axis=0) * np.tile(w["gmf_item_embeddings.weight"][:n_items], (m, 1))
-            h = np.concatenate([gmf, h], axis=1)
-        out[lo: lo + m] = (h @ w["predict_layer.weight"].T + w["predict_layer.bias"]).reshape(m, n_items)
-    return out
-
-
-def check_head_covered(factor_num: int, num_layers: int, kind: str) -> None:
-    """ValueError naming the limit when pmgt_ncf_score does not cover the head."""
-    if kind not in ("MLP", "NeuMF-end"):
-        raise ValueError(f"ncf_score: model kind {kind!r}, covered: 'MLP', 'NeuMF-end'")
-    if factor_num not in NCF_FACTORS:
-        raise ValueError(f"ncf_score: factor_num = {factor_num}, covered: {NCF_FACTORS}")
-    if not 1 <= num_layers <= NCF_MAX_LAYERS:
-        raise ValueError(f"ncf_score: num_layers = {num_layers} outside [1, {NCF_MAX_LAYERS}]")
-    if factor_num << (num_layers - 1) > NCF_MAX_D:
-        raise ValueError(f"ncf_score: d = factor_num * 2^(num_layers - 1) = {factor_num << (num_layers - 1)} above {NCF_MAX_D}")
-
-
 # ---- device side ------------------------------------------------------------------------------------------------------------------------------
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class NcfScorer:
     """The fused head over one item table: NcfScorer(weights, table) splits layer 0 and computes the per-item half Pi = table W0e^T + b0
     once; score(users) computes the per-user half Pu = U_mlp[users] W0u^T (a torch matmul: plumbing) and launches pmgt_ncf_score.
@@ -157,21 +97,19 @@ class NcfScorer:
 
     def __init__(self, weights: dict, table):
         import torch
-        from . import _lib
         self.lib = _lib.hip()
         self.factor, self.num_layers, self.kind, self.d = head_shape(weights)
         check_head_covered(self.factor, self.num_layers, self.kind)
         need = ["mlp_user_embeddings.weight", "predict_layer.weight", "predict_layer.bias"]
         need += [f"mlp_layers.{i}.linear.{p}" for i in range(self.num_layers) for p in ("weight", "bias")]
         need += ["gmf_user_embeddings.weight", "gmf_item_embeddings.weight"] if self.kind == "NeuMF-end" else []
+        check_item_table(table, None, self.d, None, "ncf_score")
         self.w = {}
         for key in need:
             t = weights[key]
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != table.device or not t.is_cuda:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != table.device:
                 raise ValueError(f"ncf_score: {key} must be an fp32 tensor on the table's device")
             self.w[key] = t.detach().contiguous()
-        if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != self.d or table.shape[0] < 1:
-            raise ValueError(f"ncf_score: the item table {tuple(table.shape)} must be fp32 [I >= 1, d = {self.d}]")
         self.n_items = int(table.shape[0])
         self.user_num = int(self.w["mlp_user_embeddings.weight"].shape[0])
         w0 = self.w["mlp_layers.0.linear.weight"]
@@ -195,7 +133,6 @@ class NcfScorer:
         """users int64 [n] on the device (ids in [0, user_num): the caller checks them on the host) -> scores fp32 [n, row_stride] with the logit
         of (users[r], item j) at [r, j]; `out` (fp32, contiguous, [>= n, row_stride >= I]) is written in place and entries [r, I ..) are left."""
         import torch
-        from . import _lib
         n = int(users.shape[0])
         if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.pi.device or not users.is_contiguous() or n < 1:
             raise ValueError("ncf_score: users must be a contiguous int64 tensor [n >= 1] on the table's device")
@@ -206,7 +143,7 @@ class NcfScorer:
             raise ValueError(f"ncf_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
         pu = self.w["mlp_user_embeddings.weight"].index_select(0, users) @ self._w0u_t
         _lib.check(self.lib.pmgt_ncf_score(C.byref(self._head), pu.data_ptr(), self.pi.data_ptr(), users.data_ptr(), n, self.n_items,
-                                           out.data_ptr(), int(out.shape[1]), _stream()))
+                                           out.data_ptr(), int(out.shape[1]), _lib.stream()))
         return out
 
 
@@ -217,7 +154,6 @@ class TopkRows:
 
     def __init__(self, device, max_rows: int, n_items: int, k: int, indptr=None, items=None, user_num: int = 0):
         import torch
-        from . import _lib
         self.lib = _lib.hip()
         self.device = torch.device(device)
         self.k, self.max_rows, self.n_items = check_k(k), int(max_rows), int(n_items)
@@ -244,12 +180,11 @@ class TopkRows:
         if out is None:
             out = (torch.empty(n, self.k, dtype=torch.int32, device=self.device), torch.empty(n, self.k, dtype=torch.float32, device=self.device),
                    torch.empty(n, dtype=torch.int32, device=self.device))
-        from . import _lib
         excl = self._indptr is not None
         _lib.check(self.lib.pmgt_topk_rows(scores.data_ptr(), stride, n, self.n_items, self.k, users.data_ptr() if excl else 0,
                                            self._indptr.data_ptr() if excl else 0, self._items.data_ptr() if excl and len(self._items) else 0,
                                            self.user_num if excl else 0, len(self._items) if excl else 0, self._ws.data_ptr(),
-                                           out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()))
+                                           out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _lib.stream()))
         return out
 
 
@@ -296,8 +231,7 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     users = np.ascontiguousarray(users, dtype=np.int64)
     if users.ndim != 1 or len(users) < 1:
         raise ValueError(f"recommend: users {users.shape} must be [U >= 1]")
-    if users.min() < 0 or users.max() >= model.user_num:
-        raise ValueError(f"recommend: users in [{int(users.min())}, {int(users.max())}] outside the model's [0, {model.user_num})")
+    check_ids("users", users, model.user_num, "recommend")
     indptr, excl = exclusion_csr(exclude, model.user_num, model.item_num)
     if impl == "device":
         check_head_covered(model.factor_num, model.num_layers, model.model)
@@ -315,8 +249,7 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
         finally:
             model.train(was_training)
     dev = model.engine.device
-    if tuple(table.shape) != (n_items, model.config.hidden_size) or table.dtype != torch.float32 or table.device != dev:
-        raise ValueError(f"recommend: table must be fp32 [{n_items}, {model.config.hidden_size}] on {dev}")
+    check_item_table(table, n_items, model.config.hidden_size, dev, "recommend")
     if impl == "host":
         was_training = model.training
         model.eval()
@@ -327,7 +260,7 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
         items, scores, flags = topk_host(s, k, indptr, excl, users)
     else:
         with torch.no_grad():
-            scorer = NcfScorer({key: v for key, v in model.state_dict().items() if not key.startswith(("bert.", "feat_embeddings."))}, table)
+            scorer = NcfScorer(head_state(model), table)
             picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
             users_d = torch.from_numpy(users).to(dev)
             out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
