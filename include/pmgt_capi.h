@@ -410,6 +410,36 @@ int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const 
 int64_t pmgt_ncf_train_table_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n);
 int pmgt_ncf_train_grad_table(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
                               float* loss, float* logits, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream);
+/* THE HEAD TRAINED WITH DROPOUT (PMGT_NCF.head in training mode: a Dropout behind every Linear, emb_dropout on the concatenated
+ * [user ; item] input and on the GMF product; every config/hpo/hpo_ncf_*_params.yaml searches both p over [0, 0.8]).  With m = 0 or
+ * 1 / (1 - p), drawn per element:
+ *   x0 = m_e [mlp_user[u] ; table[i]],   h(l+1) = relu(m_l (W_l h_l + b_l)),   NeuMF-end: g = m_g (gmf_user[u] * gmf_item[i]),
+ * m_e and m_g at p_emb (two masks of their own), m_l at p_layer[l]; everything else as pmgt_ncf_train_grad states it, and the gradients are
+ * those of this function: d x0 carries m_e down to the embedding rows (and to table_grad), the ReLU passes where the DROPPED activation is
+ * > 0 with the factor 1 / (1 - p_l).  THE MASKS come from the engine's counter-based RNG (make_drop_key / drop_keep4: one hash pair
+ * decides 4 neighbouring columns, an element is kept when its 16-bit lane >= thr >> 16, thr = (uint32)(p 2^32); the scale is the fp32
+ * value 1 / (1 - p)) over `rng`, a device {seed, step} pair of the caller's own, read by the kernels: a captured call replays with fresh
+ * masks when an earlier kernel advances the step (pmgt_op_adamw does).  A site's ROW is the pair's index within the call, its COLUMN the
+ * feature; the SITE IDS (constants of ops/ncf_head.h, mirrored in _lib.py), distinct from each other (the pair is the caller's, so they
+ * need not avoid the engine's):
+ *   NCF_SITE_EMB   64       [n][2 d], the user half first
+ *   NCF_SITE_GMF   65       [n][factor_num]
+ *   NCF_SITE_LAYER 72 + l   [n][d >> l], the output of layer l
+ * so the test entry pmgt_op_dropout_keep with (rng, p, site, n, cols) writes exactly the decisions a call draws, and the call is a pure function of
+ * (inputs, seed, step).  table_grad NULL: the table is frozen (pmgt_ncf_train_grad's outputs and workspace); else it is trained
+ * (pmgt_ncf_train_grad_table's).  Still two launches, no atomic, no sync, no allocation, the gradient buffers written whole, the same
+ * workspace sizes.  With every p equal to 0 the call runs the kernels of the two entries above: the same bits, `rng` not read.
+ * Refused (-2) before anything is launched: what those entries refuse, a NULL drop, a p_emb or p_layer[l < num_layers] that is NaN or
+ * outside [0, 1), and any p > 0 with a NULL or 8-byte-misaligned rng.
+ * Added without a bump of pmgt_abi_version(): one struct, one entry, nothing existing moved. */
+typedef struct pmgt_ncf_dropout {
+    const uint64_t* rng;                          /* device {seed, step}; read only when a p is > 0 */
+    float p_emb;                                  /* emb_dropout.p: the input of layer 0 and the GMF product */
+    float p_layer[PMGT_NCF_MAX_LAYERS];           /* mlp_layers[l].dropout.p */
+} pmgt_ncf_dropout;
+int pmgt_ncf_train_grad_dropout(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                                float* loss, float* logits, float* table_grad /* NULL: frozen table */, const pmgt_ncf_dropout* drop,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average

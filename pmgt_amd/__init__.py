@@ -2,7 +2,8 @@
 from .configuration_pmgt import PMGTConfig  # noqa: F401
 # (binds the name `recommend` to the function: the submodule stays reachable as `from pmgt_amd.recommend import ...`)
 from .recommend import ncf_head_host, recommend, topk_host  # noqa: F401
-from .ncf_train import NcfHeadTrainer, fit_ncf, ncf_head_grad_host, ng_sample, normalize_item_table  # noqa: F401
+from .ncf_train import (NcfHeadTrainer, fit_ncf, ncf_dropout_keep, ncf_dropout_masks, ncf_head_grad_host, ng_sample,  # noqa: F401
+                        normalize_item_table)
 
 __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_grad_host", "ng_sample", "NcfHeadTrainer", "fit_ncf",
-           "normalize_item_table"]
+           "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks"]

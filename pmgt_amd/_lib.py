@@ -91,10 +91,16 @@ class NcfTrainC(C.Structure):
                 ("item_num", C.c_int64), ("table", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p)]
 
 
+class NcfDropoutC(C.Structure):
+    """pmgt_ncf_dropout (include/pmgt_capi.h): rng = the device {seed, step} pair."""
+    _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_layer", C.c_float * 4)]
+
+
 NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
 NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
 NCF_FACTORS, NCF_MAX_D = (8, 16, 32, 64), 256      # the covered heads (pmgt_ncf_score's comment): factor_num, d = factor_num * 2^(num_layers - 1)
 NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS = 65536, 13      # PMGT_NCF_TRAIN_*
+NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER = 64, 65, 72      # NCF_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the trained head; layer l = NCF_SITE_LAYER + l
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
@@ -124,7 +130,7 @@ HIP_SYMBOLS = [
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
-    "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table",
+    "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -288,6 +294,7 @@ def hip():
     L.pmgt_ncf_train_table_workspace_bytes.restype = i64
     L.pmgt_ncf_train_table_workspace_bytes.argtypes = [i, i, i, i64]
     L.pmgt_ncf_train_grad_table.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
+    L.pmgt_ncf_train_grad_dropout.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... table_grad or NULL, drop ...)
     _hip = L
     return L
 

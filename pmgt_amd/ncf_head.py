@@ -1,10 +1,11 @@
 """What the head of a PMGT_NCF is (pmgt/pmgt_ncf/models.py:91-105), stated once for the scoring (recommend.py), the training (ncf_train.py) and
 the ranking evaluation (evaluation.py): which heads the kernels cover, the flat parameter layout, the refusals of the ids and tables that the
 kernels read unchecked, and the two numpy references that every NCF kernel is judged against (ncf_head_host: users x catalogue;
-ncf_head_grad_host: loss, logits and every gradient of a list of pairs).  Pure numpy and the bindings module: importing this loads no GPU library."""
+ncf_head_grad_host: loss, logits and every gradient of a list of pairs, under the masks of ncf_dropout_masks when the head is trained with
+dropout).  Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
-from ._lib import NCF_FACTORS, NCF_KINDS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_TRAIN_MAX_PAIRS
+from ._lib import NCF_FACTORS, NCF_KINDS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER, NCF_TRAIN_MAX_PAIRS
 
 HEAD_PREFIXES = ("mlp_user_embeddings.", "mlp_layers.", "predict_layer.", "gmf_user_embeddings.", "gmf_item_embeddings.")
 TABLE_KEY = "item_table"                         # the trained table's name in the layouts, the gradients and the checkpoints
@@ -123,6 +124,72 @@ def mlp_stack(w: dict, x: np.ndarray, num_layers: int) -> list:
     return hs
 
 
+def _fmix32(h: int) -> int:
+    """The murmur3 finaliser (fmix32 of csrc/common.h) on a Python int."""
+    h &= 0xFFFFFFFF
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def check_dropout_p(p, what: str) -> float:
+    """`p` as the fp32 value the kernels take; ValueError unless it lies in [0, 1) (a NaN does not)."""
+    q = float(np.float32(p))
+    if not 0.0 <= q < 1.0:
+        raise ValueError(f"ncf_train: {what} = {p!r} outside [0, 1)")
+    return q
+
+
+def ncf_dropout_keep(seed: int, step: int, site: int, rows: int, cols: int, p: float) -> np.ndarray:
+    """bool [rows, cols]: True where the kernels keep element (row, col) of dropout site `site` (make_drop_key and drop_keep4 of
+    csrc/common.h restated in uint32 arithmetic, bit for bit; what pmgt_op_dropout_keep writes).  seed / step: the int64 values of the
+    device {seed, step} pair.  One hash pair (x, y) decides the 4 columns of group col >> 2 with 16 bits each; an element is kept when its
+    16 bits are >= thr >> 16, thr = (uint32)(double(float32 p) 2^32) saturated.  p = 0 keeps everything."""
+    p = check_dropout_p(p, "p")
+    if not p > 0.0:
+        return np.ones((rows, cols), dtype=bool)
+    seed, step, site = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF
+    k0 = _fmix32((seed & 0xFFFFFFFF) ^ ((site * 0x9E3779B1) & 0xFFFFFFFF))
+    k1 = _fmix32((seed >> 32) + (step & 0xFFFFFFFF) * 0x7FEB352D + (step >> 32) + site)
+    t = p * 4294967296.0
+    thr = 0xFFFFFFFF if t >= 4294967295.0 else int(t)
+    u32 = np.uint32
+    r, cg = np.arange(rows, dtype=u32)[:, None], np.arange((cols + 3) // 4, dtype=u32)[None, :]
+    with np.errstate(over="ignore"):
+        x = r * u32(0x9E3779B1) + cg * u32(0x85EBCA77) + u32(k0)
+        x ^= x >> u32(15)
+        x *= u32(0x2C1B3C6D)
+        x ^= x >> u32(12)
+        y = x * u32(0x297A2D39) + u32(k1)
+        y ^= y >> u32(15)
+    lanes = np.stack([x & u32(0xFFFF), x >> u32(16), y & u32(0xFFFF), y >> u32(16)], axis=2)
+    return (lanes >= u32(thr >> 16)).reshape(rows, -1)[:, :cols]
+
+
+def ncf_dropout_scale(p: float) -> np.float32:
+    """What a kept element is multiplied by: the fp32 value 1 / (1 - p)."""
+    return np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+
+
+def ncf_dropout_masks(seed: int, step: int, n: int, factor_num: int, num_layers: int, kind: str, p_emb: float, p_layer) -> dict:
+    """The masks pmgt_ncf_train_grad_dropout draws for a call on `n` pairs -> {site name: (bool keep [n, cols], fp32 scale)}:
+    "emb" [n, 2 d] (the user half first), "layer<l>" [n, d >> l] for every layer and, NeuMF-end, "gmf" [n, factor_num] at p_emb with a
+    mask of its own.  p_layer: one p for every layer or a sequence of num_layers.  What ncf_head_grad_host(masks=...) applies."""
+    check_head_covered(factor_num, num_layers, kind)
+    p_layer = [p_layer] * num_layers if np.isscalar(p_layer) else list(p_layer)
+    if len(p_layer) != num_layers:
+        raise ValueError(f"ncf_train: {len(p_layer)} layer dropouts for {num_layers} layers")
+    d = factor_num << (num_layers - 1)
+    masks = {"emb": (ncf_dropout_keep(seed, step, NCF_SITE_EMB, n, 2 * d, p_emb), ncf_dropout_scale(p_emb))}
+    if kind == "NeuMF-end":
+        masks["gmf"] = (ncf_dropout_keep(seed, step, NCF_SITE_GMF, n, factor_num, p_emb), ncf_dropout_scale(p_emb))
+    for i in range(num_layers):
+        masks[f"layer{i}"] = (ncf_dropout_keep(seed, step, NCF_SITE_LAYER + i, n, d >> i, p_layer[i]), ncf_dropout_scale(p_layer[i]))
+    return masks
+
+
 def ncf_head_host(weights: dict, users, table, dtype=np.float64) -> np.ndarray:
     """PMGT_NCF.head in eval mode on plain arrays, every user of `users` against every row of `table` [I, d] -> logits [len(users), I] in
     `dtype`.  `weights` is keyed like the model's state_dict ("mlp_user_embeddings.weight", "mlp_layers.<i>.linear.weight" / ".bias",
@@ -147,12 +214,15 @@ def ncf_head_host(weights: dict, users, table, dtype=np.float64) -> np.ndarray:
     return out
 
 
-def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False):
+def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False, masks: dict = None):
     """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
     `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
     model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
     in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order.
-    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule."""
+    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule.
+    masks: None, or {site: (bool keep [n, cols], scale)} as ncf_dropout_masks names them -- the head in TRAINING mode under these masks,
+    m = keep * scale in `dtype`: x0 = m_emb [user ; item], h_(l+1) = relu(m_l (W_l h_l + b_l)), gmf = m_gmf (gmf_u gmf_i), and the
+    gradients of that function (d x0 carries m_emb to the embedding rows and the table).  A site that is missing is not dropped."""
     w = head_weights(weights, dtype)
     factor, num_layers, kind, d = head_shape(w)
     table = np.asarray(table).astype(dtype)
@@ -160,11 +230,19 @@ def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.floa
     y = y.astype(dtype)
     n = len(users)
     one = dtype(1)
-    hs = mlp_stack(w, np.concatenate([w["mlp_user_embeddings.weight"][users], table[items]], axis=1), num_layers)
+    m = {} if masks is None else {k: np.asarray(keep, dtype=bool).astype(dtype) * dtype(scale) for k, (keep, scale) in masks.items()}
+    x0 = np.concatenate([w["mlp_user_embeddings.weight"][users], table[items]], axis=1)
+    if masks is None:
+        hs = mlp_stack(w, x0, num_layers)
+    else:
+        hs = [x0 * m["emb"] if "emb" in m else x0]
+        for i in range(num_layers):
+            a = hs[-1] @ w[f"mlp_layers.{i}.linear.weight"].T + w[f"mlp_layers.{i}.linear.bias"]
+            hs.append(np.maximum(a * m[f"layer{i}"] if f"layer{i}" in m else a, 0))
     feat = hs[-1]
     if kind == "NeuMF-end":
         gu, gi = w["gmf_user_embeddings.weight"][users], w["gmf_item_embeddings.weight"][items]
-        feat = np.concatenate([gu * gi, feat], axis=1)
+        feat = np.concatenate([gu * gi * m["gmf"] if "gmf" in m else gu * gi, feat], axis=1)
     wp = w["predict_layer.weight"].reshape(-1)
     z = feat @ wp + w["predict_layer.bias"][0]               # (a matrix-vector product; ncf_head_host's is matrix-matrix: kept apart)
     e = np.exp(-np.abs(z))
@@ -174,6 +252,8 @@ def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.floa
     dfeat = dl[:, None] * wp[None, :]
     if kind == "NeuMF-end":
         dg, dh = dfeat[:, :factor], dfeat[:, factor:]
+        if "gmf" in m:
+            dg = dg * m["gmf"]
         grads["gmf_user_embeddings.weight"] = np.zeros_like(w["gmf_user_embeddings.weight"])
         grads["gmf_item_embeddings.weight"] = np.zeros_like(w["gmf_item_embeddings.weight"])
         np.add.at(grads["gmf_user_embeddings.weight"], users, dg * gi)
@@ -181,10 +261,12 @@ def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.floa
     else:
         dh = dfeat
     for i in reversed(range(num_layers)):
-        dz = dh * (hs[i + 1] > 0)
+        dz = dh * m[f"layer{i}"] * (hs[i + 1] > 0) if f"layer{i}" in m else dh * (hs[i + 1] > 0)
         grads[f"mlp_layers.{i}.linear.weight"] = dz.T @ hs[i]
         grads[f"mlp_layers.{i}.linear.bias"] = dz.sum(axis=0, dtype=dtype)
         dh = dz @ w[f"mlp_layers.{i}.linear.weight"]
+    if "emb" in m:
+        dh = dh * m["emb"]
     grads["mlp_user_embeddings.weight"] = np.zeros_like(w["mlp_user_embeddings.weight"])
     np.add.at(grads["mlp_user_embeddings.weight"], users, dh[:, :d])
     if table_grad:

@@ -7,7 +7,8 @@ every config/hpo/train_ncf_*_params.json do (pmgt/ncf/trainer.py:168-179, "freez
   ng_sample            the reference's training-mode negative sampling, the same stream of draws
   normalize_item_table row-wise L2 normalisation of the exported embeddings (--normalize-item-init-emb)
   NcfHeadTrainer       the head's parameters (and the table) in one flat device buffer; step() = pmgt_ncf_train_grad or
-                       pmgt_ncf_train_grad_table (two launches) + pmgt_op_adamw (three)
+                       pmgt_ncf_train_grad_table (two launches) + pmgt_op_adamw (three); with dropout_seed, a head with dropout:
+                       pmgt_ncf_train_grad_dropout, its masks drawn from the device {seed, step} pair that pmgt_op_adamw advances
   fit_ncf              epochs of sampled pairs, ranking validation, early stopping, the best head (and table) restored
 
 The pure-numpy part needs no GPU; the head (head_layout, table_layout, check_pairs, the yardstick ncf_head_grad_host) is stated in ncf_head.py."""
@@ -17,9 +18,9 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS, NcfTrainC  # noqa: F401
-from .ncf_head import (HEAD_PREFIXES, TABLE_KEY, check_head_covered, check_item_table, check_pairs, head_layout, head_shape,  # noqa: F401
-                       head_state, layout_slots, ncf_head_grad_host, table_layout)
+from ._lib import NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS, NcfDropoutC, NcfTrainC  # noqa: F401
+from .ncf_head import (HEAD_PREFIXES, TABLE_KEY, check_dropout_p, check_head_covered, check_item_table, check_pairs, head_layout,  # noqa: F401
+                       head_shape, head_state, layout_slots, ncf_dropout_keep, ncf_dropout_masks, ncf_head_grad_host, table_layout)
 
 
 # ---- host side: pure numpy ------------------------------------------------------------------------------------------------------------------
@@ -86,9 +87,11 @@ class NcfHeadGrad:
     returns (loss [1], logits [n]) as device tensors.  Two launches; nothing is copied to the host, nothing waits.  `params` and `grads` are
     fp32 device tensors of head_layout's parameter count; the workspace grows to the largest n seen (never inside a capture: call
     reserve(n) first).  With `table_grad`, a contiguous fp32 device tensor of the table's shape, the entry is pmgt_ncf_train_grad_table:
-    d loss / d table is written whole into it as well (the table is trained); `table` and `table_grad` may be views into larger buffers."""
+    d loss / d table is written whole into it as well (the table is trained); `table` and `table_grad` may be views into larger buffers.
+    With `dropout` = (rng, p_emb, p_layer) the entry is pmgt_ncf_train_grad_dropout, the head in training mode: rng an int64 [2] device
+    tensor {seed, step} that the kernels read at every call, p_emb and p_layer (one p or one per layer) in [0, 1)."""
 
-    def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads, table_grad=None):
+    def __init__(self, factor_num: int, num_layers: int, kind: str, user_num: int, table, params, grads, table_grad=None, dropout=None):
         import torch
         self.lib = _lib.hip()
         self.layout, self.count = head_layout(factor_num, num_layers, kind, user_num, int(table.shape[0]) if table.dim() == 2 else 0)
@@ -111,6 +114,18 @@ class NcfHeadGrad:
         if count != self.count or list(offs) != layout_slots(self.layout):
             raise RuntimeError("ncf_train: the library's parameter layout differs from head_layout")
         self._ws, self._ws_pairs = None, 0
+        self.rng = self._drop = None
+        if dropout is not None:
+            rng, p_emb, p_layer = dropout
+            if rng.dtype != torch.int64 or tuple(rng.shape) != (2,) or rng.device != table.device or not rng.is_contiguous():
+                raise ValueError("ncf_train: the dropout rng must be a contiguous int64 tensor [2] = {seed, step} on the table's device")
+            p_layer = [p_layer] * num_layers if np.isscalar(p_layer) else list(p_layer)
+            if len(p_layer) != num_layers:
+                raise ValueError(f"ncf_train: {len(p_layer)} layer dropouts for {num_layers} layers")
+            self.rng = rng
+            self._drop = NcfDropoutC(rng.data_ptr(), check_dropout_p(p_emb, "emb_dropout"))
+            for i, p in enumerate(p_layer):
+                self._drop.p_layer[i] = check_dropout_p(p, f"the dropout of layer {i}")
 
     def reserve(self, n: int) -> None:
         import torch
@@ -135,7 +150,10 @@ class NcfHeadGrad:
         loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
         logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
         front = (C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(), logits.data_ptr())
-        if self.table_grad is None:
+        if self._drop is not None:
+            _lib.check(self.lib.pmgt_ncf_train_grad_dropout(*front, None if self.table_grad is None else self.table_grad.data_ptr(),
+                                                            C.byref(self._drop), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
+        elif self.table_grad is None:
             _lib.check(self.lib.pmgt_ncf_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
         else:
             _lib.check(self.lib.pmgt_ncf_train_grad_table(*front, self.table_grad.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
@@ -153,14 +171,28 @@ class NcfHeadTrainer:
     and recommend(table=trainer.table) read the trained rows with no copy --, the kernel's table and table_grad pointers point into the
     flat parameters and gradients, and the one pmgt_op_adamw call over the whole buffer clips head and table by ONE global norm and steps
     both: still five launches.  The table decays like every weight (get_optimizer exempts only biases and LayerNorm).  The pad floats are 0
-    in the parameters, the gradients and the moments, their decay mask is 0, and nothing writes them."""
+    in the parameters, the gradients and the moments, their decay mask is 0, and nothing writes them.
+    dropout_seed=<int>: the head is trained WITH ITS DROPOUT (model.emb_dropout.p on the concatenated input and on the GMF product, each
+    model.mlp_layers[i].dropout.p behind its Linear; the reference's hpo_ncf_*_params.yaml search both).  step() is then a TRAINING-mode step
+    whatever model.training says -- model.head, rank_users and recommend stay what the model's mode makes them, eval for validation --, the
+    masks come from the project's counter-based RNG over `trainer.rng`, an int64 [2] device tensor {seed, step}, and `step_count` is a view
+    of rng[1:2]: the pmgt_op_adamw call that ends every step advances the mask stream, so eager and replayed steps draw fresh masks with no
+    host write.  Still five launches.  Without a seed a model with dropout is refused."""
 
     def __init__(self, model, table, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: float = None, train_table: bool = False):
+                 max_grad_norm: float = None, train_table: bool = False, dropout_seed: int = None):
         import torch
         import torch.nn as nn
-        if model.emb_dropout.p != 0 or any(layer.dropout.p != 0 for layer in model.mlp_layers):
-            raise ValueError("ncf_train: dropout in the head is not covered (emb_dropout and every layer's dropout must be 0)")
+        p_emb, p_layer = model.emb_dropout.p, [layer.dropout.p for layer in model.mlp_layers]
+        if dropout_seed is None and (p_emb != 0 or any(p != 0 for p in p_layer)):
+            raise ValueError("ncf_train: dropout in the head is not covered without dropout_seed (pass dropout_seed=<int> to train with "
+                             "emb_dropout and the layers' dropout, or set them to 0)")
+        if dropout_seed is not None:
+            if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, (int, np.integer)) or not -2 ** 63 <= dropout_seed < 2 ** 63:
+                raise ValueError(f"ncf_train: dropout_seed = {dropout_seed!r} must be an integer that fits int64")
+            check_dropout_p(p_emb, "emb_dropout")
+            for i, p in enumerate(p_layer):
+                check_dropout_p(p, f"the dropout of layer {i}")
         check_head_covered(model.factor_num, model.num_layers, model.model)
         dev = model.mlp_user_embeddings.weight.device
         check_item_table(table, model.item_num, model.factor_num << (model.num_layers - 1), dev, "ncf_train")
@@ -172,7 +204,12 @@ class NcfHeadTrainer:
         self.params = torch.zeros(self.count, dtype=torch.float32, device=dev)
         self.grads = torch.zeros_like(self.params)
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        if self.dropout_seed is None:
+            self.rng, self.step_count = None, torch.zeros(1, dtype=torch.int64, device=dev)
+        else:
+            self.rng = torch.tensor([self.dropout_seed, 0], dtype=torch.int64, device=dev)
+            self.step_count = self.rng[1:2]                  # the optimizer's step counter IS the step of the mask stream
         self.decay = torch.zeros(self.count, dtype=torch.uint8, device=dev)
         self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
         self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
@@ -191,7 +228,8 @@ class NcfHeadTrainer:
         head_count = head_layout(*dims)[1]                  # (the whole buffer when the table is frozen)
         self.table = self.views(self.params)[TABLE_KEY] if self.train_table else table.detach().contiguous()
         self.grad_fn = NcfHeadGrad(model.factor_num, model.num_layers, model.model, model.user_num, self.table, self.params[:head_count],
-                                   self.grads[:head_count], table_grad=self.views(self.grads)[TABLE_KEY] if self.train_table else None)
+                                   self.grads[:head_count], table_grad=self.views(self.grads)[TABLE_KEY] if self.train_table else None,
+                                   dropout=None if self.rng is None else (self.rng, p_emb, p_layer))
         self._graph = self._static = None
 
     def views(self, flat) -> dict:
@@ -247,14 +285,20 @@ class NcfHeadTrainer:
     def state_dict(self) -> dict:
         """The flat parameters, both moments, the step counter and the layout; a trained table is inside the parameters and named by the
         layout, so a state saved frozen is refused by a trainer that trains the table, and the other way round."""
-        return {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
-                "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+        sd = {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+              "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+        if self.dropout_seed is not None:                    # (with "step", the whole state of the mask stream)
+            sd["dropout_seed"] = self.dropout_seed
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         import torch
         if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
             raise ValueError("ncf_train: the state was saved for another head, or with the table frozen / trained the other way "
                              "(the layouts differ)")
+        if sd.get("dropout_seed") != self.dropout_seed:
+            raise ValueError(f"ncf_train: the state was saved with dropout_seed = {sd.get('dropout_seed')!r}, this trainer has "
+                             f"{self.dropout_seed!r}")
         with torch.no_grad():
             self.params.copy_(sd["params"])
             self.exp_avg.copy_(sd["exp_avg"])
@@ -264,7 +308,7 @@ class NcfHeadTrainer:
 
 def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, num_ng: int = 1, seed: int = 0, early_criterion: str = "n20",
             patience: int = 10, ckpt_dir: str = None, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-            max_grad_norm: float = 5.0, batch_users: int = 256, log=None, train_table: bool = False):
+            max_grad_norm: float = 5.0, batch_users: int = 256, log=None, train_table: bool = False, dropout_seed: int = None):
     """Trains the head of `model` on the interaction list `train_pairs` [(user, item)] over the frozen `table`, the reference's downstream
     fit: every epoch draws ng_sample(seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's users, items and
     labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device and are read once
@@ -275,6 +319,8 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
     NcfHeadTrainer(train_table=True)): validation ranks over the trained table, the best epoch's table is kept and restored with the head,
     the checkpoint file gains the key "item_table", and at the end the best table is copied back into the caller's `table` tensor IN PLACE:
     `table` IS OVERWRITTEN -- recommend(table=table) and evaluate_ranking(table=table) then read the trained rows.
+    dropout_seed=<int> (NcfHeadTrainer's): a model with emb_dropout / dropout > 0 is trained with them, the masks a pure function of the
+    seed and the count of steps taken; validation stays in eval mode and never drops.  Without it such a model is refused.
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
     import torch
     from .evaluation import check_candidates, rank_users
@@ -288,7 +334,7 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
     check_pairs(pairs[:, 0], pairs[:, 1], np.ones(len(pairs), np.float32), model.user_num, model.item_num, max_pairs=1 << 40)
     valid = check_candidates(model, *valid, "fit_ncf: validation")
     trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                             train_table=train_table)
+                             train_table=train_table, dropout_seed=dropout_seed)
     dev = trainer.params.device
     on_dev = [torch.from_numpy(a).to(dev) for a in valid]
     metrics = RankingMetrics(dev, len(valid[0]), (10, 20))

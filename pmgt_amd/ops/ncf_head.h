@@ -1,4 +1,5 @@
-// What ncf_score.hip and ncf_train.hip share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU, the covered heads.
+// What ncf_score.hip and ncf_train.hip share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU, the covered heads, the
+// dropout sites of the trained head.
 #pragma once
 #include "../csrc/common.h"
 #include "../../include/pmgt_capi.h"
@@ -7,6 +8,9 @@ namespace pmgt {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 static constexpr int NCF_MAX_D = 256;      // the widest layer-0 half: d = factor_num * 2^(num_layers - 1)
+// the dropout sites of the trained head (DropCfg.site; pmgt_ncf_train_grad_dropout of include/pmgt_capi.h, mirrored in _lib.py): the
+// concatenated [user ; item] input, the GMF product, and layer l's output = NCF_SITE_LAYER + l.  Row = the pair's index within the call, column = the feature.
+static constexpr uint32_t NCF_SITE_EMB = 64, NCF_SITE_GMF = 65, NCF_SITE_LAYER = 72;
 
 // relu that keeps a NaN (fmaxf would return 0 and hide a broken table from the NaN check of the selection)
 __device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }

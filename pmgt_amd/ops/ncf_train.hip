@@ -32,6 +32,17 @@
 //          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.  The item kind sums the GMF item rows (NeuMF-end)
 //          and, for a trained table, the item half of dx by the same rule.
 // DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+//
+// DROPOUT (pmgt_ncf_train_grad_dropout; the DROP instantiations, the others are the kernels as they were): PMGT_NCF.head in training mode,
+// the masks m = 0 or 1 / (1 - p) drawn by the counter-based RNG of csrc/common.h from the caller's device {seed, step} pair, indexed by
+// (pair, feature), one hash pair per 4 neighbouring features, nothing stored:
+//   emb      x0 = m_e [U_mlp[u] ; table[i]]: applied to the 16-byte x loads of layer 0, drawn again by the weight task of layer 0 in launch 2
+//            (its B operand is gathered from the tables) and by the last data gradient, which makes dx the gradient of the embedding ROWS
+//   layer l  act_l = m_l relu(W_l x + b_l) = relu(m_l (W_l x + b_l)): applied before the store.  The stored activation is > 0 exactly where
+//            the element was kept and its pre-activation positive (the scale is >= 1), so the walk back keeps its act > 0 tests, multiplies
+//            the passed gradient by 1 / (1 - p_l) and draws no layer mask again
+//   gmf      gprod = m_g (gmf_u gmf_i), a mask of its own at emb_dropout's p: stored dropped, drawn again for the per-pair GMF gradients
+// A site whose p is 0 draws nothing and multiplies by nothing.
 #include "ncf_head.h"
 
 namespace pmgt {
@@ -80,6 +91,8 @@ struct NtTask {
     int m, col_blocks, first, predict;      // col_blocks counts the constant column's block
 };
 
+typedef pmgt_ncf_dropout NtDrop;      // the second kernel argument; only the DROP instantiations read it
+
 struct NtGradsArgs {
     NtTask task[NT_MAX_TASKS];
     const int64_t *users, *items;
@@ -94,10 +107,15 @@ __device__ __forceinline__ float4 ld4(const float* p, bool ok) {
 }
 __device__ __forceinline__ float elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }      // provably uniform
+__device__ __forceinline__ DropKey drop_off() { return DropKey{0u, 0u, 0u, 1.f, false}; }
+__device__ __forceinline__ void mul4(float4& v, const float (&m)[4]) { v.x *= m[0], v.y *= m[1], v.z *= m[2], v.w *= m[3]; }
 
 // act[pair][0 .. M) = relu(W [M][K] x + bias); x = [r1[0 .. w1) ; r2[0 .. K - w1)], the lane's own pair row(s)
+// DROP: x is multiplied by the mask of key kx as it is loaded and the result by the mask of ky before the store (row = the pair)
+template <bool DROP>
 __device__ __forceinline__ void forward_layer(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* r1, int w1,
-                                              const float* r2, bool valid, float* act_row, int wave, int lane) {
+                                              const float* r2, bool valid, float* act_row, int wave, int lane, const DropKey& kx,
+                                              const DropKey& ky, int pair) {
     const int p = lane & 31, h = lane >> 5;
     for (int mb = wave; mb * 32 < M; mb += NT_WAVES) {
         f32x16 acc;
@@ -115,6 +133,13 @@ __device__ __forceinline__ void forward_layer(const float* __restrict__ W, const
                 const int k = k0 + 16 * h + 4 * j;
                 a[j] = ld4(wrow + k, m < M && k < K);
                 x[j] = ld4(k < w1 ? r1 + k : r2 + (k - w1), valid && k < K);
+                if constexpr (DROP) {
+                    if (kx.on) {
+                        float mk[4];
+                        drop_mul4(kx, (uint32_t)pair, (uint32_t)(k >> 2), mk);
+                        mul4(x[j], mk);
+                    }
+                }
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -129,14 +154,23 @@ __device__ __forceinline__ void forward_layer(const float* __restrict__ W, const
             v.y = relu_keep_nan(acc[4 * q + 1]);
             v.z = relu_keep_nan(acc[4 * q + 2]);
             v.w = relu_keep_nan(acc[4 * q + 3]);
+            if constexpr (DROP) {
+                if (ky.on) {
+                    float mk[4];
+                    drop_mul4(ky, (uint32_t)pair, (uint32_t)(f >> 2), mk);
+                    mul4(v, mk);
+                }
+            }
             if (valid && f < M) *reinterpret_cast<float4*>(act_row + f) = v;
         }
     }
 }
 
 // dx[pair][c] = sum_o W[o][c] dz[pair][o] for c in [0, C), W [M][K] with C <= K; times (mask_row[c] > 0) when mask_row
+// DROP: a gradient that passes mask_row is multiplied by gscale (the scale of the layer that wrote mask_row), and the result by the mask of kx
+template <bool DROP>
 __device__ __forceinline__ void backward_layer(const float* __restrict__ W, int M, int K, int C, const float* dz_row, const float* mask_row,
-                                               bool valid, float* dx_row, int wave, int lane) {
+                                               bool valid, float* dx_row, int wave, int lane, float gscale, const DropKey& kx, int pair) {
     const int p = lane & 31, h = lane >> 5;
     for (int cb = wave; cb * 32 < C; cb += NT_WAVES) {
         f32x16 acc;
@@ -167,6 +201,14 @@ __device__ __forceinline__ void backward_layer(const float* __restrict__ W, int 
                 v.y = hm.y > 0.f ? v.y : 0.f;
                 v.z = hm.z > 0.f ? v.z : 0.f;
                 v.w = hm.w > 0.f ? v.w : 0.f;
+                if constexpr (DROP) v.x *= gscale, v.y *= gscale, v.z *= gscale, v.w *= gscale;
+            }
+            if constexpr (DROP) {
+                if (kx.on) {
+                    float mk[4];
+                    drop_mul4(kx, (uint32_t)pair, (uint32_t)(f >> 2), mk);
+                    mul4(v, mk);
+                }
             }
             if (ok) *reinterpret_cast<float4*>(dx_row + f) = v;
         }
@@ -174,8 +216,9 @@ __device__ __forceinline__ void backward_layer(const float* __restrict__ W, int 
 }
 
 // TABLE: the item table is trained (the frozen instantiation is the kernel as it was: the widths below fold to d)
-template <bool TABLE>
-__global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a) {
+// DROP: dropout is on at one site or more (without it the kernel's instructions are those it had: `dr` is not read)
+template <bool TABLE, bool DROP>
+__global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a, NtDrop dr) {
     __shared__ float s_dl[NT_TILE];
     __shared__ int64_t s_ids[NT_THREADS];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
@@ -219,12 +262,20 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     const int64_t uid = valid ? a.users[pair] : 0, iid = valid ? a.items[pair] : 0;
     const float* urow = a.u_mlp + uid * d;
     const float* irow = a.table + iid * d;
-    forward_layer(a.layer[0].w, a.layer[0].b, d, 2 * d, urow, d, irow, valid, a.layer[0].act + (int64_t)pair * d, wave, lane);
+    DropKey kemb = drop_off(), kgmf = drop_off(), klay = drop_off();
+    if constexpr (DROP) {
+        kemb = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB});
+        if (a.neumf) kgmf = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_GMF});
+        klay = make_drop_key(DropCfg{dr.rng, dr.p_layer[0], NCF_SITE_LAYER});
+    }
+    forward_layer<DROP>(a.layer[0].w, a.layer[0].b, d, 2 * d, urow, d, irow, valid, a.layer[0].act + (int64_t)pair * d, wave, lane, kemb, klay,
+                        pair);
     __syncthreads();
     for (int l = 1; l < L; ++l) {
         const int M = a.layer[l].out;
-        forward_layer(a.layer[l].w, a.layer[l].b, M, 2 * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, 2 * M, nullptr, valid,
-                      a.layer[l].act + (int64_t)pair * M, wave, lane);
+        if constexpr (DROP) klay = make_drop_key(DropCfg{dr.rng, dr.p_layer[l], NCF_SITE_LAYER + (uint32_t)l});
+        forward_layer<DROP>(a.layer[l].w, a.layer[l].b, M, 2 * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, 2 * M, nullptr, valid,
+                            a.layer[l].act + (int64_t)pair * M, wave, lane, drop_off(), klay, pair);
         __syncthreads();
     }
     const float* feat = a.layer[L - 1].act;                  // [n][F]
@@ -236,10 +287,23 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
             if (a.neumf) {
                 const float* gu = a.gu + uid * F;
                 const float* gi = a.gi + iid * F;
-                for (int f = h * half; f < (h + 1) * half; ++f) {
-                    const float g = gu[f] * gi[f];
-                    a.gprod[(int64_t)pair * F + f] = g;
-                    s = fmaf(a.wp[f], g, s);
+                if constexpr (DROP) {                        // (half is a multiple of 4: one draw per 4 factors)
+                    for (int f = h * half; f < (h + 1) * half; f += 4) {
+                        float mk[4] = {1.f, 1.f, 1.f, 1.f};
+                        if (kgmf.on) drop_mul4(kgmf, (uint32_t)pair, (uint32_t)(f >> 2), mk);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float g = gu[f + e] * gi[f + e] * mk[e];
+                            a.gprod[(int64_t)pair * F + f + e] = g;
+                            s = fmaf(a.wp[f + e], g, s);
+                        }
+                    }
+                } else {
+                    for (int f = h * half; f < (h + 1) * half; ++f) {
+                        const float g = gu[f] * gi[f];
+                        a.gprod[(int64_t)pair * F + f] = g;
+                        s = fmaf(a.wp[f], g, s);
+                    }
                 }
             }
             const float* hl = feat + (int64_t)pair * F;
@@ -261,14 +325,20 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
         }
     }
     __syncthreads();
+    float gscale = 1.f;                                      // DROP: 1 / (1 - p) of the layer whose activation masks the gradient
+    if constexpr (DROP) gscale = klay.scale;                 // (klay is the last layer's key)
     for (int e = tid; e < NT_TILE * F; e += NT_THREADS) {    // dz of the last layer and the per-pair GMF gradients
         const int pp = e / F, f = e - pp * F, pr = bid * NT_TILE + pp;
         if (pr >= n) continue;
         const float dl = s_dl[pp];
         const int64_t at = (int64_t)pr * F + f;
-        a.layer[L - 1].dz[at] = feat[at] > 0.f ? dl * wp_mlp[f] : 0.f;
+        if constexpr (DROP) a.layer[L - 1].dz[at] = feat[at] > 0.f ? dl * wp_mlp[f] * gscale : 0.f;
+        else a.layer[L - 1].dz[at] = feat[at] > 0.f ? dl * wp_mlp[f] : 0.f;
         if (a.neumf) {
-            const float dg = dl * a.wp[f];
+            float dg = dl * a.wp[f];
+            if constexpr (DROP) {
+                if (kgmf.on) dg *= drop_mul1(kgmf, (uint32_t)pr, (uint32_t)f);
+            }
             a.ggu[at] = dg * a.gi[a.items[pr] * F + f];
             a.ggi[at] = dg * a.gu[a.users[pr] * F + f];
         }
@@ -276,12 +346,14 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     __syncthreads();
     for (int l = L - 1; l >= 1; --l) {
         const int M = a.layer[l].out;
-        backward_layer(a.layer[l].w, M, 2 * M, 2 * M, a.layer[l].dz + (int64_t)pair * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, valid,
-                       a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane);
+        if constexpr (DROP) gscale = make_drop_key(DropCfg{dr.rng, dr.p_layer[l - 1], NCF_SITE_LAYER + (uint32_t)(l - 1)}).scale;
+        backward_layer<DROP>(a.layer[l].w, M, 2 * M, 2 * M, a.layer[l].dz + (int64_t)pair * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, valid,
+                             a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane, gscale, drop_off(), pair);
         __syncthreads();
     }
     const int dxw = TABLE ? 2 * d : d;                       // the columns of layer 0's input that dx covers
-    backward_layer(a.layer[0].w, d, 2 * d, dxw, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.dx + (int64_t)pair * dxw, wave, lane);
+    backward_layer<DROP>(a.layer[0].w, d, 2 * d, dxw, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.dx + (int64_t)pair * dxw, wave, lane,
+                         1.f, kemb, pair);
 }
 
 __device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
@@ -293,8 +365,9 @@ __device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
     return s.p2[row * s.w2 + (c - s.w1)];
 }
 
-template <bool TABLE>
-__global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs a) {
+// DROP: the weight task of layer 0 gathers its B operand from the tables and applies the emb mask to it, drawn again per element
+template <bool TABLE, bool DROP>
+__global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs a, NtDrop dr) {
     __shared__ float s_acc[NT_WAVES][16][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
     int bid = blockIdx.x;
@@ -340,6 +413,10 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
     const int mb = local / t.col_blocks, nb = local - mb * t.col_blocks;
     const bool ones = nb == t.col_blocks - 1;
     const int p = lane & 31, h = lane >> 5, m = mb * 32 + p, c = nb * 32 + p;
+    DropKey kemb = drop_off();
+    if constexpr (DROP) {
+        if (ti == 0 && !ones) kemb = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB});
+    }
     f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 16; ++g) acc[g] = 0.f;
@@ -351,6 +428,9 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
             const bool ok = pair < n;
             av[s] = (ok && m < M) ? t.a[(int64_t)pair * M + m] : 0.f;
             bv[s] = ones ? (p == 0 ? 1.f : 0.f) : ((ok && c < K) ? src_at(t.b, pair, c) : 0.f);
+            if constexpr (DROP) {
+                if (kemb.on) bv[s] *= drop_mul1(kemb, (uint32_t)pair, (uint32_t)c);
+            }
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
@@ -449,9 +529,10 @@ static int64_t nt_workspace_bytes(int factor_num, int num_layers, int kind, int6
     return nt_workspace_floats(s, n, table) * (int64_t)sizeof(float);
 }
 
-// both gradient entries; want_table: the table is trained and table_grad [item_num][d] is written whole
+// every gradient entry; want_table: the table is trained and table_grad [item_num][d] is written whole; drop: NULL or the dropout of the call
 static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
-                   float* loss, float* logits, bool want_table, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream) {
+                   float* loss, float* logits, bool want_table, float* table_grad, const pmgt_ncf_dropout* drop, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
     PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
     NtShape s;
     if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, who, &s)) return rc;
@@ -464,6 +545,19 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
                "%s: misaligned buffer", who);
     const int64_t need = nt_workspace_floats(s, n, want_table) * (int64_t)sizeof(float);
     PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
+    NtDrop dr = {};
+    bool drop_on = false;                                    // every p 0: the instantiations without dropout
+    if (drop) {
+        dr.rng = drop->rng, dr.p_emb = drop->p_emb;
+        PMGT_CHECK(dr.p_emb >= 0.f && dr.p_emb < 1.f, -2, "%s: p_emb = %g outside [0, 1)", who, (double)dr.p_emb);      // (a NaN fails both)
+        drop_on = dr.p_emb > 0.f;
+        for (int l = 0; l < s.L; ++l) {
+            dr.p_layer[l] = drop->p_layer[l];
+            PMGT_CHECK(dr.p_layer[l] >= 0.f && dr.p_layer[l] < 1.f, -2, "%s: p_layer[%d] = %g outside [0, 1)", who, l, (double)dr.p_layer[l]);
+            drop_on = drop_on || dr.p_layer[l] > 0.f;
+        }
+        PMGT_CHECK(!drop_on || (dr.rng && ((uintptr_t)dr.rng & 7) == 0), -2, "%s: dropout needs the device {seed, step} pair, 8-byte aligned", who);
+    }
     int64_t off[PMGT_NCF_TRAIN_TENSORS];
     nt_layout(s, off);
     const float* P = head->params;
@@ -553,12 +647,20 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     hipStream_t st = (hipStream_t)stream;
     const int kinds = (s.neumf || want_table) ? 2 : 1;       // MLP over a frozen table has no rows indexed by item: its item order is not read
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
-    if (want_table) hipLaunchKernelGGL(ncf_train_pairs_kernel<true>, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
-    else hipLaunchKernelGGL(ncf_train_pairs_kernel<false>, dim3(grid1), dim3(NT_THREADS), 0, st, pa);
+    if (drop_on) {
+        if (want_table) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+    }
+    else if (want_table) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+    else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
     PMGT_LAUNCH_OK();
     const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks);
-    if (want_table) hipLaunchKernelGGL(ncf_train_grads_kernel<true>, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
-    else hipLaunchKernelGGL(ncf_train_grads_kernel<false>, dim3(grid2), dim3(NT_THREADS), 0, st, ga);
+    if (drop_on && dr.p_emb > 0.f) {                         // (launch 2 draws the emb mask only)
+        if (want_table) hipLaunchKernelGGL((ncf_train_grads_kernel<true, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+        else hipLaunchKernelGGL((ncf_train_grads_kernel<false, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+    }
+    else if (want_table) hipLaunchKernelGGL((ncf_train_grads_kernel<true, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+    else hipLaunchKernelGGL((ncf_train_grads_kernel<false, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
     PMGT_LAUNCH_OK();
     return 0;
 }
@@ -577,12 +679,21 @@ int64_t pmgt_ncf_train_table_workspace_bytes(int factor_num, int num_layers, int
 
 int pmgt_ncf_train_grad(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                         float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
-    return nt_grad("pmgt_ncf_train_grad", head, users, items, labels, n, loss, logits, false, nullptr, workspace, workspace_bytes, stream);
+    return nt_grad("pmgt_ncf_train_grad", head, users, items, labels, n, loss, logits, false, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 int pmgt_ncf_train_grad_table(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                               float* logits, float* table_grad, void* workspace, int64_t workspace_bytes, void* stream) {
-    return nt_grad("pmgt_ncf_train_grad_table", head, users, items, labels, n, loss, logits, true, table_grad, workspace, workspace_bytes, stream);
+    return nt_grad("pmgt_ncf_train_grad_table", head, users, items, labels, n, loss, logits, true, table_grad, nullptr, workspace, workspace_bytes,
+                   stream);
+}
+
+int pmgt_ncf_train_grad_dropout(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                                float* loss, float* logits, float* table_grad, const pmgt_ncf_dropout* drop, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    const char* who = "pmgt_ncf_train_grad_dropout";
+    PMGT_CHECK(drop != nullptr, -2, "%s: NULL drop", who);
+    return nt_grad(who, head, users, items, labels, n, loss, logits, table_grad != nullptr, table_grad, drop, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
