@@ -441,6 +441,59 @@ int pmgt_ncf_train_grad_dropout(const pmgt_ncf_train* head, const int64_t* users
                                 float* loss, float* logits, float* table_grad /* NULL: frozen table */, const pmgt_ncf_dropout* drop,
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The DEEP & CROSS NETWORK of the reference's click-through experiment ON THE DEVICE (pmgt/dcn/models.py, scripts/run_dcn.sh): for n
+ * (user, item, label) pairs the logits (pmgt_dcn_forward) or the mean loss, the logits and the gradient of that loss with respect to
+ * EVERY trained parameter, both embedding tables included (pmgt_dcn_train_grad), in two launches, no sync, no allocation, no atomic:
+ * capturable, and the same inputs give the same bits.  With E = factor_num * 2^deep_layers, D = 2 E, L = deep_layers, C = cross_layers:
+ *   x0 = [user_embeddings[u] ; item_embeddings[i]]                                                   (both dropouts are 0)
+ *   cross   x^(0) = x0,  s_c = x^(c) . w_c,  x^(c+1) = LN_c(x0 s_c + x0)   c = 0 .. C - 1   (the layer adds x0, NOT x^(c); the
+ *           `bias` of the reference's cross layer is never read and is no part of the buffers)
+ *   deep    h_0 = x0,  h_(l+1) = relu(LN_l(W_l h_l + b_l)),  W_l [D >> (l + 1)][D >> l]   l = 0 .. L - 1
+ *   z = output_weight . [x^(C) ; h_L] + output_bias,   loss = mean of max(z, 0) - z y + log1p(exp(-|z|)),   dz = (sigmoid(z) - y) / n
+ * LN(v) = (v - mean) / sqrt(var + layer_norm_eps) gamma + beta, mean and BIASED variance over the row (torch.nn.LayerNorm); with
+ * use_layer_norm = 0 it is the identity and the gamma / beta slots are absent.  The ReLU passes where h > 0.
+ * THE PARAMETERS are ONE flat fp32 buffer, the gradients another of the same layout; pmgt_dcn_layout gives the offset in floats of each
+ * tensor in this order of PMGT_DCN_TENSORS slots (row-major, the state_dict's shapes; -1 for a tensor the model does not have) and
+ * returns the parameter count; the tensors are packed in slot order:
+ *   [0] user_embeddings.weight [user_num][E]      [1] item_embeddings.weight [item_num][E]
+ *   [2 + 4 l] deep_net.layers.l.linear.weight [D >> (l + 1)][D >> l]   [3 + 4 l] .linear.bias   [4 + 4 l] .layer_norm.weight   [5 + 4 l] .layer_norm.bias
+ *   [18 + 3 c] cross_net.layers.c.weight [D]      [19 + 3 c] .layer_norm.weight [D]      [20 + 3 c] .layer_norm.bias [D]
+ *   [36] output_layer.weight [D + 2 factor_num] = [cross | deep]      [37] output_layer.bias [1]
+ * Every tensor but the last has a multiple of 8 floats.
+ * THE GRADIENT BUFFER IS WRITTEN WHOLE: embedding rows no pair touches hold +0.0; rows hit by several pairs are summed in pair order,
+ * for both tables.  d x0 of a pair is ((cross layer C - 1's term + ... + layer 0's) + d x^(0)) + the deep net's.  The sums over the
+ * pairs have one fixed order: the Linear weights, their biases and the output layer (the loss with them) over 32-pair chunks dealt to
+ * four accumulators, added as (0 + 1) + (2 + 3); the column sums (gamma, beta and w_c gradients) over the pairs p = a, a + 4, ... in
+ * four accumulators a = 0 .. 3, added the same way.
+ * pmgt_dcn_forward writes the logits pmgt_dcn_train_grad writes, bit for bit: the same forward code without the stores of the backward;
+ * it reads head->params only (grads may be NULL).
+ * users / items int64 [n] (ids inside the tables: THE CALLER CHECKS THEM, they are read as they are), labels fp32 [n], loss one device
+ * float, logits fp32 [n] (pmgt_dcn_train_grad: or NULL); workspace: pmgt_dcn_workspace_bytes(...) bytes of 16-byte aligned device memory
+ * (one size serves both entries).  Covered: factor_num in {8, 16, 32, 64}, 1 <= L <= PMGT_DCN_MAX_DEEP with E <= 256, 1 <= C <=
+ * PMGT_DCN_MAX_CROSS, 1 <= n <= PMGT_DCN_MAX_PAIRS, user_num and item_num in [1, 2^31 - 2].
+ * Refused (-2; the layout and sizing entries return it as their value) before anything is launched: a shape or n outside these limits, a
+ * NULL or misaligned buffer (parameters, gradients and workspace: 16 bytes), a short workspace, a layer_norm_eps that is NaN or negative.
+ * Added without a bump of pmgt_abi_version(): one struct, four entries, nothing existing moved. */
+#define PMGT_DCN_MAX_DEEP 4
+#define PMGT_DCN_MAX_CROSS 6
+#define PMGT_DCN_TENSORS 38
+#define PMGT_DCN_MAX_PAIRS 65536
+typedef struct pmgt_dcn_head {
+    int factor_num, deep_layers, cross_layers, use_layer_norm;
+    float layer_norm_eps;
+    int reserved;
+    int64_t user_num, item_num;                   /* rows of the two embedding tables */
+    const float* params;                          /* the flat parameters */
+    float* grads;                                 /* the flat gradients, written whole (pmgt_dcn_forward: not read, may be NULL) */
+} pmgt_dcn_head;
+int64_t pmgt_dcn_layout(int factor_num, int deep_layers, int cross_layers, int use_layer_norm, int64_t user_num, int64_t item_num,
+                        int64_t* offsets);
+int64_t pmgt_dcn_workspace_bytes(int factor_num, int deep_layers, int cross_layers, int use_layer_norm, int64_t n);
+int pmgt_dcn_forward(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, int64_t n, float* logits, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int pmgt_dcn_train_grad(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                        float* loss, float* logits /* or NULL */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average
  * that lives inside a captured step.  One update is, per element,

@@ -96,11 +96,20 @@ class NcfDropoutC(C.Structure):
     _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_layer", C.c_float * 4)]
 
 
+class DcnHeadC(C.Structure):
+    """pmgt_dcn_head (include/pmgt_capi.h)."""
+    _fields_ = [("factor_num", C.c_int), ("deep_layers", C.c_int), ("cross_layers", C.c_int), ("use_layer_norm", C.c_int),
+                ("layer_norm_eps", C.c_float), ("reserved", C.c_int), ("user_num", C.c_int64), ("item_num", C.c_int64),
+                ("params", C.c_void_p), ("grads", C.c_void_p)]
+
+
 NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
 NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
 NCF_FACTORS, NCF_MAX_D = (8, 16, 32, 64), 256      # the covered heads (pmgt_ncf_score's comment): factor_num, d = factor_num * 2^(num_layers - 1)
 NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS = 65536, 13      # PMGT_NCF_TRAIN_*
 NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER = 64, 65, 72      # NCF_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the trained head; layer l = NCF_SITE_LAYER + l
+DCN_MAX_DEEP, DCN_MAX_CROSS, DCN_TENSORS, DCN_MAX_PAIRS = 4, 6, 38, 65536      # PMGT_DCN_*
+DCN_FACTORS, DCN_MAX_E = (8, 16, 32, 64), 256      # the covered shapes (pmgt_dcn_train_grad's comment): factor_num, E = factor_num * 2^deep_layers
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
@@ -131,6 +140,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
+    "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -295,6 +305,12 @@ def hip():
     L.pmgt_ncf_train_table_workspace_bytes.argtypes = [i, i, i, i64]
     L.pmgt_ncf_train_grad_table.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
     L.pmgt_ncf_train_grad_dropout.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... table_grad or NULL, drop ...)
+    L.pmgt_dcn_layout.restype = i64
+    L.pmgt_dcn_layout.argtypes = [i, i, i, i, i64, i64, vp]
+    L.pmgt_dcn_workspace_bytes.restype = i64
+    L.pmgt_dcn_workspace_bytes.argtypes = [i, i, i, i, i64]
+    L.pmgt_dcn_forward.argtypes = [C.POINTER(DcnHeadC), vp, vp, i64, vp, vp, i64, vp]
+    L.pmgt_dcn_train_grad.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, i64, vp, vp, vp, i64, vp]
     _hip = L
     return L
 

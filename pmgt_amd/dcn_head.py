@@ -1,0 +1,212 @@
+"""What the reference's Deep & Cross Network is (pmgt/dcn/models.py), stated once for the model class (dcn.py), the training and the
+evaluation (dcn_train.py): which shapes the kernels cover, the flat parameter layout of pmgt_dcn_train_grad, the refusals, and the two
+numpy references every DCN kernel is judged against (dcn_head_host: logits; dcn_head_grad_host: loss, logits and every gradient).
+With E = F 2^L the embedding width and D = 2 E:
+  x0 = [user_embeddings[u] ; item_embeddings[i]]
+  cross   x^(0) = x0,  s_c = x^(c) . w_c,  x^(c+1) = LN_c(x0 s_c + x0)            (the layer adds x0, NOT x^(c); its `bias` is never read)
+  deep    h_0 = x0,  h_(l+1) = relu(LN_l(W_l h_l + b_l)),  W_l [D >> (l + 1)][D >> l]
+  z = output_layer.weight . [x^(C) ; h_L] + output_layer.bias,   loss = mean BCE-with-logits
+LN is torch.nn.LayerNorm (biased variance, (x - mean) / sqrt(var + eps) gamma + beta), absent without use_layer_norm.
+Pure numpy and the bindings module: importing this loads no GPU library."""
+import numpy as np
+
+from ._lib import DCN_FACTORS, DCN_MAX_CROSS, DCN_MAX_DEEP, DCN_MAX_E, DCN_MAX_PAIRS, DCN_TENSORS
+from .ncf_head import check_ids, check_pairs, head_weights  # noqa: F401
+
+USER_KEY, ITEM_KEY = "user_embeddings.weight", "item_embeddings.weight"
+OUT_W, OUT_B = "output_layer.weight", "output_layer.bias"
+
+
+def deep_keys(l: int, use_layer_norm: bool) -> list:
+    p = f"deep_net.layers.{l}."
+    return [p + "linear.weight", p + "linear.bias"] + ([p + "layer_norm.weight", p + "layer_norm.bias"] if use_layer_norm else [])
+
+
+def cross_keys(c: int, use_layer_norm: bool) -> list:
+    """The TRAINED tensors of cross layer c: `cross_net.layers.c.bias` is a parameter the forward never reads, so it is not among them."""
+    p = f"cross_net.layers.{c}."
+    return [p + "weight"] + ([p + "layer_norm.weight", p + "layer_norm.bias"] if use_layer_norm else [])
+
+
+def check_dcn_covered(factor_num: int, deep_layers: int, cross_layers: int) -> None:
+    """ValueError naming the limit when the kernels (pmgt_dcn_forward, pmgt_dcn_train_grad) do not cover the shape."""
+    if factor_num not in DCN_FACTORS:
+        raise ValueError(f"dcn: factor_num = {factor_num}, covered: {DCN_FACTORS}")
+    if not (isinstance(deep_layers, (int, np.integer)) and 1 <= deep_layers <= DCN_MAX_DEEP):
+        raise ValueError(f"dcn: deep_net_num_layers = {deep_layers} outside [1, {DCN_MAX_DEEP}]")
+    if factor_num << deep_layers > DCN_MAX_E:
+        raise ValueError(f"dcn: embedding width factor_num * 2^deep_net_num_layers = {factor_num << deep_layers} above {DCN_MAX_E}")
+    if not (isinstance(cross_layers, (int, np.integer)) and 1 <= cross_layers <= DCN_MAX_CROSS):
+        raise ValueError(f"dcn: cross_net_num_layers = {cross_layers} outside [1, {DCN_MAX_CROSS}]")
+
+
+def check_dcn_dropout(emb_dropout: float, dropout: float) -> None:
+    if emb_dropout != 0 or dropout != 0:
+        raise ValueError(f"dcn: dropout is not covered (emb_dropout = {emb_dropout}, dropout = {dropout}): the trainer, the fit and the "
+                         "evaluation are eval-mode arithmetic; set both to 0")
+
+
+def dcn_shape(weights: dict):
+    """(factor_num, deep_layers, cross_layers, use_layer_norm) of a DCN given as a state_dict-keyed mapping."""
+    L = C = 0
+    while f"deep_net.layers.{L}.linear.weight" in weights:
+        L += 1
+    while f"cross_net.layers.{C}.weight" in weights:
+        C += 1
+    if L < 1 or C < 1:
+        raise ValueError("dcn: the weights hold no deep_net.layers.0.linear.weight or no cross_net.layers.0.weight")
+    E = int(weights[USER_KEY].shape[1])
+    return E >> L, L, C, "deep_net.layers.0.layer_norm.weight" in weights
+
+
+def dcn_layout(factor_num: int, deep_layers: int, cross_layers: int, use_layer_norm: bool, user_num: int, item_num: int):
+    """The flat parameter layout of pmgt_dcn_train_grad (include/pmgt_capi.h) -> ({state_dict key: (offset in floats, shape)} in buffer
+    order, parameter count): the user table, the item table, per deep layer W, b[, gamma, beta], per cross layer w[, gamma, beta], then
+    output_layer.weight and .bias.  Every tensor but the last (one float) has a multiple of 8 floats, so every offset is 32-byte aligned.
+    cross_net.layers.c.bias is not in it: it is never read, gets no gradient and is never stepped."""
+    check_dcn_covered(factor_num, deep_layers, cross_layers)
+    if not (isinstance(user_num, (int, np.integer)) and isinstance(item_num, (int, np.integer)) and 1 <= user_num < 2 ** 31 - 1
+            and 1 <= item_num < 2 ** 31 - 1):
+        raise ValueError(f"dcn: user_num = {user_num!r} and item_num = {item_num!r} must be integers in [1, 2^31 - 2]")
+    E = factor_num << deep_layers
+    D = 2 * E
+    shapes = [(USER_KEY, (int(user_num), E)), (ITEM_KEY, (int(item_num), E))]
+    for l in range(deep_layers):
+        out, inn = D >> (l + 1), D >> l
+        shapes += list(zip(deep_keys(l, use_layer_norm), [(out, inn), (out,), (out,), (out,)]))
+    for c in range(cross_layers):
+        shapes += list(zip(cross_keys(c, use_layer_norm), [(D, 1), (D,), (D,)]))
+    shapes += [(OUT_W, (1, D + 2 * factor_num)), (OUT_B, (1,))]
+    layout, at = {}, 0
+    for key, shape in shapes:
+        layout[key] = (at, shape)
+        at += int(np.prod(shape))
+    return layout, at
+
+
+def dcn_layout_slots(layout: dict) -> list:
+    """The offsets of `layout` in the slot order of pmgt_dcn_layout: DCN_TENSORS = 38 slots, -1 for a tensor the model does not have."""
+    slots = [USER_KEY, ITEM_KEY]
+    for l in range(DCN_MAX_DEEP):
+        slots += deep_keys(l, True)
+    for c in range(DCN_MAX_CROSS):
+        slots += cross_keys(c, True)
+    slots += [OUT_W, OUT_B]
+    assert len(slots) == DCN_TENSORS
+    return [layout[k][0] if k in layout else -1 for k in slots]
+
+
+def decays(key: str) -> bool:
+    """get_optimizer's rule (pmgt/base_trainer.py:35-58, no_decay = ["bias", "LayerNorm.weight"]) on the DCN's names: its LayerNorms are
+    called `layer_norm`, so their weights DO decay; a tensor decays unless its name contains "bias"."""
+    return "bias" not in key
+
+
+def check_dcn_pairs(users, items, labels, user_num: int, item_num: int):
+    """check_pairs with the DCN entries' limit of pairs a call."""
+    return check_pairs(users, items, labels, user_num, item_num, max_pairs=DCN_MAX_PAIRS)
+
+
+def _ln(u, gamma, beta, eps):
+    mean = u.mean(axis=1, keepdims=True)
+    cen = u - mean
+    rstd = u.dtype.type(1) / np.sqrt((cen * cen).mean(axis=1, keepdims=True) + u.dtype.type(eps))
+    xhat = cen * rstd
+    return xhat * gamma + beta, xhat, rstd
+
+
+def _ln_bwd(gy, gamma, xhat, rstd):
+    gp = gy * gamma
+    return rstd * (gp - gp.mean(axis=1, keepdims=True) - xhat * (gp * xhat).mean(axis=1, keepdims=True))
+
+
+def _forward(w: dict, users, items, eps: float):
+    """Everything the backward needs: x0, the cross states xs [x^(0) .. x^(C)] with (xhat, rstd) per layer, the deep states."""
+    _, L, C, ln = dcn_shape(w)
+    x0 = np.concatenate([w[USER_KEY][users], w[ITEM_KEY][items]], axis=1)
+    xs, cross = [x0], []
+    for c in range(C):
+        s = xs[-1] @ w[f"cross_net.layers.{c}.weight"].reshape(-1)
+        u = x0 * s[:, None] + x0
+        if ln:
+            p = f"cross_net.layers.{c}.layer_norm."
+            y, xhat, rstd = _ln(u, w[p + "weight"], w[p + "bias"], eps)
+        else:
+            y, xhat, rstd = u, None, None
+        xs.append(y)
+        cross.append((s, xhat, rstd))
+    hs, deep = [x0], []
+    for l in range(L):
+        p = f"deep_net.layers.{l}."
+        a = hs[-1] @ w[p + "linear.weight"].T + w[p + "linear.bias"]
+        if ln:
+            a, xhat, rstd = _ln(a, w[p + "layer_norm.weight"], w[p + "layer_norm.bias"], eps)
+        else:
+            xhat = rstd = None
+        hs.append(np.maximum(a, 0))
+        deep.append((a, xhat, rstd))
+    feat = np.concatenate([xs[-1], hs[-1]], axis=1)
+    z = feat @ w[OUT_W].reshape(-1) + w[OUT_B][0]
+    return x0, xs, cross, hs, deep, feat, z
+
+
+def dcn_head_host(weights: dict, users, items, dtype=np.float64, layer_norm_eps: float = 1e-12) -> np.ndarray:
+    """DCN.forward in eval mode on plain arrays -> logits [n] in `dtype`.  `weights` is keyed like the model's state_dict (arrays or CPU
+    tensors); the LayerNorm is on when its keys are there."""
+    w = head_weights(weights, dtype)
+    users, items = np.asarray(users, dtype=np.int64), np.asarray(items, dtype=np.int64)
+    check_ids("users", users, len(w[USER_KEY]), "dcn")
+    check_ids("items", items, len(w[ITEM_KEY]), "dcn")
+    return _forward(w, users, items, layer_norm_eps)[-1]
+
+
+def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, layer_norm_eps: float = 1e-12):
+    """DCN.forward with dropout 0 on the pairs (users[p], items[p]), the mean BCE-with-logits loss against `labels` and its gradient, every
+    operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}) for every tensor of dcn_layout (the cross layers' unused `bias`
+    has no gradient).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dz = (sigmoid(z) - y) / n with the sigmoid in its overflow-free
+    form, the ReLU passes where h > 0, and embedding rows hit by several pairs are summed in pair order (np.add.at)."""
+    w = head_weights(weights, dtype)
+    F, L, C, ln = dcn_shape(w)
+    users, items, y = check_pairs(users, items, labels, len(w[USER_KEY]), len(w[ITEM_KEY]), max_pairs=1 << 40)
+    y = y.astype(dtype)
+    n, one = len(users), dtype(1)
+    x0, xs, cross, hs, deep, feat, z = _forward(w, users, items, layer_norm_eps)
+    D = x0.shape[1]
+    e = np.exp(-np.abs(z))
+    loss = (np.maximum(z, 0) - z * y + np.log1p(e)).sum(dtype=dtype) / dtype(n)
+    dl = (np.where(z >= 0, one / (one + e), e / (one + e)) - y) / dtype(n)
+    wo = w[OUT_W].reshape(-1)
+    grads = {OUT_W: (dl @ feat).reshape(1, -1), OUT_B: dl.sum(dtype=dtype).reshape(1)}
+    dfeat = dl[:, None] * wo[None, :]
+    g, dx0 = dfeat[:, :D], np.zeros_like(x0)
+    for c in reversed(range(C)):
+        s, xhat, rstd = cross[c]
+        p = f"cross_net.layers.{c}."
+        if ln:
+            grads[p + "layer_norm.weight"] = (g * xhat).sum(axis=0, dtype=dtype)
+            grads[p + "layer_norm.bias"] = g.sum(axis=0, dtype=dtype)
+            g = _ln_bwd(g, w[p + "layer_norm.weight"], xhat, rstd)
+        ds = (g * x0).sum(axis=1, dtype=dtype)
+        dx0 = dx0 + (g * s[:, None] + g)
+        grads[p + "weight"] = (ds @ xs[c]).reshape(-1, 1)
+        g = ds[:, None] * w[p + "weight"].reshape(-1)[None, :]
+    dx0 = dx0 + g                                            # x^(0) is x0
+    dh = dfeat[:, D:]
+    for l in reversed(range(L)):
+        a, xhat, rstd = deep[l]
+        p = f"deep_net.layers.{l}."
+        da = dh * (hs[l + 1] > 0)
+        if ln:
+            grads[p + "layer_norm.weight"] = (da * xhat).sum(axis=0, dtype=dtype)
+            grads[p + "layer_norm.bias"] = da.sum(axis=0, dtype=dtype)
+            da = _ln_bwd(da, w[p + "layer_norm.weight"], xhat, rstd)
+        grads[p + "linear.weight"] = da.T @ hs[l]
+        grads[p + "linear.bias"] = da.sum(axis=0, dtype=dtype)
+        dh = da @ w[p + "linear.weight"]
+    dx0 = dx0 + dh
+    E = D // 2
+    grads[USER_KEY], grads[ITEM_KEY] = np.zeros_like(w[USER_KEY]), np.zeros_like(w[ITEM_KEY])
+    np.add.at(grads[USER_KEY], users, dx0[:, :E])
+    np.add.at(grads[ITEM_KEY], items, dx0[:, E:])
+    assert all(v.dtype == dtype for v in grads.values()) and z.dtype == dtype
+    return dtype(loss), z, grads

@@ -1,0 +1,359 @@
+"""Training and scoring of the Deep & Cross Network on the device: the reference's click-through experiment (scripts/run_dcn.sh,
+pmgt/dcn/trainer.py: item_embeddings initialised from the exported embeddings, one sampled negative per positive every epoch,
+BCEWithLogitsLoss, gradient clipping at 5, AdamW, validation ROC AUC with early stopping).
+
+  DcnGrad       pmgt_dcn_train_grad / pmgt_dcn_forward over one flat parameter buffer (two launches / one)
+  DcnTrainer    every trained parameter, both embedding tables included, in one flat device buffer; step() = the gradient entry +
+                ONE pmgt_op_adamw over the whole buffer (five launches); capture / replay; state_dict
+  evaluate_ctr  logits per batch from pmgt_dcn_forward, ROC AUC of sigmoid(logit) on the device (ValidationMetrics), the mean loss
+  fit_dcn       epochs of sampled pairs, validation AUC / loss, early stopping, the best parameters restored
+
+Dropout is not covered: a model with emb_dropout or dropout != 0 is refused.  The model, the layout and the numpy yardstick are stated in
+dcn_head.py and dcn.py."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnHeadC
+from .dcn_head import (ITEM_KEY, check_dcn_covered, check_dcn_dropout, check_dcn_pairs, dcn_layout, dcn_layout_slots, decays)  # noqa: F401
+from .ncf_head import check_ids
+from .ncf_train import ng_sample, normalize_item_table  # noqa: F401
+
+
+def _model_dims(model):
+    check_dcn_dropout(model.emb_dropout.p, model.dropout_p)
+    check_dcn_covered(model.factor_num, model.deep_layers, model.cross_layers)
+    return (model.factor_num, model.deep_layers, model.cross_layers, model.use_layer_norm, model.user_num, model.item_num)
+
+
+class DcnGrad:
+    """pmgt_dcn_train_grad over one flat parameter buffer: __call__(users, items, labels) writes `grads` whole and returns (loss [1],
+    logits [n]) as device tensors; forward(users, items) is pmgt_dcn_forward -> logits [n], the same bits.  Nothing is copied to the host,
+    nothing waits.  `params` and `grads` are fp32 device tensors of dcn_layout's parameter count (grads None: forward only); the workspace
+    grows to the largest n seen (never inside a capture: call reserve(n) first).  The library's layout is compared with dcn_layout here."""
+
+    def __init__(self, factor_num: int, deep_layers: int, cross_layers: int, use_layer_norm: bool, layer_norm_eps: float, user_num: int,
+                 item_num: int, params, grads=None):
+        import torch
+        self.lib = _lib.hip()
+        self.layout, self.count = dcn_layout(factor_num, deep_layers, cross_layers, use_layer_norm, user_num, item_num)
+        eps = float(np.float32(layer_norm_eps))
+        if not eps >= 0.0:
+            raise ValueError(f"dcn: layer_norm_eps = {layer_norm_eps!r} is NaN or negative")
+        for name, t in (("params", params), ("grads", grads)):
+            if t is None and name == "grads":
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (self.count,)
+                    or not t.is_contiguous() or t.device != params.device):
+                raise ValueError(f"dcn: {name} must be a contiguous fp32 device tensor [{self.count}]")
+        self.params, self.grads = params, grads
+        self.shape = (int(factor_num), int(deep_layers), int(cross_layers), int(bool(use_layer_norm)))
+        self.user_num, self.item_num = int(user_num), int(item_num)
+        self._head = DcnHeadC(*self.shape, eps, 0, self.user_num, self.item_num, params.data_ptr(), None if grads is None else grads.data_ptr())
+        offs = (C.c_int64 * DCN_TENSORS)()
+        count = int(self.lib.pmgt_dcn_layout(*self.shape, self.user_num, self.item_num, offs))
+        if count != self.count or list(offs) != dcn_layout_slots(self.layout):
+            raise RuntimeError("dcn: the library's parameter layout differs from dcn_layout")
+        self._ws, self._ws_pairs = None, 0
+
+    def reserve(self, n: int) -> None:
+        import torch
+        if n <= self._ws_pairs:
+            return
+        nbytes = int(self.lib.pmgt_dcn_workspace_bytes(*self.shape, int(n)))
+        if nbytes < 0:
+            raise ValueError(f"dcn: n = {n} pairs outside [1, {DCN_MAX_PAIRS}]")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dcn: the workspace cannot grow inside a capture; call reserve(n) first")
+        self._ws, self._ws_pairs = torch.empty(nbytes, dtype=torch.uint8, device=self.params.device), int(n)
+
+    def _check(self, tensors):
+        import torch
+        n = int(tensors[0].shape[0])
+        for t, dt in zip(tensors, (torch.int64, torch.int64, torch.float32)):
+            if t.dtype != dt or tuple(t.shape) != (n,) or t.device != self.params.device or not t.is_contiguous():
+                raise ValueError("dcn: users, items (int64) and labels (fp32) must be contiguous [n] tensors on the parameters' device")
+        self.reserve(n)
+        return n
+
+    def __call__(self, users, items, labels, loss=None, logits=None):
+        import torch
+        if self.grads is None:
+            raise ValueError("dcn: this DcnGrad was made without a gradient buffer")
+        n = self._check((users, items, labels))
+        dev = self.params.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
+        logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
+        _lib.check(self.lib.pmgt_dcn_train_grad(C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(),
+                                                logits.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
+        return loss, logits
+
+    def forward(self, users, items, logits=None):
+        import torch
+        n = self._check((users, items))
+        logits = torch.empty(n, dtype=torch.float32, device=self.params.device) if logits is None else logits
+        _lib.check(self.lib.pmgt_dcn_forward(C.byref(self._head), users.data_ptr(), items.data_ptr(), n, logits.data_ptr(), self._ws.data_ptr(),
+                                             self._ws.numel(), _lib.stream()))
+        return logits
+
+
+class DcnTrainer:
+    """AdamW on a dcn.DCN, all on the device.  Every trained parameter -- both embedding tables, the deep net, the cross weights, the
+    LayerNorms, the output layer -- moves into ONE flat fp32 buffer (dcn_layout) and the model's nn.Parameters are re-pointed at views of
+    it, so model.forward and state_dict see the trained weights with no copy.  `cross_net.layers.c.bias`, which the forward never reads,
+    stays an ordinary nn.Parameter outside the buffer: it gets no gradient and no step, as under the reference's optimizer, which skips
+    parameters whose grad is None.  The trainer owns the gradient buffer, exp_avg, exp_avg_sq, the device step counter and the decay
+    mask: a tensor decays unless its name contains "bias" (get_optimizer's rule; the LayerNorms are named layer_norm, so their weights DO
+    decay).  item_init [item_num, E]: copied into item_embeddings first (the DCN-PMGT variant; normalize_item_table for
+    --normalize-item-init-emb).  max_grad_norm None or 0: no clipping.  Dropout is not covered: such a model is refused."""
+
+    def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = None,
+                 item_init=None):
+        import torch
+        import torch.nn as nn
+        dims = _model_dims(model)
+        dev = model.user_embeddings.weight.device
+        if dev.type != "cuda":
+            raise ValueError("dcn: the model must be on a GPU")
+        self.model = model
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = float(max_grad_norm or 0.0)
+        self.layout, self.count = dcn_layout(*dims)
+        E = model.factor_num << model.deep_layers
+        if item_init is not None and (not isinstance(item_init, torch.Tensor) or item_init.dtype != torch.float32
+                                      or tuple(item_init.shape) != (model.item_num, E)):
+            raise ValueError(f"dcn: item_init must be an fp32 tensor [{model.item_num}, {E}]")
+        self.params = torch.zeros(self.count, dtype=torch.float32, device=dev)
+        self.grads = torch.zeros_like(self.params)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.decay = torch.zeros(self.count, dtype=torch.uint8, device=dev)
+        self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
+        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
+        named = dict(model.named_parameters())
+        with torch.no_grad():
+            for key, (off, shape) in self.layout.items():
+                view = self.params[off: off + int(np.prod(shape))].view(shape)
+                view.copy_(item_init.detach() if key == ITEM_KEY and item_init is not None else named[key].detach())
+                mod = model.get_submodule(key.rsplit(".", 1)[0])
+                setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
+                if decays(key):
+                    self.decay[off: off + int(np.prod(shape))] = 1
+        self.grad_fn = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, self.params, self.grads)
+        model._dcn_flat = self.params                        # evaluate_ctr reads the trained parameters in place
+        self._graph = self._static = self._logit_buf = None
+
+    def views(self, flat) -> dict:
+        """{state_dict key: view of `flat`} for a buffer of the layout (params, grads, exp_avg, ...)."""
+        return {k: flat[off: off + int(np.prod(shape))].view(shape) for k, (off, shape) in self.layout.items()}
+
+    def step(self, users, items, labels, loss=None):
+        """One optimizer step on the pairs (device tensors: int64 [n], int64 [n], fp32 [n]; ids inside the tables, check_dcn_pairs checks
+        them on the host) -> the loss before the step as a device tensor [1].  Five launches enqueued; no host copy, no synchronisation."""
+        loss, _ = self.grad_fn(users, items, labels, loss=loss, logits=self._logits(int(users.shape[0])))
+        _lib.check(self.grad_fn.lib.pmgt_op_adamw(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                  self.exp_avg_sq.data_ptr(), self.decay.data_ptr(), self.count, self.lr, self.weight_decay,
+                                                  self.betas[0], self.betas[1], self.eps, self.max_grad_norm, self.step_count.data_ptr(),
+                                                  self._scal.data_ptr(), self._part.data_ptr(), _lib.stream()))
+        return loss
+
+    def _logits(self, n: int):
+        import torch
+        if self._logit_buf is None or self._logit_buf.numel() < n:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("dcn: buffers cannot grow inside a capture")
+            self._logit_buf = torch.empty(n, dtype=torch.float32, device=self.params.device)
+        return self._logit_buf[:n]
+
+    def capture(self, n: int):
+        """Captures step() on `n` pairs into a graph over static input buffers -> (users, items, labels, loss): write a batch into the first
+        three, replay(), read the last.  One stream.  Every buffer is created before the capture, and one warm-up step runs eagerly on the
+        zeroed static batch with the parameters, the moments and the step counter put back afterwards: capturing leaves the state as it was."""
+        import torch
+        if not 1 <= int(n) <= DCN_MAX_PAIRS:
+            raise ValueError(f"dcn: n = {n} pairs outside [1, {DCN_MAX_PAIRS}]")
+        dev = self.params.device
+        self._static = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                        torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        self.grad_fn.reserve(n)
+        self._logits(n)
+        saved = self.state_dict()
+        self.step(*self._static[:3], loss=self._static[3])
+        self.load_state_dict(saved)
+        torch.cuda.synchronize(dev)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.step(*self._static[:3], loss=self._static[3])
+        return self._static
+
+    def replay(self):
+        if self._graph is None:
+            raise RuntimeError("dcn: capture(n) comes before replay()")
+        self._graph.replay()
+        return self._static[3]
+
+    def state_dict(self) -> dict:
+        """The flat parameters, both moments, the step counter and the layout (which names the shape and the LayerNorm setting)."""
+        return {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+                "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        import torch
+        if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
+            raise ValueError("dcn: the state was saved for a model of another shape or LayerNorm setting (the layouts differ)")
+        with torch.no_grad():
+            self.params.copy_(sd["params"])
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+            self.step_count.copy_(sd["step"])
+
+
+def bce_with_logits_host(logits: np.ndarray, labels: np.ndarray) -> float:
+    """The mean of max(z, 0) - z y + log1p(exp(-|z|)) in float64."""
+    z, y = np.asarray(logits, dtype=np.float64), np.asarray(labels, dtype=np.float64)
+    return float((np.maximum(z, 0) - z * y + np.log1p(np.exp(-np.abs(z)))).mean())
+
+
+def _flat_of(model):
+    """The flat parameter buffer a DcnTrainer gave the model, or a fresh one gathered from its parameters."""
+    import torch
+    dims = _model_dims(model)
+    layout, count = dcn_layout(*dims)
+    named = dict(model.named_parameters())
+    first = named[next(iter(layout))]
+    base = getattr(model, "_dcn_flat", None)                 # (a DcnTrainer leaves its parameter buffer here)
+    if (base is not None and tuple(base.shape) == (count,)
+            and all(named[k].data_ptr() == base.data_ptr() + 4 * off for k, (off, _) in layout.items())):
+        return dims, base
+    flat = torch.empty(count, dtype=torch.float32, device=first.device)
+    with torch.no_grad():
+        for k, (off, shape) in layout.items():
+            flat[off: off + int(np.prod(shape))].view(shape).copy_(named[k].detach())
+    return dims, flat
+
+
+def evaluate_ctr(model, users, items, labels, batch_size: int = 256, metrics: str = "device") -> dict:
+    """Click-through evaluation of a dcn.DCN on labelled pairs (numpy: int64 [N], int64 [N], 0 / 1 labels [N]) -> {"auc", "loss", "n"}.
+    The logits come from pmgt_dcn_forward, one call per batch of `batch_size` pairs into one device buffer; nothing is copied per batch.
+    AUC is that of sigmoid(logit) in fp32, as the reference ranks it (_validation_and_test_step):
+      metrics="device"  ValidationMetrics: the sigmoid, the sort and the count on the device, one small copy at the end
+      metrics="host"    the scores ValidationMetrics stored, copied once, through evaluation.roc_auc_score
+    and `loss` is the mean BCE-with-logits over all pairs, in float64 from the logits copied once.  Where the reference turns NaN
+    predictions into 0 (np.nan_to_num), a NaN logit here raises ValueError, as fit_ncf does.  A model a DcnTrainer holds is read in
+    place; another model's parameters are gathered into a flat buffer first."""
+    import torch
+    from .evaluation import roc_auc_score
+    from .metrics import ValidationMetrics
+    if metrics not in ("device", "host"):
+        raise ValueError(f"evaluate_ctr: metrics={metrics!r}: expected 'device' or 'host'")
+    if not 1 <= int(batch_size) <= DCN_MAX_PAIRS:
+        raise ValueError(f"evaluate_ctr: batch_size = {batch_size} outside [1, {DCN_MAX_PAIRS}]")
+    dims, flat = _flat_of(model)
+    users, items, labels = (np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int64),
+                            np.ascontiguousarray(labels, dtype=np.float32))
+    n = len(users)
+    if n < 1 or users.ndim != 1 or items.shape != (n,) or labels.shape != (n,):
+        raise ValueError(f"evaluate_ctr: users {users.shape}, items {items.shape} and labels {labels.shape} must be one [N], N >= 1")
+    check_ids("users", users, model.user_num, "evaluate_ctr")
+    check_ids("items", items, model.item_num, "evaluate_ctr")
+    dev = flat.device
+    fwd = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, flat)
+    users_d, items_d, labels_d = torch.from_numpy(users).to(dev), torch.from_numpy(items).to(dev), torch.from_numpy(labels).to(dev)
+    logits = torch.empty(n, dtype=torch.float32, device=dev)
+    vm = ValidationMetrics(dev, n)
+    for lo in range(0, n, int(batch_size)):
+        hi = min(lo + int(batch_size), n)
+        fwd.forward(users_d[lo:hi], items_d[lo:hi], logits=logits[lo:hi])
+        vm.update(logits[lo:hi], labels_d[lo:hi])
+    if metrics == "device":
+        auc = vm.result()["val/auc"]                         # (raises for NaN scores and for one class)
+        z = logits.cpu().numpy()
+    else:
+        z = logits.cpu().numpy()
+        if np.isnan(z).any():
+            raise ValueError(f"evaluate_ctr: {int(np.isnan(z).sum())} of {n} logits are NaN")
+        auc = roc_auc_score(vm.labels(), vm.scores())
+    if np.isnan(z).any():
+        raise ValueError(f"evaluate_ctr: {int(np.isnan(z).sum())} of {n} logits are NaN")
+    return {"auc": float(auc), "loss": bce_with_logits_host(z, labels), "n": n}
+
+
+def validation_seed(seed: int) -> int:
+    """The seed of fit_dcn's one validation draw: seed - 1 modulo 2^32 (the epochs take seed, seed + 1, ...)."""
+    return (int(seed) - 1) % (1 << 32)
+
+
+def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, num_ng: int = 1, max_sample_items: int = 5, seed: int = 0,
+            early_criterion: str = "auc", patience: int = 10, ckpt_dir: str = None, lr: float = 1e-3, weight_decay: float = 0.0,
+            betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 5.0, eval_batch_size: int = 256, item_init=None, log=None):
+    """Trains `model` (a dcn.DCN on a GPU) on the interaction list `train_pairs` [(user, item)], the reference's click-through fit: every
+    epoch draws ng_sample(train_pairs, num_ng, seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's
+    users, items and labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device
+    and are read once per epoch.  The validation set is ng_sample(valid_pairs, num_ng=max_sample_items, validation_seed(seed)) drawn ONCE before the
+    first epoch -- DCNDataset's valid mode: labelled pairs, no candidate lists -- and judged by evaluate_ctr(metrics="device").  The
+    reference draws its three datasets from one global numpy stream; that order of draws is NOT reproduced (each set has a seed of its
+    own), and a negative is never one of the user's items of THAT list.  early_criterion: "auc" or "loss" (EarlyStopping / BestCheckpoint
+    of fit_loop.py); the best epoch's parameters are restored into the model at the end (and kept as a state_dict file in ckpt_dir when
+    given).  item_init: DcnTrainer's.
+    -> the history, one dict per epoch: epoch, train_loss (mean over the steps), auc, loss, best (whether it improved)."""
+    import torch
+    from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, monitor_of
+    if early_criterion not in ("auc", "loss"):
+        raise ValueError(f"early_criterion={early_criterion!r}: expected 'auc' or 'loss'")
+    if not 1 <= int(batch_size) <= DCN_MAX_PAIRS or max_epochs < 1:
+        raise ValueError(f"fit_dcn: batch_size = {batch_size} outside [1, {DCN_MAX_PAIRS}] or max_epochs = {max_epochs} below 1")
+    _model_dims(model)                                       # (refuses dropout and uncovered shapes before anything is drawn)
+    pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
+    vpairs = np.asarray(valid_pairs, dtype=np.int64).reshape(-1, 2)
+    valid = ng_sample(vpairs, model.user_num, model.item_num, max_sample_items, validation_seed(seed))
+    if len(pairs) < 1:
+        raise ValueError("fit_dcn: no training pair")
+    check_ids("users", pairs[:, 0], model.user_num, "fit_dcn")
+    check_ids("items", pairs[:, 1], model.item_num, "fit_dcn")
+    trainer = DcnTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm, item_init=item_init)
+    dev = trainer.params.device
+    monitor, mode = monitor_of(early_criterion)
+    stopper = EarlyStopping(monitor, patience, mode)
+    keeper = BestCheckpoint(ckpt_dir or "", monitor, mode)
+    if ckpt_dir:
+        os.makedirs(ckpt_dir, exist_ok=True)
+    best_params, history = None, []
+    was_training = model.training
+    model.eval()
+    try:
+        for epoch in range(int(max_epochs)):
+            users, items, labels = ng_sample(pairs, model.user_num, model.item_num, num_ng, seed + epoch)
+            order = epoch_order(len(users), seed, epoch)
+            users_d, items_d, labels_d = (torch.from_numpy(np.ascontiguousarray(a[order])).to(dev) for a in (users, items, labels))
+            n_steps = (len(order) + batch_size - 1) // batch_size
+            losses = torch.empty(n_steps, 1, dtype=torch.float32, device=dev)
+            for s in range(n_steps):
+                lo, hi = s * batch_size, min((s + 1) * batch_size, len(order))
+                trainer.step(users_d[lo:hi], items_d[lo:hi], labels_d[lo:hi], loss=losses[s])
+            try:
+                ev = evaluate_ctr(model, *valid, batch_size=eval_batch_size, metrics="device")
+            except ValueError as e:
+                raise ValueError(f"fit_dcn: epoch {epoch}: validation: {e}") from e
+            row = {"epoch": epoch, "train_loss": float(losses.double().mean().item()), "auc": ev["auc"], "loss": ev["loss"]}
+            write, remove = keeper.update(epoch, row[early_criterion])
+            row["best"] = write is not None
+            if write is not None:
+                best_params = trainer.params.detach().clone()
+                if ckpt_dir:
+                    torch.save({"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+                                "metrics": dict(row)}, write)
+                    if remove and os.path.exists(remove):
+                        os.remove(remove)
+            history.append(row)
+            if log is not None:
+                log(row)
+            if stopper.update(row[early_criterion], epoch):
+                break
+        if best_params is not None:
+            with torch.no_grad():
+                trainer.params.copy_(best_params)
+    finally:
+        model.train(was_training)
+    return history

@@ -1,0 +1,783 @@
+// The Deep & Cross Network of the reference's click-through experiment (pmgt/dcn/models.py; pmgt_dcn_forward and pmgt_dcn_train_grad of
+// include/pmgt_capi.h, where the formulae stand): logits, or loss, logits and the gradient of the mean BCE-with-logits loss with respect to
+// every trained parameter, both embedding tables included, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for
+// ncf_train.hip's reason: the measured step launches nothing of this.  fp32 end to end; the Linear layers and their gradients run on the exact
+// f32-input MFMA (v_mfma_f32_32x32x2_f32) in the pair-major forms of ncf_train.hip (forward Y^T = W X^T, data dX^T = W^T dY^T, weight
+// dW = dY^T X), everything else is ROW WORK: one wave owns one pair's row (up to D = 512 floats, 8 a lane as two 16-byte pieces) and
+// reduces over it with a shuffle butterfly.
+//
+// EVERYTHING IS PAIR-MAJOR in the caller's workspace: x0 [n][D], the deep net's y_l = W_l h_l + b_l, h_(l+1), g_l = d loss / d LN_l's
+// output behind the ReLU and dy_l = d loss / d y_l, each [n][D >> (l + 1)]; the cross net's final x^(C) [n][D] and, with LayerNorm, G_c = d loss
+// / d x^(c+1) [n][D] per layer; four statistics per pair and layer (cross: s_c, mean, rstd, ds_c; deep: -, mean, rstd, -).  The cross
+// states x^(c) themselves are NOT stored: x^(c+1) = ((x0 s_c + x0) - mean) rstd gamma + beta is recomputed from x0 and the statistics by
+// the same sequence of operations wherever it is needed (the file is compiled without contraction, so the bits agree).
+//
+// LAUNCH 1, dcn_pairs_kernel, three roles by block index (the forward entry launches the tiles only, instantiated without the backward):
+//   tile   32 pairs a workgroup of 4 waves.  Gathers x0; deep forward: per layer the MFMA product (the waves share out the 32-feature
+//          blocks) then, per pair row, LayerNorm and ReLU; cross forward per pair row, wave w taking pairs 8 w .. 8 w + 7: the dot with w_c,
+//          x0 s + x0, LayerNorm; the output layer, the loss and dz.  Then back: per deep layer the row pass (ReLU mask, LayerNorm
+//          backward) and the MFMA data gradient, down to d x0's deep part; per pair row the cross chain from layer C - 1 to 0, which adds
+//          its terms in that order, then d x^(0), then the deep part.  A workgroup reads only what it wrote itself, behind a barrier.
+//   rank   the position of every pair in the STABLE order by user id and by item id, counted (n <= 65 536), as ncf_train.hip does.
+//   zero   the gradient rows of the two embedding tables, whole.
+// LAUNCH 2, dcn_grads_kernel, three roles:
+//   weight one workgroup per 32 x 32 block of a layer's dW = dy^T h, 32-pair chunks dealt to the 4 waves in order, added as (w0 + w1) +
+//          (w2 + w3); one more block column against the constant column (1, 0, ..) gives the bias gradient.  The output layer is the
+//          pseudo-layer with dy = [dz, loss of the pair] against [x^(C) ; h_L]: row 0 its weight and bias gradient, row 1 the loss sum.
+//   cols   64 columns a workgroup: gamma, beta and w_c gradients, wave a summing the pairs a, a + 4, .. in order, added the same way.
+//   rows   one wave per position of a stable order; the wave at the start of a run of equal ids adds the run's d x0 halves in pair order.
+// DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+#include "ncf_head.h"
+
+#pragma clang fp contract(off)
+
+namespace pmgt {
+
+static constexpr int DC_THREADS = 256, DC_WAVES = 4, DC_TILE = 32, DC_PER_WAVE = DC_TILE / DC_WAVES;
+static constexpr int DC_MAX_DEEP = PMGT_DCN_MAX_DEEP, DC_MAX_CROSS = PMGT_DCN_MAX_CROSS, DC_ZERO_BLOCKS = 1024;
+static constexpr int DC_MAX_TASKS = DC_MAX_DEEP + 1, DC_MAX_JOBS = 2 * DC_MAX_DEEP + 3 * DC_MAX_CROSS, DC_MAX_E = 256;
+
+struct DcDeep {
+    const float *w, *b, *gamma, *beta;      // [out][in], [out], LayerNorm [out] (NULL without)
+    float *y, *h, *g, *dy, *st;             // workspace [n][out] x 4 (g: LayerNorm only), statistics [n][4]
+    int out, in;
+};
+
+struct DcCross {
+    const float *w, *gamma, *beta;          // [D] each
+    float* G;                               // workspace [n][D]: d loss / d x^(c+1) (LayerNorm only)
+};
+
+struct DcPairsArgs {
+    DcDeep deep[DC_MAX_DEEP];
+    DcCross cross[DC_MAX_CROSS];
+    const float *users_t, *items_t, *wo, *bo;
+    const int64_t *users, *items;
+    const float* labels;
+    float *x0, *xC, *dx0, *cst, *pz;        // workspace: [n][D] x 3, [n][C][4], [n][2] = (dz, loss of the pair)
+    int *order_u, *order_i;
+    float* logits;
+    float* zero_base;
+    int64_t zero_vec4;
+    float eps;
+    int n, E, D, F, L, C, tiles, rank_blocks, zero_blocks;
+};
+
+struct DcTask {
+    const float* a;                         // dy [n][m]
+    const float *b1, *b2;                   // the layer's input [n][w1 + w2] from one or two pair-major sources
+    float *gw, *gb;
+    int m, w1, w2, col_blocks, first, predict;
+};
+
+enum { DC_JOB_SUM = 0, DC_JOB_DEEP_GAMMA = 1, DC_JOB_CROSS_GAMMA = 2, DC_JOB_CROSS_W = 3 };
+
+struct DcJob {
+    const float* a;          // SUM / GAMMA: [n][W]; CROSS_W: ds_c of pair p at a[p * stride]
+    const float* x;          // DEEP_GAMMA: y_l; CROSS_*: x0
+    const float* st;         // the statistics of pair p at st[p * stride + {0: s, 1: mean, 2: rstd}]; CROSS_W: those of layer c - 1, NULL for c = 0
+    const float *gamma, *beta;      // CROSS_W with LayerNorm: of layer c - 1
+    float* out;
+    int W, kind, first, stride;
+};
+
+struct DcGradsArgs {
+    DcTask task[DC_MAX_TASKS];
+    DcJob job[DC_MAX_JOBS];
+    const int64_t *users, *items;
+    const int *order_u, *order_i;
+    const float* dx0;
+    float *g_users, *g_items, *loss;
+    int n, E, ntasks, njobs, weight_blocks, col_blocks, row_blocks;
+};
+
+__device__ __forceinline__ float4 dc_ld4(const float* p, bool ok) {
+    return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float dc_elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+__device__ __forceinline__ int dc_wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ float dc_wave_sum(float x) {      // a butterfly: every lane ends with the same bits
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// ---- a row of W <= 512 floats (W a multiple of 8) on a wave: lane holds the pieces lane and lane + 64, elements k = 4 j + e ----------
+struct DcRow {
+    int col[2];
+    bool ok[2];
+};
+__device__ __forceinline__ DcRow dc_row(int W, int lane) {
+    DcRow r;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) r.col[j] = 4 * (lane + 64 * j), r.ok[j] = r.col[j] < W;
+    return r;
+}
+__device__ __forceinline__ void dc_row_ld(float (&e)[8], const float* p, const DcRow& r) {      // elements outside the row are 0
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const float4 v = dc_ld4(p + r.col[j], r.ok[j]);
+        e[4 * j] = v.x, e[4 * j + 1] = v.y, e[4 * j + 2] = v.z, e[4 * j + 3] = v.w;
+    }
+}
+__device__ __forceinline__ void dc_row_st(float* p, const float (&e)[8], const DcRow& r) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (r.ok[j]) *reinterpret_cast<float4*>(p + r.col[j]) = make_float4(e[4 * j], e[4 * j + 1], e[4 * j + 2], e[4 * j + 3]);
+}
+__device__ __forceinline__ float dc_row_dot(const float (&a)[8], const float (&b)[8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += a[k] * b[k];
+    return dc_wave_sum(s);
+}
+__device__ __forceinline__ float dc_row_sum(const float (&a)[8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += a[k];
+    return dc_wave_sum(s);
+}
+// u -> (u - mean) rstd, the statistics out
+__device__ __forceinline__ void dc_ln_stats(float (&u)[8], const DcRow& r, int W, float eps, float& mean, float& rstd) {
+    mean = dc_row_sum(u) / (float)W;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = r.ok[k >> 2] ? u[k] - mean : 0.f;
+    rstd = 1.f / sqrtf(dc_row_dot(u, u) / (float)W + eps);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = u[k] * rstd;
+}
+// u -> (u - mean) rstd with given statistics (what dc_ln_stats left, bit for bit)
+__device__ __forceinline__ void dc_ln_xhat(float (&u)[8], const DcRow& r, float mean, float rstd) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = (r.ok[k >> 2] ? u[k] - mean : 0.f) * rstd;
+}
+__device__ __forceinline__ void dc_affine(float (&x)[8], const float* gamma, const float* beta, const DcRow& r) {
+    float g[8], b[8];
+    dc_row_ld(g, gamma, r);
+    dc_row_ld(b, beta, r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = x[k] * g[k] + b[k];
+}
+// g = d loss / d LN output -> d loss / d LN input
+__device__ __forceinline__ void dc_ln_bwd(float (&g)[8], const float (&xhat)[8], const float* gamma, const DcRow& r, int W, float rstd) {
+    float gm[8];
+    dc_row_ld(gm, gamma, r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g[k] = g[k] * gm[k];
+    const float m1 = dc_row_sum(g) / (float)W, m2 = dc_row_dot(g, xhat) / (float)W;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g[k] = r.ok[k >> 2] ? rstd * ((g[k] - m1) - xhat[k] * m2) : 0.f;
+}
+// the cross layer's pre-LayerNorm value from x0: x0 s + x0
+__device__ __forceinline__ void dc_cross_u(float (&u)[8], const float (&x0)[8], float s) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = x0[k] * s + x0[k];
+}
+
+// y[pair][0 .. M) = W [M][K] x + bias, x the lane's own pair row (forward_layer of ncf_train.hip without its ReLU; K a multiple of 32)
+__device__ __forceinline__ void dc_linear(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* xrow, bool valid,
+                                          float* yrow, int wave, int lane) {
+    const int p = lane & 31, h = lane >> 5;
+    for (int mb = wave; mb * 32 < M; mb += DC_WAVES) {
+        f32x16 acc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int f = mb * 32 + rho(g) + 4 * h;
+            acc[g] = f < M ? bias[f] : 0.f;
+        }
+        const int m = mb * 32 + p;
+        const float* wrow = W + (int64_t)m * K;
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            float4 a[4], x[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = k0 + 16 * h + 4 * j;
+                a[j] = dc_ld4(wrow + k, m < M && k < K);
+                x[j] = dc_ld4(xrow + k, valid && k < K);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int f = mb * 32 + 8 * q + 4 * h;
+            if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+        }
+    }
+}
+
+// dx[pair][c] = sum_o W[o][c] dy[pair][o] for c in [0, K), W [M][K]
+__device__ __forceinline__ void dc_linear_bwd(const float* __restrict__ W, int M, int K, const float* dy_row, bool valid, float* dx_row, int wave,
+                                              int lane) {
+    const int p = lane & 31, h = lane >> 5;
+    for (int cb = wave; cb * 32 < K; cb += DC_WAVES) {
+        f32x16 acc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+        const int c = cb * 32 + p;
+        for (int o0 = 0; o0 < M; o0 += 32) {
+            float4 z[4];
+            float a[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = dc_ld4(dy_row + o0 + 16 * h + 4 * j, valid && o0 + 16 * h + 4 * j < M);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                const int o = o0 + 16 * h + s;
+                a[s] = (c < K && o < M) ? W[(int64_t)o * K + c] : 0.f;
+            }
+#pragma unroll
+            for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int f = cb * 32 + 8 * q + 4 * h;
+            if (valid && f < K) *reinterpret_cast<float4*>(dx_row + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+        }
+    }
+}
+
+// TRAIN: the gradient entry (the forward entry is the same forward code without the stores and the phases only the backward needs)
+// LN: use_layer_norm
+template <bool TRAIN, bool LN>
+__global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
+    __shared__ float s_dl[DC_TILE];
+    __shared__ int64_t s_ids[DC_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
+    int bid = blockIdx.x;
+    if constexpr (TRAIN) {
+        if (bid >= a.tiles + 2 * a.rank_blocks) {            // ---- zero: the gradients of the two embedding tables, whole
+            float4* z = reinterpret_cast<float4*>(a.zero_base);
+            for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * DC_THREADS + tid; i < a.zero_vec4; i += (int64_t)a.zero_blocks * DC_THREADS)
+                z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+        if (bid >= a.tiles) {                                // ---- rank: the stable order by id, counted
+            bid -= a.tiles;
+            const int kind = bid / a.rank_blocks;
+            const int64_t* ids = kind ? a.items : a.users;
+            int* order = kind ? a.order_i : a.order_u;
+            const int p = (bid - kind * a.rank_blocks) * DC_THREADS + tid;
+            const int64_t mine = p < n ? ids[p] : 0;
+            int rank = 0;
+            for (int q0 = 0; q0 < n; q0 += DC_THREADS) {
+                __syncthreads();
+                s_ids[tid] = q0 + tid < n ? ids[q0 + tid] : 0;
+                __syncthreads();
+                const int cnt = min(DC_THREADS, n - q0);
+                for (int j = 0; j < cnt; ++j) {
+                    const int64_t v = s_ids[j];
+                    rank += (v < mine || (v == mine && q0 + j < p)) ? 1 : 0;
+                }
+            }
+            if (p < n) order[rank] = p;
+            return;
+        }
+    }
+    // ---- tile: 32 pairs
+    const int D = a.D, E = a.E, L = a.L, C = a.C;
+    const int mpair = bid * DC_TILE + (lane & 31);           // the lane's pair in the MFMA phases
+    const bool mvalid = mpair < n;
+    const DcRow rD = dc_row(D, lane);
+    // x0 = [users_t[u] ; items_t[i]]: a piece lies in one half (E is a multiple of 4)
+    for (int i = 0; i < DC_PER_WAVE; ++i) {
+        const int pair = bid * DC_TILE + wave * DC_PER_WAVE + i;
+        if (pair >= n) break;                                // (uniform per wave)
+        const float* urow = a.users_t + a.users[pair] * E;
+        const float* irow = a.items_t + a.items[pair] * E;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (rD.ok[j]) {
+                const int c = rD.col[j];
+                *reinterpret_cast<float4*>(a.x0 + (int64_t)pair * D + c) = *reinterpret_cast<const float4*>(c < E ? urow + c : irow + (c - E));
+            }
+    }
+    __syncthreads();
+    // deep forward
+    for (int l = 0; l < L; ++l) {
+        const DcDeep& dl = a.deep[l];
+        const float* xin = l == 0 ? a.x0 : a.deep[l - 1].h;
+        dc_linear(dl.w, dl.b, dl.out, dl.in, xin + (int64_t)mpair * dl.in, mvalid, dl.y + (int64_t)mpair * dl.out, wave, lane);
+        __syncthreads();
+        const DcRow r = dc_row(dl.out, lane);
+        for (int i = 0; i < DC_PER_WAVE; ++i) {
+            const int pair = bid * DC_TILE + wave * DC_PER_WAVE + i;
+            if (pair >= n) break;
+            float v[8];
+            dc_row_ld(v, dl.y + (int64_t)pair * dl.out, r);
+            if constexpr (LN) {
+                float mean, rstd;
+                dc_ln_stats(v, r, dl.out, a.eps, mean, rstd);
+                dc_affine(v, dl.gamma, dl.beta, r);
+                if constexpr (TRAIN) {
+                    if (lane == 0) dl.st[(int64_t)pair * 4 + 1] = mean, dl.st[(int64_t)pair * 4 + 2] = rstd;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = relu_keep_nan(v[k]);
+            dc_row_st(dl.h + (int64_t)pair * dl.out, v, r);
+        }
+        __syncthreads();
+    }
+    // cross forward, the output layer, the loss
+    const int HW = a.deep[L - 1].out;                        // 2 F
+    const DcRow rH = dc_row(HW, lane);
+    for (int i = 0; i < DC_PER_WAVE; ++i) {
+        const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+        if (pair >= n) {
+            if (TRAIN && lane == 0) s_dl[pl] = 0.f;
+            continue;
+        }
+        float e0[8], x[8], w[8];
+        dc_row_ld(e0, a.x0 + (int64_t)pair * D, rD);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = e0[k];
+        for (int c = 0; c < C; ++c) {
+            dc_row_ld(w, a.cross[c].w, rD);
+            const float s = dc_row_dot(x, w);
+            dc_cross_u(x, e0, s);
+            float mean = 0.f, rstd = 0.f;
+            if constexpr (LN) {
+                dc_ln_stats(x, rD, D, a.eps, mean, rstd);
+                dc_affine(x, a.cross[c].gamma, a.cross[c].beta, rD);
+            }
+            if constexpr (TRAIN) {
+                if (lane == 0) {
+                    float* st = a.cst + ((int64_t)pair * C + c) * 4;
+                    st[0] = s, st[1] = mean, st[2] = rstd;
+                }
+            }
+        }
+        if constexpr (TRAIN) dc_row_st(a.xC + (int64_t)pair * D, x, rD);
+        dc_row_ld(w, a.wo, rD);
+        const float zc = dc_row_dot(x, w);
+        float hrow[8];
+        dc_row_ld(hrow, a.deep[L - 1].h + (int64_t)pair * HW, rH);
+        dc_row_ld(w, a.wo + D, rH);
+        const float z = (zc + dc_row_dot(hrow, w)) + a.bo[0];
+        if (lane == 0) {
+            if (a.logits) a.logits[pair] = z;
+            if constexpr (TRAIN) {
+                const float y = a.labels[pair];
+                const float e = expf(-fabsf(z));
+                const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                const float dz = (sig - y) / (float)n;
+                a.pz[(int64_t)pair * 2] = dz;
+                a.pz[(int64_t)pair * 2 + 1] = (fmaxf(z, 0.f) - z * y) + log1pf(e);
+                s_dl[pl] = dz;
+            }
+        }
+    }
+    if constexpr (!TRAIN) return;
+    __syncthreads();
+    // deep backward
+    for (int l = L - 1; l >= 0; --l) {
+        const DcDeep& dl = a.deep[l];
+        const DcRow r = dc_row(dl.out, lane);
+        for (int i = 0; i < DC_PER_WAVE; ++i) {
+            const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+            if (pair >= n) break;
+            float g[8], hv[8];
+            if (l == L - 1) {
+                dc_row_ld(g, a.wo + D, r);
+                const float dz = s_dl[pl];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) g[k] = dz * g[k];
+            } else {
+                dc_row_ld(g, dl.dy + (int64_t)pair * dl.out, r);      // W_(l+1)^T dy_(l+1), left here by the data gradient below
+            }
+            dc_row_ld(hv, dl.h + (int64_t)pair * dl.out, r);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[k] = hv[k] > 0.f ? g[k] : 0.f;
+            if constexpr (LN) {
+                dc_row_st(dl.g + (int64_t)pair * dl.out, g, r);
+                const float mean = dl.st[(int64_t)pair * 4 + 1], rstd = dl.st[(int64_t)pair * 4 + 2];
+                dc_row_ld(hv, dl.y + (int64_t)pair * dl.out, r);
+                dc_ln_xhat(hv, r, mean, rstd);
+                dc_ln_bwd(g, hv, dl.gamma, r, dl.out, rstd);
+            }
+            dc_row_st(dl.dy + (int64_t)pair * dl.out, g, r);
+        }
+        __syncthreads();
+        float* dst = l == 0 ? a.dx0 : a.deep[l - 1].dy;
+        dc_linear_bwd(dl.w, dl.out, dl.in, dl.dy + (int64_t)mpair * dl.out, mvalid, dst + (int64_t)mpair * dl.in, wave, lane);
+        __syncthreads();
+    }
+    // cross backward and d x0
+    for (int i = 0; i < DC_PER_WAVE; ++i) {
+        const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+        if (pair >= n) break;
+        float e0[8], g[8], acc[8], t[8];
+        dc_row_ld(e0, a.x0 + (int64_t)pair * D, rD);
+        dc_row_ld(g, a.wo, rD);
+        const float dz = s_dl[pl];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) g[k] = dz * g[k], acc[k] = 0.f;
+        for (int c = C - 1; c >= 0; --c) {
+            float* st = a.cst + ((int64_t)pair * C + c) * 4;
+            const float s = st[0];
+            if constexpr (LN) {
+                dc_row_st(a.cross[c].G + (int64_t)pair * D, g, rD);
+                const float mean = st[1], rstd = st[2];
+                dc_cross_u(t, e0, s);
+                dc_ln_xhat(t, rD, mean, rstd);
+                dc_ln_bwd(g, t, a.cross[c].gamma, rD, D, rstd);
+            }
+            const float ds = dc_row_dot(g, e0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] = acc[k] + (g[k] * s + g[k]);
+            if (lane == 0) st[3] = ds;
+            dc_row_ld(t, a.cross[c].w, rD);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[k] = ds * t[k];
+        }
+        dc_row_ld(t, a.dx0 + (int64_t)pair * D, rD);         // the deep net's part
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = (acc[k] + g[k]) + t[k];
+        dc_row_st(a.dx0 + (int64_t)pair * D, acc, rD);
+    }
+}
+
+__device__ __forceinline__ float dc_src_at(const DcTask& t, int pair, int c) {
+    return c < t.w1 ? t.b1[(int64_t)pair * t.w1 + c] : t.b2[(int64_t)pair * t.w2 + (c - t.w1)];
+}
+
+template <bool LN>
+__global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a) {
+    __shared__ float s_acc[DC_WAVES][16][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
+    int bid = blockIdx.x;
+    if (bid >= a.weight_blocks + a.col_blocks) {             // ---- rows: segment sums of d x0's halves in pair order
+        bid -= a.weight_blocks + a.col_blocks;
+        const int kind = bid / a.row_blocks;
+        const int s = (bid - kind * a.row_blocks) * DC_WAVES + wave;
+        if (s >= n) return;
+        const int64_t* ids = kind ? a.items : a.users;
+        const int* order = kind ? a.order_i : a.order_u;
+        const int64_t id = ids[order[s]];
+        if (s > 0 && ids[order[s - 1]] == id) return;        // (uniform per wave) not the start of a run
+        const int E = a.E;
+        const float* src = a.dx0 + (kind ? E : 0);
+        float* dst = (kind ? a.g_items : a.g_users) + id * E;
+        for (int c = lane; c < E; c += 64) {
+            float sum = 0.f;
+            for (int t = s; t < n; ++t) {
+                const int pr = order[t];
+                if (ids[pr] != id) break;
+                sum += src[(int64_t)pr * 2 * E + c];
+            }
+            dst[c] = sum;
+        }
+        return;
+    }
+    if (bid >= a.weight_blocks) {                            // ---- cols: sums over the pairs of 64 columns
+        bid -= a.weight_blocks;
+        int ji = 0;
+        for (int i = 1; i < a.njobs; ++i)
+            if (bid >= a.job[i].first) ji = i;
+        const DcJob& jb = a.job[ji];
+        const int col = (bid - jb.first) * 64 + lane, W = jb.W;
+        const bool ok = col < W;
+        float gam = 0.f, bet = 0.f;
+        if (LN && jb.kind == DC_JOB_CROSS_W && jb.st && ok) gam = jb.gamma[col], bet = jb.beta[col];
+        float sum = 0.f;
+        for (int p = wave; p < n; p += DC_WAVES) {
+            if (!ok) break;
+            const int64_t at = (int64_t)p * W + col;
+            float v;
+            if (jb.kind == DC_JOB_SUM) {
+                v = jb.a[at];
+            } else if (jb.kind == DC_JOB_DEEP_GAMMA) {
+                const float* st = jb.st + (int64_t)p * jb.stride;
+                v = jb.a[at] * ((jb.x[at] - st[1]) * st[2]);
+            } else if (jb.kind == DC_JOB_CROSS_GAMMA) {
+                const float* st = jb.st + (int64_t)p * jb.stride;
+                const float x0 = jb.x[at];
+                v = jb.a[at] * (((x0 * st[0] + x0) - st[1]) * st[2]);
+            } else {
+                float x = jb.x[at];
+                if (jb.st) {                                 // x^(c) from x0 and the statistics of layer c - 1
+                    const float* st = jb.st + (int64_t)p * jb.stride;
+                    x = x * st[0] + x;
+                    if constexpr (LN) x = ((x - st[1]) * st[2]) * gam + bet;
+                }
+                v = jb.a[(int64_t)p * jb.stride] * x;
+            }
+            sum += v;
+        }
+        s_acc[wave][0][lane] = sum;
+        __syncthreads();
+        if (wave == 0 && ok) jb.out[col] = (s_acc[0][0][lane] + s_acc[1][0][lane]) + (s_acc[2][0][lane] + s_acc[3][0][lane]);
+        return;
+    }
+    // ---- weight: one 32 x 32 block of dW = dy^T x, the pairs in order
+    int ti = 0;
+    for (int i = 1; i < a.ntasks; ++i)
+        if (bid >= a.task[i].first) ti = i;
+    const DcTask& t = a.task[ti];
+    const int local = bid - t.first, M = t.m, K = t.w1 + t.w2;
+    const int mb = local / t.col_blocks, nb = local - mb * t.col_blocks;
+    const bool ones = nb == t.col_blocks - 1;
+    const int p = lane & 31, h = lane >> 5, m = mb * 32 + p, c = nb * 32 + p;
+    f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+    for (int ch = wave; ch * 32 < n; ch += DC_WAVES) {
+        float av[16], bv[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int pair = ch * 32 + 16 * h + s;
+            const bool ok = pair < n;
+            av[s] = (ok && m < M) ? t.a[(int64_t)pair * M + m] : 0.f;
+            bv[s] = ones ? (p == 0 ? 1.f : 0.f) : ((ok && c < K) ? dc_src_at(t, pair, c) : 0.f);
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g) s_acc[wave][g][lane] = acc[g];
+    __syncthreads();
+    const int gq = tid >> 6;
+#pragma unroll
+    for (int gg = 0; gg < 4; ++gg) {
+        const int g = gq * 4 + gg;
+        const float v = (s_acc[0][g][lane] + s_acc[1][g][lane]) + (s_acc[2][g][lane] + s_acc[3][g][lane]);
+        const int mo = mb * 32 + rho(g) + 4 * h;
+        if (t.predict) {
+            if (mo == 0) {
+                if (ones) { if (p == 0) t.gb[0] = v; }
+                else if (c < K) t.gw[c] = v;
+            } else if (mo == 1 && ones && p == 0) {
+                a.loss[0] = v / (float)n;
+            }
+        } else if (mo < M) {
+            if (ones) { if (p == 0) t.gb[mo] = v; }
+            else if (c < K) t.gw[(int64_t)mo * K + c] = v;
+        }
+    }
+}
+
+struct DcShape {
+    int F, L, C, ln, E, D;
+    int64_t user_num, item_num;
+};
+
+static int dc_shape(int F, int L, int C, int ln, int64_t user_num, int64_t item_num, const char* who, DcShape* s) {
+    PMGT_CHECK(F == 8 || F == 16 || F == 32 || F == 64, -2, "%s: factor_num = %d, covered: 8, 16, 32, 64", who, F);
+    PMGT_CHECK(L >= 1 && L <= DC_MAX_DEEP, -2, "%s: deep_layers = %d outside [1, %d]", who, L, DC_MAX_DEEP);
+    PMGT_CHECK((F << L) <= DC_MAX_E, -2, "%s: E = factor_num * 2^deep_layers = %d above %d", who, F << L, DC_MAX_E);
+    PMGT_CHECK(C >= 1 && C <= DC_MAX_CROSS, -2, "%s: cross_layers = %d outside [1, %d]", who, C, DC_MAX_CROSS);
+    PMGT_CHECK(ln == 0 || ln == 1, -2, "%s: use_layer_norm = %d, expected 0 or 1", who, ln);
+    PMGT_CHECK(user_num >= 1 && user_num <= 0x7FFFFFFELL, -2, "%s: user_num = %lld outside [1, 2^31 - 2]", who, (long long)user_num);
+    PMGT_CHECK(item_num >= 1 && item_num <= 0x7FFFFFFELL, -2, "%s: item_num = %lld outside [1, 2^31 - 2]", who, (long long)item_num);
+    *s = DcShape{F, L, C, ln, F << L, 2 * (F << L), user_num, item_num};
+    return 0;
+}
+
+// the flat parameter layout: off[PMGT_DCN_TENSORS] in floats (-1 = the model has no such tensor) -> the parameter count
+static int64_t dc_layout(const DcShape& s, int64_t* off) {
+    int64_t at = 0;
+    for (int i = 0; i < PMGT_DCN_TENSORS; ++i) off[i] = -1;
+    off[0] = at, at += s.user_num * s.E;
+    off[1] = at, at += s.item_num * s.E;
+    for (int l = 0; l < s.L; ++l) {
+        const int64_t out = s.D >> (l + 1), in = s.D >> l;
+        off[2 + 4 * l] = at, at += out * in;
+        off[3 + 4 * l] = at, at += out;
+        if (s.ln) {
+            off[4 + 4 * l] = at, at += out;
+            off[5 + 4 * l] = at, at += out;
+        }
+    }
+    for (int c = 0; c < s.C; ++c)
+        for (int j = 0; j < (s.ln ? 3 : 1); ++j) off[18 + 3 * c + j] = at, at += s.D;
+    off[36] = at, at += s.D + 2 * s.F;
+    off[37] = at, at += 1;
+    return at;
+}
+
+// the workspace in floats: x0, x^(C), d x0 [n][D]; G_c [n][D] per cross layer (LayerNorm); the cross statistics [n][C][4]; per deep
+// layer y, h, dy (LayerNorm: and g) [n][out] and the statistics [n][4]; pz [n][2]; the two orders (int [n] each)
+static int64_t dc_workspace_floats(const DcShape& s, int64_t n) {
+    int64_t w = 3 * n * s.D + (s.ln ? s.C * n * s.D : 0) + n * s.C * 4;
+    for (int l = 0; l < s.L; ++l) w += (s.ln ? 4 : 3) * n * (s.D >> (l + 1)) + n * 4;
+    w += (2 * n + 3) / 4 * 4;
+    w += 2 * ((n + 3) / 4 * 4);
+    return w;
+}
+
+static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels,
+                  int64_t n, float* loss, float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+    PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
+    DcShape s;
+    if (int rc = dc_shape(head->factor_num, head->deep_layers, head->cross_layers, head->use_layer_norm, head->user_num, head->item_num, who, &s))
+        return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_DCN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_DCN_MAX_PAIRS);
+    PMGT_CHECK(head->layer_norm_eps >= 0.f, -2, "%s: layer_norm_eps = %g is NaN or negative", who, (double)head->layer_norm_eps);      // (a NaN fails)
+    PMGT_CHECK(head->params && users && items && workspace, -2, "%s: NULL buffer", who);
+    PMGT_CHECK(train ? (head->grads && labels && loss) : logits != nullptr, -2, "%s: NULL buffer", who);
+    PMGT_CHECK((((uintptr_t)head->params | (uintptr_t)(train ? head->grads : nullptr) | (uintptr_t)workspace) & 15) == 0, -2,
+               "%s: the parameters, the gradients and the workspace must be 16-byte aligned", who);
+    PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
+               "%s: misaligned buffer", who);
+    const int64_t need = dc_workspace_floats(s, n) * (int64_t)sizeof(float);
+    PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
+    int64_t off[PMGT_DCN_TENSORS];
+    dc_layout(s, off);
+    const float* P = head->params;
+    float* G = train ? head->grads : nullptr;
+    float* ws = (float*)workspace;
+    const int D = s.D, L = s.L, C = s.C;
+
+    DcPairsArgs pa = {};
+    pa.x0 = ws, ws += n * D;
+    pa.xC = ws, ws += n * D;
+    pa.dx0 = ws, ws += n * D;
+    for (int c = 0; c < C; ++c) {
+        pa.cross[c].w = P + off[18 + 3 * c];
+        pa.cross[c].gamma = s.ln ? P + off[19 + 3 * c] : nullptr;
+        pa.cross[c].beta = s.ln ? P + off[20 + 3 * c] : nullptr;
+        if (s.ln) pa.cross[c].G = ws, ws += n * D;
+    }
+    pa.cst = ws, ws += n * C * 4;
+    for (int l = 0; l < L; ++l) {
+        DcDeep& d = pa.deep[l];
+        d.out = D >> (l + 1), d.in = D >> l;
+        d.w = P + off[2 + 4 * l];
+        d.b = P + off[3 + 4 * l];
+        d.gamma = s.ln ? P + off[4 + 4 * l] : nullptr;
+        d.beta = s.ln ? P + off[5 + 4 * l] : nullptr;
+        d.y = ws, ws += n * d.out;
+        d.h = ws, ws += n * d.out;
+        d.dy = ws, ws += n * d.out;
+        if (s.ln) d.g = ws, ws += n * d.out;
+        d.st = ws, ws += n * 4;
+    }
+    pa.pz = ws, ws += (2 * n + 3) / 4 * 4;
+    pa.order_u = (int*)ws, ws += (n + 3) / 4 * 4;
+    pa.order_i = (int*)ws;
+    pa.users_t = P + off[0], pa.items_t = P + off[1];
+    pa.wo = P + off[36], pa.bo = P + off[37];
+    pa.users = users, pa.items = items, pa.labels = labels, pa.logits = logits;
+    pa.zero_base = G;
+    pa.zero_vec4 = off[2] / 4;                               // the two tables come first; E is a multiple of 8
+    pa.eps = head->layer_norm_eps;
+    pa.n = (int)n, pa.E = s.E, pa.D = D, pa.F = s.F, pa.L = L, pa.C = C;
+    pa.tiles = (int)cdiv64(n, DC_TILE);
+    pa.rank_blocks = (int)cdiv64(n, DC_THREADS);
+    pa.zero_blocks = (int)std::min<int64_t>(DC_ZERO_BLOCKS, cdiv64(pa.zero_vec4, DC_THREADS));
+    hipStream_t st = (hipStream_t)stream;
+    if (!train) {
+        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<false, true>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa);
+        else hipLaunchKernelGGL((dcn_pairs_kernel<false, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa);
+        PMGT_LAUNCH_OK();
+        return 0;
+    }
+
+    DcGradsArgs ga = {};
+    int first = 0;
+    for (int l = 0; l < L; ++l) {
+        DcTask& t = ga.task[l];
+        t.a = pa.deep[l].dy;
+        t.m = pa.deep[l].out;
+        t.b1 = l == 0 ? pa.x0 : pa.deep[l - 1].h, t.w1 = pa.deep[l].in;
+        t.b2 = nullptr, t.w2 = 0;
+        t.gw = G + off[2 + 4 * l];
+        t.gb = G + off[3 + 4 * l];
+        t.col_blocks = (t.w1 + 31) / 32 + 1;
+        t.first = first;
+        t.predict = 0;
+        first += (t.m + 31) / 32 * t.col_blocks;
+    }
+    {
+        DcTask& t = ga.task[L];
+        t.a = pa.pz;
+        t.m = 2;
+        t.b1 = pa.xC, t.w1 = D;
+        t.b2 = pa.deep[L - 1].h, t.w2 = 2 * s.F;
+        t.gw = G + off[36];
+        t.gb = G + off[37];
+        t.col_blocks = (D + 2 * s.F + 31) / 32 + 1;
+        t.first = first;
+        t.predict = 1;
+        first += t.col_blocks;
+    }
+    ga.ntasks = L + 1;
+    ga.weight_blocks = first;
+    int nj = 0, cfirst = 0;
+    auto add_job = [&](int kind, const float* a, const float* x, const float* stp, int stride, const float* gm, const float* bt, float* out, int W) {
+        DcJob& j = ga.job[nj++];
+        j.kind = kind, j.a = a, j.x = x, j.st = stp, j.stride = stride, j.gamma = gm, j.beta = bt, j.out = out, j.W = W, j.first = cfirst;
+        cfirst += (W + 63) / 64;
+    };
+    for (int l = 0; l < L && s.ln; ++l) {
+        const DcDeep& d = pa.deep[l];
+        add_job(DC_JOB_DEEP_GAMMA, d.g, d.y, d.st, 4, nullptr, nullptr, G + off[4 + 4 * l], d.out);
+        add_job(DC_JOB_SUM, d.g, nullptr, nullptr, 0, nullptr, nullptr, G + off[5 + 4 * l], d.out);
+    }
+    for (int c = 0; c < C; ++c) {
+        if (s.ln) {
+            add_job(DC_JOB_CROSS_GAMMA, pa.cross[c].G, pa.x0, pa.cst + 4 * c, 4 * C, nullptr, nullptr, G + off[19 + 3 * c], D);
+            add_job(DC_JOB_SUM, pa.cross[c].G, nullptr, nullptr, 0, nullptr, nullptr, G + off[20 + 3 * c], D);
+        }
+        add_job(DC_JOB_CROSS_W, pa.cst + 4 * c + 3, pa.x0, c ? pa.cst + 4 * (c - 1) : nullptr, 4 * C, c ? pa.cross[c - 1].gamma : nullptr,
+                c ? pa.cross[c - 1].beta : nullptr, G + off[18 + 3 * c], D);
+    }
+    ga.njobs = nj;
+    ga.col_blocks = cfirst;
+    ga.row_blocks = (int)cdiv64(n, DC_WAVES);
+    ga.users = users, ga.items = items;
+    ga.order_u = pa.order_u, ga.order_i = pa.order_i;
+    ga.dx0 = pa.dx0;
+    ga.g_users = G + off[0], ga.g_items = G + off[1];
+    ga.loss = loss;
+    ga.n = (int)n, ga.E = s.E;
+
+    const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
+    if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa);
+    else hipLaunchKernelGGL((dcn_pairs_kernel<true, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa);
+    PMGT_LAUNCH_OK();
+    const unsigned grid2 = (unsigned)(ga.weight_blocks + ga.col_blocks + 2 * ga.row_blocks);
+    if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga);
+    else hipLaunchKernelGGL((dcn_grads_kernel<false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga);
+    PMGT_LAUNCH_OK();
+    return 0;
+}
+
+}  // namespace pmgt
+
+using namespace pmgt;
+
+extern "C" {
+
+int64_t pmgt_dcn_layout(int factor_num, int deep_layers, int cross_layers, int use_layer_norm, int64_t user_num, int64_t item_num,
+                        int64_t* offsets) {
+    DcShape s;
+    if (int rc = dc_shape(factor_num, deep_layers, cross_layers, use_layer_norm, user_num, item_num, "pmgt_dcn_layout", &s)) return rc;
+    int64_t off[PMGT_DCN_TENSORS];
+    const int64_t count = dc_layout(s, off);
+    if (offsets)
+        for (int i = 0; i < PMGT_DCN_TENSORS; ++i) offsets[i] = off[i];
+    return count;
+}
+
+int64_t pmgt_dcn_workspace_bytes(int factor_num, int deep_layers, int cross_layers, int use_layer_norm, int64_t n) {
+    const char* who = "pmgt_dcn_workspace_bytes";
+    DcShape s;
+    if (int rc = dc_shape(factor_num, deep_layers, cross_layers, use_layer_norm, 1, 1, who, &s)) return rc;
+    PMGT_CHECK(n >= 1 && n <= PMGT_DCN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_DCN_MAX_PAIRS);
+    return dc_workspace_floats(s, n) * (int64_t)sizeof(float);
+}
+
+int pmgt_dcn_forward(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, int64_t n, float* logits, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+    return dc_run("pmgt_dcn_forward", false, head, users, items, nullptr, n, nullptr, logits, workspace, workspace_bytes, stream);
+}
+
+int pmgt_dcn_train_grad(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                        float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+    return dc_run("pmgt_dcn_train_grad", true, head, users, items, labels, n, loss, logits, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
