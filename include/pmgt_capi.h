@@ -493,6 +493,38 @@ int pmgt_dcn_forward(const pmgt_dcn_head* head, const int64_t* users, const int6
                      int64_t workspace_bytes, void* stream);
 int pmgt_dcn_train_grad(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
                         float* loss, float* logits /* or NULL */, void* workspace, int64_t workspace_bytes, void* stream);
+/* THE DCN TRAINED WITH DROPOUT (pmgt/dcn/models.py in training mode; scripts/run_dcn.sh passes --emb-dropout 0.2 and both
+ * config/hpo/hpo_dcn*_params.yaml search emb_dropout and dropout over [0, 0.8]).  With m = 0 or 1 / (1 - p), drawn per element:
+ *   x0 = m_e [user_embeddings[u] ; item_embeddings[i]]                                        m_e at p_emb,      [n][D]
+ *   cross   s_c = x^(c) . w_c,  x^(c+1) = LN_c(m_c (x0 s_c) + x0)                             m_c at p_cross[c], [n][D]
+ *           (the added x0 is the already dropped x0 and is not masked again)
+ *   deep    h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))                                         m_l at p_deep[l],  [n][D >> (l + 1)]
+ *           (the dropout sits BEFORE the LayerNorm: dropped zeros enter the layer's statistics)
+ * the output layer and the loss as pmgt_dcn_train_grad states them, and the gradients are those of this function: dy_l = m_l LNbwd(..)
+ * (without LayerNorm the ReLU passes where the DROPPED activation is > 0, with the factor 1 / (1 - p_l)), ds_c = sum_j g_j m_cj x0_j,
+ * d x0 += g (m_c s_c) + g, and d x0 carries m_e down to the embedding rows.  A cross layer whose own mask is drawn has a non-zero gradient
+ * for w_c, and gamma / beta of cross layer c stop being degenerate when p_cross[c + 1] > 0.  THE MASKS come from the engine's counter-based
+ * RNG exactly as pmgt_ncf_train_grad_dropout describes it, over `rng`, a device {seed, step} pair of the caller's own; none is stored: they
+ * are drawn again wherever the backward and the second launch need them.  A site's ROW is the pair's index within the call, its COLUMN the
+ * feature; the SITE IDS (constants of ops/ncf_head.h, mirrored in _lib.py), distinct from each other:
+ *   DCN_SITE_EMB   64       [n][D], the user half first
+ *   DCN_SITE_DEEP  72 + l   [n][D >> (l + 1)], the Linear output of deep layer l
+ *   DCN_SITE_CROSS 80 + c   [n][D], the product x0 s_c of cross layer c
+ * so pmgt_op_dropout_keep with (rng, p, site, n, cols) writes exactly the decisions a call draws, and the call is a pure function of
+ * (inputs, seed, step).  Still two launches, no atomic, no sync, no allocation, the gradient buffer written whole, the same workspace size.
+ * A site with p = 0 draws nothing; with every p equal to 0 the call runs the kernels of pmgt_dcn_train_grad: the same bits, `rng` not read.
+ * Refused (-2) before anything is launched: what pmgt_dcn_train_grad refuses, a NULL drop, a p_emb, p_deep[l < L] or p_cross[c < C] that is
+ * NaN or outside [0, 1), and any p > 0 with a NULL or 8-byte-misaligned rng.
+ * Added without a bump of pmgt_abi_version(): one struct, one entry, nothing existing moved. */
+typedef struct pmgt_dcn_dropout {
+    const uint64_t* rng;                          /* device {seed, step}; read only when a p is > 0 */
+    float p_emb;                                  /* emb_dropout.p: the concatenated input */
+    float p_deep[PMGT_DCN_MAX_DEEP];              /* deep_net.layers[l].dropout.p */
+    float p_cross[PMGT_DCN_MAX_CROSS];            /* cross_net.layers[c].dropout.p */
+} pmgt_dcn_dropout;
+int pmgt_dcn_train_grad_dropout(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                                float* loss, float* logits /* or NULL */, const pmgt_dcn_dropout* drop, void* workspace,
+                                int64_t workspace_bytes, void* stream);
 
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average

@@ -4,10 +4,10 @@ from .configuration_pmgt import PMGTConfig  # noqa: F401
 from .recommend import ncf_head_host, recommend, topk_host  # noqa: F401
 from .ncf_train import (NcfHeadTrainer, fit_ncf, ncf_dropout_keep, ncf_dropout_masks, ncf_head_grad_host, ng_sample,  # noqa: F401
                         normalize_item_table)
-from .dcn_head import check_dcn_covered, dcn_head_grad_host, dcn_head_host, dcn_layout  # noqa: F401
+from .dcn_head import check_dcn_covered, dcn_dropout_masks, dcn_head_grad_host, dcn_head_host, dcn_layout  # noqa: F401
 from .dcn import DCN  # noqa: F401
 from .dcn_train import DcnGrad, DcnTrainer, evaluate_ctr, fit_dcn  # noqa: F401
 
 __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_grad_host", "ng_sample", "NcfHeadTrainer", "fit_ncf",
            "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks", "DCN", "DcnGrad", "DcnTrainer", "evaluate_ctr", "fit_dcn",
-           "check_dcn_covered", "dcn_layout", "dcn_head_host", "dcn_head_grad_host"]
+           "check_dcn_covered", "dcn_layout", "dcn_head_host", "dcn_head_grad_host", "dcn_dropout_masks"]

@@ -103,12 +103,18 @@ class DcnHeadC(C.Structure):
                 ("params", C.c_void_p), ("grads", C.c_void_p)]
 
 
+class DcnDropoutC(C.Structure):
+    """pmgt_dcn_dropout (include/pmgt_capi.h): rng = the device {seed, step} pair."""
+    _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_deep", C.c_float * 4), ("p_cross", C.c_float * 6)]
+
+
 NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
 NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
 NCF_FACTORS, NCF_MAX_D = (8, 16, 32, 64), 256      # the covered heads (pmgt_ncf_score's comment): factor_num, d = factor_num * 2^(num_layers - 1)
 NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS = 65536, 13      # PMGT_NCF_TRAIN_*
 NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER = 64, 65, 72      # NCF_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the trained head; layer l = NCF_SITE_LAYER + l
 DCN_MAX_DEEP, DCN_MAX_CROSS, DCN_TENSORS, DCN_MAX_PAIRS = 4, 6, 38, 65536      # PMGT_DCN_*
+DCN_SITE_EMB, DCN_SITE_DEEP, DCN_SITE_CROSS = 64, 72, 80      # DCN_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the DCN; deep layer l = DCN_SITE_DEEP + l, cross layer c = DCN_SITE_CROSS + c
 DCN_FACTORS, DCN_MAX_E = (8, 16, 32, 64), 256      # the covered shapes (pmgt_dcn_train_grad's comment): factor_num, E = factor_num * 2^deep_layers
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 
@@ -141,6 +147,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
+    "pmgt_dcn_train_grad_dropout",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -311,6 +318,7 @@ def hip():
     L.pmgt_dcn_workspace_bytes.argtypes = [i, i, i, i, i64]
     L.pmgt_dcn_forward.argtypes = [C.POINTER(DcnHeadC), vp, vp, i64, vp, vp, i64, vp]
     L.pmgt_dcn_train_grad.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, i64, vp, vp, vp, i64, vp]
+    L.pmgt_dcn_train_grad_dropout.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, i64, vp, vp, C.POINTER(DcnDropoutC), vp, i64, vp]      # (... logits or NULL, drop ...)
     _hip = L
     return L
 

@@ -7,11 +7,15 @@ With E = F 2^L the embedding width and D = 2 E:
   deep    h_0 = x0,  h_(l+1) = relu(LN_l(W_l h_l + b_l)),  W_l [D >> (l + 1)][D >> l]
   z = output_layer.weight . [x^(C) ; h_L] + output_layer.bias,   loss = mean BCE-with-logits
 LN is torch.nn.LayerNorm (biased variance, (x - mean) / sqrt(var + eps) gamma + beta), absent without use_layer_norm.
+IN TRAINING MODE (pmgt_dcn_train_grad_dropout; masks m = 0 or 1 / (1 - p) per element, dcn_dropout_masks):
+  x0 = m_e [user ; item],   x^(c+1) = LN_c(m_c (x0 s_c) + x0),   h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))
+the added x0 is the dropped x0, not masked again, and the deep dropout sits BEFORE the LayerNorm (dropped zeros enter its statistics).
 Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
-from ._lib import DCN_FACTORS, DCN_MAX_CROSS, DCN_MAX_DEEP, DCN_MAX_E, DCN_MAX_PAIRS, DCN_TENSORS
-from .ncf_head import check_ids, check_pairs, head_weights  # noqa: F401
+from ._lib import (DCN_FACTORS, DCN_MAX_CROSS, DCN_MAX_DEEP, DCN_MAX_E, DCN_MAX_PAIRS, DCN_SITE_CROSS, DCN_SITE_DEEP, DCN_SITE_EMB,
+                   DCN_TENSORS)
+from .ncf_head import check_ids, check_pairs, head_weights, ncf_dropout_keep, ncf_dropout_scale  # noqa: F401
 
 USER_KEY, ITEM_KEY = "user_embeddings.weight", "item_embeddings.weight"
 OUT_W, OUT_B = "output_layer.weight", "output_layer.bias"
@@ -44,6 +48,44 @@ def check_dcn_dropout(emb_dropout: float, dropout: float) -> None:
     if emb_dropout != 0 or dropout != 0:
         raise ValueError(f"dcn: dropout is not covered (emb_dropout = {emb_dropout}, dropout = {dropout}): the trainer, the fit and the "
                          "evaluation are eval-mode arithmetic; set both to 0")
+
+
+def check_dcn_p(p, what: str) -> float:
+    """`p` as the fp32 value the kernels take; ValueError unless it lies in [0, 1) (a NaN does not)."""
+    q = float(np.float32(p))
+    if not 0.0 <= q < 1.0:
+        raise ValueError(f"dcn: {what} = {p!r} outside [0, 1)")
+    return q
+
+
+def dcn_dropout_masks(seed: int, step: int, n: int, factor: int, deep: int, cross: int, p_emb: float, p_deep, p_cross) -> dict:
+    """The masks pmgt_dcn_train_grad_dropout draws for a call on `n` pairs -> {site name: (bool keep [n, cols], fp32 scale)}: "emb" [n, D]
+    (the user half first), "deep<l>" [n, D >> (l + 1)] and "cross<c>" [n, D], by the hash ncf_head.ncf_dropout_keep restates (one RNG for
+    every kernel of the project) at the sites DCN_SITE_EMB, DCN_SITE_DEEP + l, DCN_SITE_CROSS + c; row = the pair's index within the call.
+    p_deep / p_cross: one p for every layer or a sequence of one per layer.  What dcn_head_grad_host(masks=...) applies."""
+    check_dcn_covered(factor, deep, cross)
+    p_deep = [p_deep] * deep if np.isscalar(p_deep) else list(p_deep)
+    p_cross = [p_cross] * cross if np.isscalar(p_cross) else list(p_cross)
+    if len(p_deep) != deep or len(p_cross) != cross:
+        raise ValueError(f"dcn: {len(p_deep)} deep and {len(p_cross)} cross dropouts for {deep} deep and {cross} cross layers")
+    for what, p in [("emb_dropout", p_emb)] + [(f"the dropout of deep layer {l}", p) for l, p in enumerate(p_deep)] + \
+            [(f"the dropout of cross layer {c}", p) for c, p in enumerate(p_cross)]:
+        check_dcn_p(p, what)
+    D = 2 * (factor << deep)
+    masks = {"emb": (ncf_dropout_keep(seed, step, DCN_SITE_EMB, n, D, p_emb), ncf_dropout_scale(p_emb))}
+    for l in range(deep):
+        masks[f"deep{l}"] = (ncf_dropout_keep(seed, step, DCN_SITE_DEEP + l, n, D >> (l + 1), p_deep[l]), ncf_dropout_scale(p_deep[l]))
+    for c in range(cross):
+        masks[f"cross{c}"] = (ncf_dropout_keep(seed, step, DCN_SITE_CROSS + c, n, D, p_cross[c]), ncf_dropout_scale(p_cross[c]))
+    return masks
+
+
+def _mask(masks, site: str, dtype):
+    """keep * scale of `site` in `dtype`, or None: no mask (masks None, or the site missing)"""
+    if masks is None or site not in masks:
+        return None
+    keep, scale = masks[site]
+    return np.asarray(keep).astype(dtype) * dtype(scale)
 
 
 def dcn_shape(weights: dict):
@@ -120,14 +162,21 @@ def _ln_bwd(gy, gamma, xhat, rstd):
     return rstd * (gp - gp.mean(axis=1, keepdims=True) - xhat * (gp * xhat).mean(axis=1, keepdims=True))
 
 
-def _forward(w: dict, users, items, eps: float):
-    """Everything the backward needs: x0, the cross states xs [x^(0) .. x^(C)] with (xhat, rstd) per layer, the deep states."""
+def _forward(w: dict, users, items, eps: float, masks: dict = None):
+    """Everything the backward needs: x0, the cross states xs [x^(0) .. x^(C)] with (xhat, rstd) per layer, the deep states.
+    masks: None (eval mode, today's bits) or dcn_dropout_masks' dict: x0 is then the DROPPED x0 and deep[l][0] the LayerNorm's output
+    over the dropped Linear output."""
     _, L, C, ln = dcn_shape(w)
     x0 = np.concatenate([w[USER_KEY][users], w[ITEM_KEY][items]], axis=1)
+    dtype = x0.dtype.type
+    m = _mask(masks, "emb", dtype)
+    if m is not None:
+        x0 = x0 * m
     xs, cross = [x0], []
     for c in range(C):
         s = xs[-1] @ w[f"cross_net.layers.{c}.weight"].reshape(-1)
-        u = x0 * s[:, None] + x0
+        m = _mask(masks, f"cross{c}", dtype)
+        u = x0 * s[:, None] + x0 if m is None else (x0 * s[:, None]) * m + x0
         if ln:
             p = f"cross_net.layers.{c}.layer_norm."
             y, xhat, rstd = _ln(u, w[p + "weight"], w[p + "bias"], eps)
@@ -139,6 +188,9 @@ def _forward(w: dict, users, items, eps: float):
     for l in range(L):
         p = f"deep_net.layers.{l}."
         a = hs[-1] @ w[p + "linear.weight"].T + w[p + "linear.bias"]
+        m = _mask(masks, f"deep{l}", dtype)
+        if m is not None:
+            a = a * m
         if ln:
             a, xhat, rstd = _ln(a, w[p + "layer_norm.weight"], w[p + "layer_norm.bias"], eps)
         else:
@@ -160,17 +212,20 @@ def dcn_head_host(weights: dict, users, items, dtype=np.float64, layer_norm_eps:
     return _forward(w, users, items, layer_norm_eps)[-1]
 
 
-def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, layer_norm_eps: float = 1e-12):
+def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, layer_norm_eps: float = 1e-12, masks: dict = None):
     """DCN.forward with dropout 0 on the pairs (users[p], items[p]), the mean BCE-with-logits loss against `labels` and its gradient, every
     operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}) for every tensor of dcn_layout (the cross layers' unused `bias`
     has no gradient).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dz = (sigmoid(z) - y) / n with the sigmoid in its overflow-free
-    form, the ReLU passes where h > 0, and embedding rows hit by several pairs are summed in pair order (np.add.at)."""
+    form, the ReLU passes where h > 0, and embedding rows hit by several pairs are summed in pair order (np.add.at).
+    masks: None, or {site: (bool keep [n, cols], scale)} as dcn_dropout_masks names them -- the model in TRAINING mode under these masks,
+    m = keep * scale in `dtype` (the module's header), and the gradients of that function: dy_l = m_l LNbwd(..), ds_c = sum_j g_j m_cj x0_j,
+    d x0 += g (m_c s_c) + g, and d x0 carries m_e to the embedding rows.  A site that is missing is not dropped; None keeps today's bits."""
     w = head_weights(weights, dtype)
     F, L, C, ln = dcn_shape(w)
     users, items, y = check_pairs(users, items, labels, len(w[USER_KEY]), len(w[ITEM_KEY]), max_pairs=1 << 40)
     y = y.astype(dtype)
     n, one = len(users), dtype(1)
-    x0, xs, cross, hs, deep, feat, z = _forward(w, users, items, layer_norm_eps)
+    x0, xs, cross, hs, deep, feat, z = _forward(w, users, items, layer_norm_eps, masks)
     D = x0.shape[1]
     e = np.exp(-np.abs(z))
     loss = (np.maximum(z, 0) - z * y + np.log1p(e)).sum(dtype=dtype) / dtype(n)
@@ -186,8 +241,10 @@ def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, la
             grads[p + "layer_norm.weight"] = (g * xhat).sum(axis=0, dtype=dtype)
             grads[p + "layer_norm.bias"] = g.sum(axis=0, dtype=dtype)
             g = _ln_bwd(g, w[p + "layer_norm.weight"], xhat, rstd)
-        ds = (g * x0).sum(axis=1, dtype=dtype)
-        dx0 = dx0 + (g * s[:, None] + g)
+        m = _mask(masks, f"cross{c}", dtype)
+        gm = g if m is None else g * m                       # d loss / d (x0 s_c)
+        ds = (gm * x0).sum(axis=1, dtype=dtype)
+        dx0 = dx0 + (gm * s[:, None] + g)
         grads[p + "weight"] = (ds @ xs[c]).reshape(-1, 1)
         g = ds[:, None] * w[p + "weight"].reshape(-1)[None, :]
     dx0 = dx0 + g                                            # x^(0) is x0
@@ -200,10 +257,16 @@ def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, la
             grads[p + "layer_norm.weight"] = (da * xhat).sum(axis=0, dtype=dtype)
             grads[p + "layer_norm.bias"] = da.sum(axis=0, dtype=dtype)
             da = _ln_bwd(da, w[p + "layer_norm.weight"], xhat, rstd)
+        m = _mask(masks, f"deep{l}", dtype)
+        if m is not None:
+            da = da * m
         grads[p + "linear.weight"] = da.T @ hs[l]
         grads[p + "linear.bias"] = da.sum(axis=0, dtype=dtype)
         dh = da @ w[p + "linear.weight"]
     dx0 = dx0 + dh
+    m = _mask(masks, "emb", dtype)
+    if m is not None:
+        dx0 = dx0 * m
     E = D // 2
     grads[USER_KEY], grads[ITEM_KEY] = np.zeros_like(w[USER_KEY]), np.zeros_like(w[ITEM_KEY])
     np.add.at(grads[USER_KEY], users, dx0[:, :E])

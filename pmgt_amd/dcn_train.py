@@ -2,40 +2,55 @@
 pmgt/dcn/trainer.py: item_embeddings initialised from the exported embeddings, one sampled negative per positive every epoch,
 BCEWithLogitsLoss, gradient clipping at 5, AdamW, validation ROC AUC with early stopping).
 
-  DcnGrad       pmgt_dcn_train_grad / pmgt_dcn_forward over one flat parameter buffer (two launches / one)
+  DcnGrad       pmgt_dcn_train_grad / pmgt_dcn_forward over one flat parameter buffer (two launches / one); with a dropout setting,
+                pmgt_dcn_train_grad_dropout: the model in training mode, the masks drawn inside the same two launches
   DcnTrainer    every trained parameter, both embedding tables included, in one flat device buffer; step() = the gradient entry +
-                ONE pmgt_op_adamw over the whole buffer (five launches); capture / replay; state_dict
+                ONE pmgt_op_adamw over the whole buffer (five launches); capture / replay; state_dict; with dropout_seed, a model with
+                dropout: its masks come from the device {seed, step} pair that pmgt_op_adamw advances
   evaluate_ctr  logits per batch from pmgt_dcn_forward, ROC AUC of sigmoid(logit) on the device (ValidationMetrics), the mean loss
   fit_dcn       epochs of sampled pairs, validation AUC / loss, early stopping, the best parameters restored
 
-Dropout is not covered: a model with emb_dropout or dropout != 0 is refused.  The model, the layout and the numpy yardstick are stated in
-dcn_head.py and dcn.py."""
+Without dropout_seed a model with emb_dropout or dropout != 0 is refused ("dropout is not covered"); validation, evaluate_ctr and the forward
+entry are eval-mode arithmetic and never drop.  The model, the layout, the masks and the numpy yardstick are stated in dcn_head.py and dcn.py."""
 import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnHeadC
-from .dcn_head import (ITEM_KEY, check_dcn_covered, check_dcn_dropout, check_dcn_pairs, dcn_layout, dcn_layout_slots, decays)  # noqa: F401
+from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnDropoutC, DcnHeadC
+from .dcn_head import (ITEM_KEY, check_dcn_covered, check_dcn_dropout, check_dcn_p, check_dcn_pairs, dcn_dropout_masks, dcn_layout, dcn_layout_slots,  # noqa: F401
+                       decays)
 from .ncf_head import check_ids
 from .ncf_train import ng_sample, normalize_item_table  # noqa: F401
 
 
-def _model_dims(model):
-    check_dcn_dropout(model.emb_dropout.p, model.dropout_p)
+def _model_dims(model, dropout_ok: bool = False):
+    """dropout_ok: the caller runs eval-mode arithmetic on a model a seeded DcnTrainer holds, or is that trainer"""
+    if not dropout_ok:
+        check_dcn_dropout(model.emb_dropout.p, model.dropout_p)
     check_dcn_covered(model.factor_num, model.deep_layers, model.cross_layers)
     return (model.factor_num, model.deep_layers, model.cross_layers, model.use_layer_norm, model.user_num, model.item_num)
+
+
+def model_dropout(model):
+    """(p_emb, [p of every deep layer], [p of every cross layer]) as the model's Dropout modules hold them, each checked to lie in [0, 1)."""
+    p_emb = check_dcn_p(model.emb_dropout.p, "emb_dropout")
+    p_deep = [check_dcn_p(layer.dropout.p, f"the dropout of deep layer {l}") for l, layer in enumerate(model.deep_net.layers)]
+    p_cross = [check_dcn_p(layer.dropout.p, f"the dropout of cross layer {c}") for c, layer in enumerate(model.cross_net.layers)]
+    return p_emb, p_deep, p_cross
 
 
 class DcnGrad:
     """pmgt_dcn_train_grad over one flat parameter buffer: __call__(users, items, labels) writes `grads` whole and returns (loss [1],
     logits [n]) as device tensors; forward(users, items) is pmgt_dcn_forward -> logits [n], the same bits.  Nothing is copied to the host,
     nothing waits.  `params` and `grads` are fp32 device tensors of dcn_layout's parameter count (grads None: forward only); the workspace
-    grows to the largest n seen (never inside a capture: call reserve(n) first).  The library's layout is compared with dcn_layout here."""
+    grows to the largest n seen (never inside a capture: call reserve(n) first).  The library's layout is compared with dcn_layout here.
+    With `dropout` = (rng, p_emb, p_deep, p_cross) the gradient entry is pmgt_dcn_train_grad_dropout, the model in training mode: rng an
+    int64 [2] device tensor {seed, step} that the kernels read at every call, the p's (one, or one per layer) in [0, 1); forward() never drops."""
 
     def __init__(self, factor_num: int, deep_layers: int, cross_layers: int, use_layer_norm: bool, layer_norm_eps: float, user_num: int,
-                 item_num: int, params, grads=None):
+                 item_num: int, params, grads=None, dropout=None):
         import torch
         self.lib = _lib.hip()
         self.layout, self.count = dcn_layout(factor_num, deep_layers, cross_layers, use_layer_norm, user_num, item_num)
@@ -57,6 +72,23 @@ class DcnGrad:
         if count != self.count or list(offs) != dcn_layout_slots(self.layout):
             raise RuntimeError("dcn: the library's parameter layout differs from dcn_layout")
         self._ws, self._ws_pairs = None, 0
+        self.rng = self._drop = None
+        if dropout is not None:
+            rng, p_emb, p_deep, p_cross = dropout
+            if (not isinstance(rng, torch.Tensor) or rng.dtype != torch.int64 or tuple(rng.shape) != (2,) or rng.device != params.device
+                    or not rng.is_contiguous()):
+                raise ValueError("dcn: the dropout rng must be a contiguous int64 tensor [2] = {seed, step} on the parameters' device")
+            p_deep = [p_deep] * self.shape[1] if np.isscalar(p_deep) else list(p_deep)
+            p_cross = [p_cross] * self.shape[2] if np.isscalar(p_cross) else list(p_cross)
+            if len(p_deep) != self.shape[1] or len(p_cross) != self.shape[2]:
+                raise ValueError(f"dcn: {len(p_deep)} deep and {len(p_cross)} cross dropouts for {self.shape[1]} deep and {self.shape[2]} "
+                                 "cross layers")
+            self.rng = rng
+            self._drop = DcnDropoutC(rng.data_ptr(), check_dcn_p(p_emb, "emb_dropout"))
+            for l, p in enumerate(p_deep):
+                self._drop.p_deep[l] = check_dcn_p(p, f"the dropout of deep layer {l}")
+            for c, p in enumerate(p_cross):
+                self._drop.p_cross[c] = check_dcn_p(p, f"the dropout of cross layer {c}")
 
     def reserve(self, n: int) -> None:
         import torch
@@ -86,8 +118,11 @@ class DcnGrad:
         dev = self.params.device
         loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
         logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
-        _lib.check(self.lib.pmgt_dcn_train_grad(C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(),
-                                                logits.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
+        front = (C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(), logits.data_ptr())
+        if self._drop is None:
+            _lib.check(self.lib.pmgt_dcn_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
+        else:
+            _lib.check(self.lib.pmgt_dcn_train_grad_dropout(*front, C.byref(self._drop), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
         return loss, logits
 
     def forward(self, users, items, logits=None):
@@ -107,13 +142,23 @@ class DcnTrainer:
     parameters whose grad is None.  The trainer owns the gradient buffer, exp_avg, exp_avg_sq, the device step counter and the decay
     mask: a tensor decays unless its name contains "bias" (get_optimizer's rule; the LayerNorms are named layer_norm, so their weights DO
     decay).  item_init [item_num, E]: copied into item_embeddings first (the DCN-PMGT variant; normalize_item_table for
-    --normalize-item-init-emb).  max_grad_norm None or 0: no clipping.  Dropout is not covered: such a model is refused."""
+    --normalize-item-init-emb).  max_grad_norm None or 0: no clipping.
+    dropout_seed=<int>: the model is trained WITH ITS DROPOUT (model.emb_dropout.p on the concatenated input, each deep layer's .dropout.p
+    behind its Linear and before its LayerNorm, each cross layer's .dropout.p on x0 s_c; scripts/run_dcn.sh passes --emb-dropout 0.2).
+    step() is then a TRAINING-mode step whatever model.training says (pmgt_dcn_train_grad_dropout); validation, evaluate_ctr and
+    grad_fn.forward stay eval-mode.  The masks come from the project's counter-based RNG over `trainer.rng`, an int64 [2] device tensor
+    {seed, step}, and `step_count` is a view of rng[1:2]: the pmgt_op_adamw call that ends every step advances the mask stream, so eager
+    and replayed steps draw fresh masks with no host write.  Still five launches.  Without a seed a model with dropout is refused."""
 
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = None,
-                 item_init=None):
+                 item_init=None, dropout_seed: int = None):
         import torch
         import torch.nn as nn
-        dims = _model_dims(model)
+        if dropout_seed is not None and (isinstance(dropout_seed, bool) or not isinstance(dropout_seed, (int, np.integer))
+                                         or not -2 ** 63 <= dropout_seed < 2 ** 63):
+            raise ValueError(f"dcn: dropout_seed = {dropout_seed!r} must be an integer that fits int64")
+        dims = _model_dims(model, dropout_ok=dropout_seed is not None)
+        drop_p = None if dropout_seed is None else model_dropout(model)
         dev = model.user_embeddings.weight.device
         if dev.type != "cuda":
             raise ValueError("dcn: the model must be on a GPU")
@@ -128,7 +173,12 @@ class DcnTrainer:
         self.params = torch.zeros(self.count, dtype=torch.float32, device=dev)
         self.grads = torch.zeros_like(self.params)
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        if self.dropout_seed is None:
+            self.rng, self.step_count = None, torch.zeros(1, dtype=torch.int64, device=dev)
+        else:
+            self.rng = torch.tensor([self.dropout_seed, 0], dtype=torch.int64, device=dev)
+            self.step_count = self.rng[1:2]                  # the optimizer's step counter IS the step of the mask stream
         self.decay = torch.zeros(self.count, dtype=torch.uint8, device=dev)
         self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
         self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
@@ -141,8 +191,10 @@ class DcnTrainer:
                 setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
                 if decays(key):
                     self.decay[off: off + int(np.prod(shape))] = 1
-        self.grad_fn = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, self.params, self.grads)
+        self.grad_fn = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, self.params, self.grads,
+                               dropout=None if self.rng is None else (self.rng, *drop_p))
         model._dcn_flat = self.params                        # evaluate_ctr reads the trained parameters in place
+        model._dcn_dropout_seeded = self.rng is not None     # ... and, of a model trained with its dropout, in eval mode
         self._graph = self._static = self._logit_buf = None
 
     def views(self, flat) -> dict:
@@ -195,14 +247,20 @@ class DcnTrainer:
         return self._static[3]
 
     def state_dict(self) -> dict:
-        """The flat parameters, both moments, the step counter and the layout (which names the shape and the LayerNorm setting)."""
-        return {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
-                "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+        """The flat parameters, both moments, the step counter and the layout (which names the shape and the LayerNorm setting); with
+        dropout, the seed (with "step", the whole state of the mask stream)."""
+        sd = {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+              "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
+        if self.dropout_seed is not None:
+            sd["dropout_seed"] = self.dropout_seed
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         import torch
         if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
             raise ValueError("dcn: the state was saved for a model of another shape or LayerNorm setting (the layouts differ)")
+        if sd.get("dropout_seed") != self.dropout_seed:
+            raise ValueError(f"dcn: the state was saved with dropout_seed = {sd.get('dropout_seed')!r}, this trainer has {self.dropout_seed!r}")
         with torch.no_grad():
             self.params.copy_(sd["params"])
             self.exp_avg.copy_(sd["exp_avg"])
@@ -219,7 +277,7 @@ def bce_with_logits_host(logits: np.ndarray, labels: np.ndarray) -> float:
 def _flat_of(model):
     """The flat parameter buffer a DcnTrainer gave the model, or a fresh one gathered from its parameters."""
     import torch
-    dims = _model_dims(model)
+    dims = _model_dims(model, dropout_ok=bool(getattr(model, "_dcn_dropout_seeded", False)))
     layout, count = dcn_layout(*dims)
     named = dict(model.named_parameters())
     first = named[next(iter(layout))]
@@ -242,7 +300,8 @@ def evaluate_ctr(model, users, items, labels, batch_size: int = 256, metrics: st
       metrics="host"    the scores ValidationMetrics stored, copied once, through evaluation.roc_auc_score
     and `loss` is the mean BCE-with-logits over all pairs, in float64 from the logits copied once.  Where the reference turns NaN
     predictions into 0 (np.nan_to_num), a NaN logit here raises ValueError, as fit_ncf does.  A model a DcnTrainer holds is read in
-    place; another model's parameters are gathered into a flat buffer first."""
+    place; another model's parameters are gathered into a flat buffer first.  Always eval-mode arithmetic: a model with dropout is
+    accepted when a DcnTrainer with dropout_seed holds it (it was trained that way and is scored without masks) and refused otherwise."""
     import torch
     from .evaluation import roc_auc_score
     from .metrics import ValidationMetrics
@@ -287,7 +346,8 @@ def validation_seed(seed: int) -> int:
 
 def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, num_ng: int = 1, max_sample_items: int = 5, seed: int = 0,
             early_criterion: str = "auc", patience: int = 10, ckpt_dir: str = None, lr: float = 1e-3, weight_decay: float = 0.0,
-            betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 5.0, eval_batch_size: int = 256, item_init=None, log=None):
+            betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 5.0, eval_batch_size: int = 256, item_init=None, log=None,
+            dropout_seed: int = None):
     """Trains `model` (a dcn.DCN on a GPU) on the interaction list `train_pairs` [(user, item)], the reference's click-through fit: every
     epoch draws ng_sample(train_pairs, num_ng, seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's
     users, items and labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device
@@ -296,7 +356,9 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     reference draws its three datasets from one global numpy stream; that order of draws is NOT reproduced (each set has a seed of its
     own), and a negative is never one of the user's items of THAT list.  early_criterion: "auc" or "loss" (EarlyStopping / BestCheckpoint
     of fit_loop.py); the best epoch's parameters are restored into the model at the end (and kept as a state_dict file in ckpt_dir when
-    given).  item_init: DcnTrainer's.
+    given).  item_init: DcnTrainer's.  dropout_seed=<int> (DcnTrainer's): a model with emb_dropout / dropout > 0 is trained with them, the
+    masks a pure function of the seed and the count of steps taken; validation stays in eval mode and never drops.  Without it such a
+    model is refused.
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), auc, loss, best (whether it improved)."""
     import torch
     from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, monitor_of
@@ -304,7 +366,7 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
         raise ValueError(f"early_criterion={early_criterion!r}: expected 'auc' or 'loss'")
     if not 1 <= int(batch_size) <= DCN_MAX_PAIRS or max_epochs < 1:
         raise ValueError(f"fit_dcn: batch_size = {batch_size} outside [1, {DCN_MAX_PAIRS}] or max_epochs = {max_epochs} below 1")
-    _model_dims(model)                                       # (refuses dropout and uncovered shapes before anything is drawn)
+    _model_dims(model, dropout_ok=dropout_seed is not None)      # (refuses unseeded dropout and uncovered shapes before anything is drawn)
     pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
     vpairs = np.asarray(valid_pairs, dtype=np.int64).reshape(-1, 2)
     valid = ng_sample(vpairs, model.user_num, model.item_num, max_sample_items, validation_seed(seed))
@@ -312,7 +374,8 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
         raise ValueError("fit_dcn: no training pair")
     check_ids("users", pairs[:, 0], model.user_num, "fit_dcn")
     check_ids("items", pairs[:, 1], model.item_num, "fit_dcn")
-    trainer = DcnTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm, item_init=item_init)
+    trainer = DcnTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm, item_init=item_init,
+                         dropout_seed=dropout_seed)
     dev = trainer.params.device
     monitor, mode = monitor_of(early_criterion)
     stopper = EarlyStopping(monitor, patience, mode)

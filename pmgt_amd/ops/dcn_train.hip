@@ -27,6 +27,21 @@
 //   cols   64 columns a workgroup: gamma, beta and w_c gradients, wave a summing the pairs a, a + 4, .. in order, added the same way.
 //   rows   one wave per position of a stable order; the wave at the start of a run of equal ids adds the run's d x0 halves in pair order.
 // DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+//
+// DROPOUT (pmgt_dcn_train_grad_dropout; the DROP instantiations, which alone read the second kernel argument): the model in training
+// mode, every mask m = 0 or 1 / (1 - p) drawn by the counter-based RNG of csrc/common.h at (site, row = the pair, column = the feature):
+//   x0 = m_e [user ; item]   x^(c+1) = LN_c(m_c (x0 s_c) + x0)   h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))
+// No mask is stored.  The gather stores the DROPPED x0 and the deep epilogue the DROPPED y_l, so everything downstream (the row passes,
+// the weight tasks of launch 2) reads dropped operands as they are; m_c is drawn again wherever x^(c+1) is recomputed (the cross
+// backward and the cols role, the same sequence (x0 s) m + x0); back: dy_l = m_l LNbwd(..) (without LayerNorm h > 0 already names the
+// kept elements and the factor 1 / (1 - p_l) suffices), ds_c = sum_j g_j m_cj x0_j, d x0 += g (m_c s_c) + g, and the final d x0 is
+// multiplied by m_e before the store.  A site with p = 0 draws nothing; launch 2 runs its DROP instantiation only when a p_cross is > 0.
+// ARITHMETIC OF THE DROP INSTANTIATIONS of launch 1: the row reductions (s_c, the LayerNorm statistics and the sums of its backward, ds_c,
+// the output layer's dots) add exact products in fp64 and round to fp32 once, and an MFMA chain sums each block of 32 k from 0 and adds
+// the blocks (K / 32 + 16 additions deep instead of K / 2).  With ONE pair in a call nothing averages over pairs and the yardstick's
+// fp32 error is that of single BLAS dot products; the in-order sums of the entries without dropout, whose bits are kept, sit at up to
+// 3.8 x that on their own cases and passed 4 x on 7 of 3 936 cases under the masks.  Statistics are stored and only READ by the second
+// launch, so what it recomputes from them agrees as before.
 #include "ncf_head.h"
 
 #pragma clang fp contract(off)
@@ -91,6 +106,12 @@ struct DcGradsArgs {
     int n, E, ntasks, njobs, weight_blocks, col_blocks, row_blocks;
 };
 
+// the second kernel argument; only the DROP instantiations read it
+struct DcDrop {
+    pmgt_dcn_dropout d;
+    signed char job_cross[DC_MAX_JOBS];      // launch 2, per cols job: the cross layer whose mask its recomputation draws again, -1: none
+};
+
 __device__ __forceinline__ float4 dc_ld4(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
@@ -125,24 +146,46 @@ __device__ __forceinline__ void dc_row_st(float* p, const float (&e)[8], const D
     for (int j = 0; j < 2; ++j)
         if (r.ok[j]) *reinterpret_cast<float4*>(p + r.col[j]) = make_float4(e[4 * j], e[4 * j + 1], e[4 * j + 2], e[4 * j + 3]);
 }
+__device__ __forceinline__ double dc_wave_sum64(double x) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+// HI (the DROP instantiations): the products are exact and the sum runs in fp64, rounded to fp32 once -- a reduction over a row then
+// carries half an ulp instead of the in-order sum's few; the instantiations without dropout keep their arithmetic and their bits
+template <bool HI = false>
 __device__ __forceinline__ float dc_row_dot(const float (&a)[8], const float (&b)[8]) {
+    if constexpr (HI) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += (double)a[k] * (double)b[k];
+        return (float)dc_wave_sum64(s);
+    }
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += a[k] * b[k];
     return dc_wave_sum(s);
 }
+template <bool HI = false>
 __device__ __forceinline__ float dc_row_sum(const float (&a)[8]) {
+    if constexpr (HI) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += (double)a[k];
+        return (float)dc_wave_sum64(s);
+    }
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += a[k];
     return dc_wave_sum(s);
 }
 // u -> (u - mean) rstd, the statistics out
+template <bool HI = false>
 __device__ __forceinline__ void dc_ln_stats(float (&u)[8], const DcRow& r, int W, float eps, float& mean, float& rstd) {
-    mean = dc_row_sum(u) / (float)W;
+    mean = dc_row_sum<HI>(u) / (float)W;
 #pragma unroll
     for (int k = 0; k < 8; ++k) u[k] = r.ok[k >> 2] ? u[k] - mean : 0.f;
-    rstd = 1.f / sqrtf(dc_row_dot(u, u) / (float)W + eps);
+    rstd = 1.f / sqrtf(dc_row_dot<HI>(u, u) / (float)W + eps);
 #pragma unroll
     for (int k = 0; k < 8; ++k) u[k] = u[k] * rstd;
 }
@@ -159,12 +202,13 @@ __device__ __forceinline__ void dc_affine(float (&x)[8], const float* gamma, con
     for (int k = 0; k < 8; ++k) x[k] = x[k] * g[k] + b[k];
 }
 // g = d loss / d LN output -> d loss / d LN input
+template <bool HI = false>
 __device__ __forceinline__ void dc_ln_bwd(float (&g)[8], const float (&xhat)[8], const float* gamma, const DcRow& r, int W, float rstd) {
     float gm[8];
     dc_row_ld(gm, gamma, r);
 #pragma unroll
     for (int k = 0; k < 8; ++k) g[k] = g[k] * gm[k];
-    const float m1 = dc_row_sum(g) / (float)W, m2 = dc_row_dot(g, xhat) / (float)W;
+    const float m1 = dc_row_sum<HI>(g) / (float)W, m2 = dc_row_dot<HI>(g, xhat) / (float)W;
 #pragma unroll
     for (int k = 0; k < 8; ++k) g[k] = r.ok[k >> 2] ? rstd * ((g[k] - m1) - xhat[k] * m2) : 0.f;
 }
@@ -174,9 +218,29 @@ __device__ __forceinline__ void dc_cross_u(float (&u)[8], const float (&x0)[8], 
     for (int k = 0; k < 8; ++k) u[k] = x0[k] * s + x0[k];
 }
 
+// ---- dropout (the DROP instantiations only) ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ DropKey dc_drop_off() { return DropKey{0u, 0u, 0u, 1.f, false}; }
+// the mask of a site on the lane's 8 elements of row `pair`: the pieces lane and lane + 64 are the column groups lane and lane + 64
+__device__ __forceinline__ void dc_row_mask(float (&m)[8], const DropKey& k, int pair, int lane) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float mk[4];
+        drop_mul4(k, (uint32_t)pair, (uint32_t)(lane + 64 * j), mk);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[4 * j + e] = mk[e];
+    }
+}
+// the cross layer's pre-LayerNorm value under the layer's mask: (x0 s) m + x0
+__device__ __forceinline__ void dc_cross_u_drop(float (&u)[8], const float (&x0)[8], float s, const float (&m)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = (x0[k] * s) * m[k] + x0[k];
+}
+
 // y[pair][0 .. M) = W [M][K] x + bias, x the lane's own pair row (forward_layer of ncf_train.hip without its ReLU; K a multiple of 32)
+// DROP: the result is multiplied by the mask of key ky before the store (row = the pair)
+template <bool DROP>
 __device__ __forceinline__ void dc_linear(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* xrow, bool valid,
-                                          float* yrow, int wave, int lane) {
+                                          float* yrow, int wave, int lane, const DropKey& ky, int pair) {
     const int p = lane & 31, h = lane >> 5;
     for (int mb = wave; mb * 32 < M; mb += DC_WAVES) {
         f32x16 acc;
@@ -195,20 +259,44 @@ __device__ __forceinline__ void dc_linear(const float* __restrict__ W, const flo
                 a[j] = dc_ld4(wrow + k, m < M && k < K);
                 x[j] = dc_ld4(xrow + k, valid && k < K);
             }
+            if constexpr (DROP) {                            // a block of 32 k sums from 0 and is added whole: K / 32 + 16 additions deep, not K / 2
+                f32x16 blk;
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+                for (int g = 0; g < 16; ++g) blk[g] = 0.f;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), acc, 0, 0, 0);
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) blk = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), blk, 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < 16; ++g) acc[g] = acc[g] + blk[g];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), acc, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int f = mb * 32 + 8 * q + 4 * h;
-            if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+            if constexpr (DROP) {
+                float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+                if (ky.on) {
+                    float mk[4];
+                    drop_mul4(ky, (uint32_t)pair, (uint32_t)(f >> 2), mk);
+                    v.x *= mk[0], v.y *= mk[1], v.z *= mk[2], v.w *= mk[3];
+                }
+                if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = v;
+            } else {
+                if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+            }
         }
     }
 }
 
 // dx[pair][c] = sum_o W[o][c] dy[pair][o] for c in [0, K), W [M][K]
+// DROP: per block of 32 o, as dc_linear
+template <bool DROP>
 __device__ __forceinline__ void dc_linear_bwd(const float* __restrict__ W, int M, int K, const float* dy_row, bool valid, float* dx_row, int wave,
                                               int lane) {
     const int p = lane & 31, h = lane >> 5;
@@ -227,8 +315,18 @@ __device__ __forceinline__ void dc_linear_bwd(const float* __restrict__ W, int M
                 const int o = o0 + 16 * h + s;
                 a[s] = (c < K && o < M) ? W[(int64_t)o * K + c] : 0.f;
             }
+            if constexpr (DROP) {
+                f32x16 blk;
 #pragma unroll
-            for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), acc, 0, 0, 0);
+                for (int g = 0; g < 16; ++g) blk[g] = 0.f;
+#pragma unroll
+                for (int s = 0; s < 16; ++s) blk = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), blk, 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < 16; ++g) acc[g] = acc[g] + blk[g];
+            } else {
+#pragma unroll
+                for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), acc, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -240,8 +338,9 @@ __device__ __forceinline__ void dc_linear_bwd(const float* __restrict__ W, int M
 
 // TRAIN: the gradient entry (the forward entry is the same forward code without the stores and the phases only the backward needs)
 // LN: use_layer_norm
-template <bool TRAIN, bool LN>
-__global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
+// DROP: dropout is on at one site or more (without it the kernel's instructions are those it had: `dr` is not read)
+template <bool TRAIN, bool LN, bool DROP>
+__global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, DcDrop dr) {
     __shared__ float s_dl[DC_TILE];
     __shared__ int64_t s_ids[DC_THREADS];
     const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
@@ -280,6 +379,8 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
     const int mpair = bid * DC_TILE + (lane & 31);           // the lane's pair in the MFMA phases
     const bool mvalid = mpair < n;
     const DcRow rD = dc_row(D, lane);
+    DropKey kemb = dc_drop_off();
+    if constexpr (DROP) kemb = make_drop_key(DropCfg{dr.d.rng, dr.d.p_emb, DCN_SITE_EMB});
     // x0 = [users_t[u] ; items_t[i]]: a piece lies in one half (E is a multiple of 4)
     for (int i = 0; i < DC_PER_WAVE; ++i) {
         const int pair = bid * DC_TILE + wave * DC_PER_WAVE + i;
@@ -290,7 +391,17 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
         for (int j = 0; j < 2; ++j)
             if (rD.ok[j]) {
                 const int c = rD.col[j];
-                *reinterpret_cast<float4*>(a.x0 + (int64_t)pair * D + c) = *reinterpret_cast<const float4*>(c < E ? urow + c : irow + (c - E));
+                if constexpr (DROP) {                        // the DROPPED x0 is stored: everything downstream reads it
+                    float4 v = *reinterpret_cast<const float4*>(c < E ? urow + c : irow + (c - E));
+                    if (kemb.on) {
+                        float mk[4];
+                        drop_mul4(kemb, (uint32_t)pair, (uint32_t)(c >> 2), mk);
+                        v.x *= mk[0], v.y *= mk[1], v.z *= mk[2], v.w *= mk[3];
+                    }
+                    *reinterpret_cast<float4*>(a.x0 + (int64_t)pair * D + c) = v;
+                } else {
+                    *reinterpret_cast<float4*>(a.x0 + (int64_t)pair * D + c) = *reinterpret_cast<const float4*>(c < E ? urow + c : irow + (c - E));
+                }
             }
     }
     __syncthreads();
@@ -298,7 +409,9 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
     for (int l = 0; l < L; ++l) {
         const DcDeep& dl = a.deep[l];
         const float* xin = l == 0 ? a.x0 : a.deep[l - 1].h;
-        dc_linear(dl.w, dl.b, dl.out, dl.in, xin + (int64_t)mpair * dl.in, mvalid, dl.y + (int64_t)mpair * dl.out, wave, lane);
+        DropKey kdeep = dc_drop_off();                       // DROP: the stored y_l is the dropped one, and the row pass normalises that
+        if constexpr (DROP) kdeep = make_drop_key(DropCfg{dr.d.rng, dr.d.p_deep[l], DCN_SITE_DEEP + (uint32_t)l});
+        dc_linear<DROP>(dl.w, dl.b, dl.out, dl.in, xin + (int64_t)mpair * dl.in, mvalid, dl.y + (int64_t)mpair * dl.out, wave, lane, kdeep, mpair);
         __syncthreads();
         const DcRow r = dc_row(dl.out, lane);
         for (int i = 0; i < DC_PER_WAVE; ++i) {
@@ -308,7 +421,7 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
             dc_row_ld(v, dl.y + (int64_t)pair * dl.out, r);
             if constexpr (LN) {
                 float mean, rstd;
-                dc_ln_stats(v, r, dl.out, a.eps, mean, rstd);
+                dc_ln_stats<DROP>(v, r, dl.out, a.eps, mean, rstd);
                 dc_affine(v, dl.gamma, dl.beta, r);
                 if constexpr (TRAIN) {
                     if (lane == 0) dl.st[(int64_t)pair * 4 + 1] = mean, dl.st[(int64_t)pair * 4 + 2] = rstd;
@@ -335,11 +448,22 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
         for (int k = 0; k < 8; ++k) x[k] = e0[k];
         for (int c = 0; c < C; ++c) {
             dc_row_ld(w, a.cross[c].w, rD);
-            const float s = dc_row_dot(x, w);
-            dc_cross_u(x, e0, s);
+            const float s = dc_row_dot<DROP>(x, w);
+            if constexpr (DROP) {
+                const DropKey kc = make_drop_key(DropCfg{dr.d.rng, dr.d.p_cross[c], DCN_SITE_CROSS + (uint32_t)c});
+                if (kc.on) {
+                    float mk[8];
+                    dc_row_mask(mk, kc, pair, lane);
+                    dc_cross_u_drop(x, e0, s, mk);
+                } else {
+                    dc_cross_u(x, e0, s);
+                }
+            } else {
+                dc_cross_u(x, e0, s);
+            }
             float mean = 0.f, rstd = 0.f;
             if constexpr (LN) {
-                dc_ln_stats(x, rD, D, a.eps, mean, rstd);
+                dc_ln_stats<DROP>(x, rD, D, a.eps, mean, rstd);
                 dc_affine(x, a.cross[c].gamma, a.cross[c].beta, rD);
             }
             if constexpr (TRAIN) {
@@ -351,11 +475,11 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
         }
         if constexpr (TRAIN) dc_row_st(a.xC + (int64_t)pair * D, x, rD);
         dc_row_ld(w, a.wo, rD);
-        const float zc = dc_row_dot(x, w);
+        const float zc = dc_row_dot<DROP>(x, w);
         float hrow[8];
         dc_row_ld(hrow, a.deep[L - 1].h + (int64_t)pair * HW, rH);
         dc_row_ld(w, a.wo + D, rH);
-        const float z = (zc + dc_row_dot(hrow, w)) + a.bo[0];
+        const float z = (zc + dc_row_dot<DROP>(hrow, w)) + a.bo[0];
         if (lane == 0) {
             if (a.logits) a.logits[pair] = z;
             if constexpr (TRAIN) {
@@ -375,6 +499,8 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
     for (int l = L - 1; l >= 0; --l) {
         const DcDeep& dl = a.deep[l];
         const DcRow r = dc_row(dl.out, lane);
+        DropKey kdeep = dc_drop_off();
+        if constexpr (DROP) kdeep = make_drop_key(DropCfg{dr.d.rng, dr.d.p_deep[l], DCN_SITE_DEEP + (uint32_t)l});
         for (int i = 0; i < DC_PER_WAVE; ++i) {
             const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
             if (pair >= n) break;
@@ -395,13 +521,24 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
                 const float mean = dl.st[(int64_t)pair * 4 + 1], rstd = dl.st[(int64_t)pair * 4 + 2];
                 dc_row_ld(hv, dl.y + (int64_t)pair * dl.out, r);
                 dc_ln_xhat(hv, r, mean, rstd);
-                dc_ln_bwd(g, hv, dl.gamma, r, dl.out, rstd);
+                dc_ln_bwd<DROP>(g, hv, dl.gamma, r, dl.out, rstd);
+                if constexpr (DROP) {                        // dy_l = m_l LNbwd(..): the mask drawn again
+                    if (kdeep.on) {
+                        float mk[8];
+                        dc_row_mask(mk, kdeep, pair, lane);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) g[k] = g[k] * mk[k];
+                    }
+                }
+            } else if constexpr (DROP) {                     // h > 0 names the kept elements: the factor 1 / (1 - p_l) suffices
+#pragma unroll
+                for (int k = 0; k < 8; ++k) g[k] = g[k] * kdeep.scale;
             }
             dc_row_st(dl.dy + (int64_t)pair * dl.out, g, r);
         }
         __syncthreads();
         float* dst = l == 0 ? a.dx0 : a.deep[l - 1].dy;
-        dc_linear_bwd(dl.w, dl.out, dl.in, dl.dy + (int64_t)mpair * dl.out, mvalid, dst + (int64_t)mpair * dl.in, wave, lane);
+        dc_linear_bwd<DROP>(dl.w, dl.out, dl.in, dl.dy + (int64_t)mpair * dl.out, mvalid, dst + (int64_t)mpair * dl.in, wave, lane);
         __syncthreads();
     }
     // cross backward and d x0
@@ -417,16 +554,41 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
         for (int c = C - 1; c >= 0; --c) {
             float* st = a.cst + ((int64_t)pair * C + c) * 4;
             const float s = st[0];
-            if constexpr (LN) {
-                dc_row_st(a.cross[c].G + (int64_t)pair * D, g, rD);
-                const float mean = st[1], rstd = st[2];
-                dc_cross_u(t, e0, s);
-                dc_ln_xhat(t, rD, mean, rstd);
-                dc_ln_bwd(g, t, a.cross[c].gamma, rD, D, rstd);
-            }
-            const float ds = dc_row_dot(g, e0);
+            float ds;
+            if constexpr (DROP) {
+                const DropKey kc = make_drop_key(DropCfg{dr.d.rng, dr.d.p_cross[c], DCN_SITE_CROSS + (uint32_t)c});
+                float mk[8];
+                if (kc.on) {
+                    dc_row_mask(mk, kc, pair, lane);
+                } else {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] = acc[k] + (g[k] * s + g[k]);
+                    for (int k = 0; k < 8; ++k) mk[k] = 1.f;
+                }
+                if constexpr (LN) {
+                    dc_row_st(a.cross[c].G + (int64_t)pair * D, g, rD);
+                    const float mean = st[1], rstd = st[2];
+                    if (kc.on) dc_cross_u_drop(t, e0, s, mk);      // the forward's sequence of operations: the same bits
+                    else dc_cross_u(t, e0, s);
+                    dc_ln_xhat(t, rD, mean, rstd);
+                    dc_ln_bwd<true>(g, t, a.cross[c].gamma, rD, D, rstd);
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) t[k] = g[k] * mk[k];      // d loss / d (x0 s_c)
+                ds = dc_row_dot<true>(t, e0);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] = acc[k] + (t[k] * s + g[k]);
+            } else {
+                if constexpr (LN) {
+                    dc_row_st(a.cross[c].G + (int64_t)pair * D, g, rD);
+                    const float mean = st[1], rstd = st[2];
+                    dc_cross_u(t, e0, s);
+                    dc_ln_xhat(t, rD, mean, rstd);
+                    dc_ln_bwd(g, t, a.cross[c].gamma, rD, D, rstd);
+                }
+                ds = dc_row_dot(g, e0);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] = acc[k] + (g[k] * s + g[k]);
+            }
             if (lane == 0) st[3] = ds;
             dc_row_ld(t, a.cross[c].w, rD);
 #pragma unroll
@@ -435,6 +597,13 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a) {
         dc_row_ld(t, a.dx0 + (int64_t)pair * D, rD);         // the deep net's part
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = (acc[k] + g[k]) + t[k];
+        if constexpr (DROP) {                                // d [user ; item] = m_e d x0: the rows role adds what is stored
+            if (kemb.on) {
+                dc_row_mask(t, kemb, pair, lane);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] = acc[k] * t[k];
+            }
+        }
         dc_row_st(a.dx0 + (int64_t)pair * D, acc, rD);
     }
 }
@@ -443,8 +612,10 @@ __device__ __forceinline__ float dc_src_at(const DcTask& t, int pair, int c) {
     return c < t.w1 ? t.b1[(int64_t)pair * t.w1 + c] : t.b2[(int64_t)pair * t.w2 + (c - t.w1)];
 }
 
-template <bool LN>
-__global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a) {
+// DROP: a cross layer's mask is on: the cols role draws it again where it recomputes x^(c) / xhat (the weight and rows roles read stored,
+// already dropped operands and need nothing)
+template <bool LN, bool DROP>
+__global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a, DcDrop dr) {
     __shared__ float s_acc[DC_WAVES][16][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
     int bid = blockIdx.x;
@@ -481,6 +652,11 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a) {
         const bool ok = col < W;
         float gam = 0.f, bet = 0.f;
         if (LN && jb.kind == DC_JOB_CROSS_W && jb.st && ok) gam = jb.gamma[col], bet = jb.beta[col];
+        DropKey kc = dc_drop_off();
+        if constexpr (DROP) {
+            const int mc = dr.job_cross[ji];
+            if (mc >= 0) kc = make_drop_key(DropCfg{dr.d.rng, dr.d.p_cross[mc], DCN_SITE_CROSS + (uint32_t)mc});
+        }
         float sum = 0.f;
         for (int p = wave; p < n; p += DC_WAVES) {
             if (!ok) break;
@@ -494,12 +670,14 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a) {
             } else if (jb.kind == DC_JOB_CROSS_GAMMA) {
                 const float* st = jb.st + (int64_t)p * jb.stride;
                 const float x0 = jb.x[at];
-                v = jb.a[at] * (((x0 * st[0] + x0) - st[1]) * st[2]);
+                if (DROP && kc.on) v = jb.a[at] * ((((x0 * st[0]) * drop_mul1(kc, (uint32_t)p, (uint32_t)col) + x0) - st[1]) * st[2]);
+                else v = jb.a[at] * (((x0 * st[0] + x0) - st[1]) * st[2]);
             } else {
                 float x = jb.x[at];
                 if (jb.st) {                                 // x^(c) from x0 and the statistics of layer c - 1
                     const float* st = jb.st + (int64_t)p * jb.stride;
-                    x = x * st[0] + x;
+                    if (DROP && kc.on) x = (x * st[0]) * drop_mul1(kc, (uint32_t)p, (uint32_t)col) + x;
+                    else x = x * st[0] + x;
                     if constexpr (LN) x = ((x - st[1]) * st[2]) * gam + bet;
                 }
                 v = jb.a[(int64_t)p * jb.stride] * x;
@@ -607,8 +785,9 @@ static int64_t dc_workspace_floats(const DcShape& s, int64_t n) {
     return w;
 }
 
+// every entry; drop: NULL or the dropout of the call (the gradient entry only)
 static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels,
-                  int64_t n, float* loss, float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
+                  int64_t n, float* loss, float* logits, const pmgt_dcn_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream) {
     PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
     DcShape s;
     if (int rc = dc_shape(head->factor_num, head->deep_layers, head->cross_layers, head->use_layer_norm, head->user_num, head->item_num, who, &s))
@@ -623,6 +802,25 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
                "%s: misaligned buffer", who);
     const int64_t need = dc_workspace_floats(s, n) * (int64_t)sizeof(float);
     PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
+    DcDrop dr = {};
+    bool drop_on = false, cross_on = false;                  // every p 0: the instantiations without dropout
+    if (drop) {
+        dr.d.rng = drop->rng, dr.d.p_emb = drop->p_emb;
+        PMGT_CHECK(dr.d.p_emb >= 0.f && dr.d.p_emb < 1.f, -2, "%s: p_emb = %g outside [0, 1)", who, (double)dr.d.p_emb);      // (a NaN fails both)
+        drop_on = dr.d.p_emb > 0.f;
+        for (int l = 0; l < s.L; ++l) {
+            dr.d.p_deep[l] = drop->p_deep[l];
+            PMGT_CHECK(dr.d.p_deep[l] >= 0.f && dr.d.p_deep[l] < 1.f, -2, "%s: p_deep[%d] = %g outside [0, 1)", who, l, (double)dr.d.p_deep[l]);
+            drop_on = drop_on || dr.d.p_deep[l] > 0.f;
+        }
+        for (int c = 0; c < s.C; ++c) {
+            dr.d.p_cross[c] = drop->p_cross[c];
+            PMGT_CHECK(dr.d.p_cross[c] >= 0.f && dr.d.p_cross[c] < 1.f, -2, "%s: p_cross[%d] = %g outside [0, 1)", who, c, (double)dr.d.p_cross[c]);
+            cross_on = cross_on || dr.d.p_cross[c] > 0.f;
+        }
+        drop_on = drop_on || cross_on;
+        PMGT_CHECK(!drop_on || (dr.d.rng && ((uintptr_t)dr.d.rng & 7) == 0), -2, "%s: dropout needs the device {seed, step} pair, 8-byte aligned", who);
+    }
     int64_t off[PMGT_DCN_TENSORS];
     dc_layout(s, off);
     const float* P = head->params;
@@ -669,8 +867,8 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     pa.zero_blocks = (int)std::min<int64_t>(DC_ZERO_BLOCKS, cdiv64(pa.zero_vec4, DC_THREADS));
     hipStream_t st = (hipStream_t)stream;
     if (!train) {
-        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<false, true>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa);
-        else hipLaunchKernelGGL((dcn_pairs_kernel<false, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa);
+        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<false, true, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((dcn_pairs_kernel<false, false, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa, dr);
         PMGT_LAUNCH_OK();
         return 0;
     }
@@ -706,23 +904,25 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     ga.ntasks = L + 1;
     ga.weight_blocks = first;
     int nj = 0, cfirst = 0;
-    auto add_job = [&](int kind, const float* a, const float* x, const float* stp, int stride, const float* gm, const float* bt, float* out, int W) {
+    auto add_job = [&](int kind, const float* a, const float* x, const float* stp, int stride, const float* gm, const float* bt, float* out, int W,
+                       int mask_cross) {                     // mask_cross: the cross layer whose statistics the job recomputes from, -1: none
+        dr.job_cross[nj] = (signed char)mask_cross;
         DcJob& j = ga.job[nj++];
         j.kind = kind, j.a = a, j.x = x, j.st = stp, j.stride = stride, j.gamma = gm, j.beta = bt, j.out = out, j.W = W, j.first = cfirst;
         cfirst += (W + 63) / 64;
     };
     for (int l = 0; l < L && s.ln; ++l) {
         const DcDeep& d = pa.deep[l];
-        add_job(DC_JOB_DEEP_GAMMA, d.g, d.y, d.st, 4, nullptr, nullptr, G + off[4 + 4 * l], d.out);
-        add_job(DC_JOB_SUM, d.g, nullptr, nullptr, 0, nullptr, nullptr, G + off[5 + 4 * l], d.out);
+        add_job(DC_JOB_DEEP_GAMMA, d.g, d.y, d.st, 4, nullptr, nullptr, G + off[4 + 4 * l], d.out, -1);
+        add_job(DC_JOB_SUM, d.g, nullptr, nullptr, 0, nullptr, nullptr, G + off[5 + 4 * l], d.out, -1);
     }
     for (int c = 0; c < C; ++c) {
         if (s.ln) {
-            add_job(DC_JOB_CROSS_GAMMA, pa.cross[c].G, pa.x0, pa.cst + 4 * c, 4 * C, nullptr, nullptr, G + off[19 + 3 * c], D);
-            add_job(DC_JOB_SUM, pa.cross[c].G, nullptr, nullptr, 0, nullptr, nullptr, G + off[20 + 3 * c], D);
+            add_job(DC_JOB_CROSS_GAMMA, pa.cross[c].G, pa.x0, pa.cst + 4 * c, 4 * C, nullptr, nullptr, G + off[19 + 3 * c], D, c);
+            add_job(DC_JOB_SUM, pa.cross[c].G, nullptr, nullptr, 0, nullptr, nullptr, G + off[20 + 3 * c], D, -1);
         }
         add_job(DC_JOB_CROSS_W, pa.cst + 4 * c + 3, pa.x0, c ? pa.cst + 4 * (c - 1) : nullptr, 4 * C, c ? pa.cross[c - 1].gamma : nullptr,
-                c ? pa.cross[c - 1].beta : nullptr, G + off[18 + 3 * c], D);
+                c ? pa.cross[c - 1].beta : nullptr, G + off[18 + 3 * c], D, c - 1);
     }
     ga.njobs = nj;
     ga.col_blocks = cfirst;
@@ -735,12 +935,20 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     ga.n = (int)n, ga.E = s.E;
 
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
-    if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa);
-    else hipLaunchKernelGGL((dcn_pairs_kernel<true, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa);
+    if (drop_on) {
+        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
+    }
+    else if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
+    else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
     PMGT_LAUNCH_OK();
     const unsigned grid2 = (unsigned)(ga.weight_blocks + ga.col_blocks + 2 * ga.row_blocks);
-    if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga);
-    else hipLaunchKernelGGL((dcn_grads_kernel<false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga);
+    if (cross_on) {                                          // (launch 2 draws cross masks only)
+        if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
+        else hipLaunchKernelGGL((dcn_grads_kernel<false, true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
+    }
+    else if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
+    else hipLaunchKernelGGL((dcn_grads_kernel<false, false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
     PMGT_LAUNCH_OK();
     return 0;
 }
@@ -772,12 +980,19 @@ int64_t pmgt_dcn_workspace_bytes(int factor_num, int deep_layers, int cross_laye
 
 int pmgt_dcn_forward(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, int64_t n, float* logits, void* workspace,
                      int64_t workspace_bytes, void* stream) {
-    return dc_run("pmgt_dcn_forward", false, head, users, items, nullptr, n, nullptr, logits, workspace, workspace_bytes, stream);
+    return dc_run("pmgt_dcn_forward", false, head, users, items, nullptr, n, nullptr, logits, nullptr, workspace, workspace_bytes, stream);
 }
 
 int pmgt_dcn_train_grad(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                         float* logits, void* workspace, int64_t workspace_bytes, void* stream) {
-    return dc_run("pmgt_dcn_train_grad", true, head, users, items, labels, n, loss, logits, workspace, workspace_bytes, stream);
+    return dc_run("pmgt_dcn_train_grad", true, head, users, items, labels, n, loss, logits, nullptr, workspace, workspace_bytes, stream);
+}
+
+int pmgt_dcn_train_grad_dropout(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
+                                float* loss, float* logits, const pmgt_dcn_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "pmgt_dcn_train_grad_dropout";
+    PMGT_CHECK(drop != nullptr, -2, "%s: NULL drop", who);
+    return dc_run(who, true, head, users, items, labels, n, loss, logits, drop, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

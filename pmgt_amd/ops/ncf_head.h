@@ -1,5 +1,5 @@
 // What ncf_score.hip and ncf_train.hip share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU, the covered heads, the
-// dropout sites of the trained head.
+// dropout sites of the trained head; dcn_train.hip takes the block order, the ReLU and its own dropout sites from here.
 #pragma once
 #include "../csrc/common.h"
 #include "../../include/pmgt_capi.h"
@@ -11,6 +11,9 @@ static constexpr int NCF_MAX_D = 256;      // the widest layer-0 half: d = facto
 // the dropout sites of the trained head (DropCfg.site; pmgt_ncf_train_grad_dropout of include/pmgt_capi.h, mirrored in _lib.py): the
 // concatenated [user ; item] input, the GMF product, and layer l's output = NCF_SITE_LAYER + l.  Row = the pair's index within the call, column = the feature.
 static constexpr uint32_t NCF_SITE_EMB = 64, NCF_SITE_GMF = 65, NCF_SITE_LAYER = 72;
+// the dropout sites of the Deep & Cross Network (dcn_train.hip; pmgt_dcn_train_grad_dropout of include/pmgt_capi.h, mirrored in _lib.py): the
+// concatenated [user ; item] input, deep layer l's Linear output = DCN_SITE_DEEP + l, cross layer c's product x0 s_c = DCN_SITE_CROSS + c
+static constexpr uint32_t DCN_SITE_EMB = 64, DCN_SITE_DEEP = 72, DCN_SITE_CROSS = 80;
 
 // relu that keeps a NaN (fmaxf would return 0 and hide a broken table from the NaN check of the selection)
 __device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
