@@ -10,12 +10,15 @@ LN is torch.nn.LayerNorm (biased variance, (x - mean) / sqrt(var + eps) gamma + 
 IN TRAINING MODE (pmgt_dcn_train_grad_dropout; masks m = 0 or 1 / (1 - p) per element, dcn_dropout_masks):
   x0 = m_e [user ; item],   x^(c+1) = LN_c(m_c (x0 s_c) + x0),   h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))
 the added x0 is the dropped x0, not masked again, and the deep dropout sits BEFORE the LayerNorm (dropped zeros enter its statistics).
+What the DCN shares with the other pair head, the NCF head -- the id and pair checks, head_weights, the dropout RNG -- lives in pair_train.py.
 Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
 from ._lib import (DCN_FACTORS, DCN_MAX_CROSS, DCN_MAX_DEEP, DCN_MAX_E, DCN_MAX_PAIRS, DCN_SITE_CROSS, DCN_SITE_DEEP, DCN_SITE_EMB,
                    DCN_TENSORS)
-from .ncf_head import check_ids, check_pairs, head_weights, ncf_dropout_keep, ncf_dropout_scale  # noqa: F401
+from .pair_train import check_dropout_p, check_ids, check_pairs, dropout_keep, dropout_scale, head_weights, per_layer
+
+ncf_dropout_keep, ncf_dropout_scale = dropout_keep, dropout_scale      # (the names they were imported under before pair_train.py)
 
 USER_KEY, ITEM_KEY = "user_embeddings.weight", "item_embeddings.weight"
 OUT_W, OUT_B = "output_layer.weight", "output_layer.bias"
@@ -51,32 +54,34 @@ def check_dcn_dropout(emb_dropout: float, dropout: float) -> None:
 
 
 def check_dcn_p(p, what: str) -> float:
-    """`p` as the fp32 value the kernels take; ValueError unless it lies in [0, 1) (a NaN does not)."""
-    q = float(np.float32(p))
-    if not 0.0 <= q < 1.0:
-        raise ValueError(f"dcn: {what} = {p!r} outside [0, 1)")
-    return q
+    """check_dropout_p in the DCN's name."""
+    return check_dropout_p(p, what, "dcn")
+
+
+def dcn_per_layer(p_deep, p_cross, deep: int, cross: int):
+    """(one p per deep layer, one per cross layer) of settings that are one p or a sequence each; the refusal of a sequence of another
+    length names both counts."""
+    n_deep, n_cross = (count if np.isscalar(p) else len(p) for p, count in ((p_deep, deep), (p_cross, cross)))
+    what = f"{n_deep} deep and {n_cross} cross dropouts for {deep} deep and {cross} cross layers"
+    return per_layer(p_deep, deep, what, "dcn"), per_layer(p_cross, cross, what, "dcn")
 
 
 def dcn_dropout_masks(seed: int, step: int, n: int, factor: int, deep: int, cross: int, p_emb: float, p_deep, p_cross) -> dict:
     """The masks pmgt_dcn_train_grad_dropout draws for a call on `n` pairs -> {site name: (bool keep [n, cols], fp32 scale)}: "emb" [n, D]
-    (the user half first), "deep<l>" [n, D >> (l + 1)] and "cross<c>" [n, D], by the hash ncf_head.ncf_dropout_keep restates (one RNG for
+    (the user half first), "deep<l>" [n, D >> (l + 1)] and "cross<c>" [n, D], by the hash pair_train.dropout_keep restates (one RNG for
     every kernel of the project) at the sites DCN_SITE_EMB, DCN_SITE_DEEP + l, DCN_SITE_CROSS + c; row = the pair's index within the call.
     p_deep / p_cross: one p for every layer or a sequence of one per layer.  What dcn_head_grad_host(masks=...) applies."""
     check_dcn_covered(factor, deep, cross)
-    p_deep = [p_deep] * deep if np.isscalar(p_deep) else list(p_deep)
-    p_cross = [p_cross] * cross if np.isscalar(p_cross) else list(p_cross)
-    if len(p_deep) != deep or len(p_cross) != cross:
-        raise ValueError(f"dcn: {len(p_deep)} deep and {len(p_cross)} cross dropouts for {deep} deep and {cross} cross layers")
+    p_deep, p_cross = dcn_per_layer(p_deep, p_cross, deep, cross)
     for what, p in [("emb_dropout", p_emb)] + [(f"the dropout of deep layer {l}", p) for l, p in enumerate(p_deep)] + \
             [(f"the dropout of cross layer {c}", p) for c, p in enumerate(p_cross)]:
         check_dcn_p(p, what)
     D = 2 * (factor << deep)
-    masks = {"emb": (ncf_dropout_keep(seed, step, DCN_SITE_EMB, n, D, p_emb), ncf_dropout_scale(p_emb))}
+    masks = {"emb": (dropout_keep(seed, step, DCN_SITE_EMB, n, D, p_emb), dropout_scale(p_emb))}
     for l in range(deep):
-        masks[f"deep{l}"] = (ncf_dropout_keep(seed, step, DCN_SITE_DEEP + l, n, D >> (l + 1), p_deep[l]), ncf_dropout_scale(p_deep[l]))
+        masks[f"deep{l}"] = (dropout_keep(seed, step, DCN_SITE_DEEP + l, n, D >> (l + 1), p_deep[l]), dropout_scale(p_deep[l]))
     for c in range(cross):
-        masks[f"cross{c}"] = (ncf_dropout_keep(seed, step, DCN_SITE_CROSS + c, n, D, p_cross[c]), ncf_dropout_scale(p_cross[c]))
+        masks[f"cross{c}"] = (dropout_keep(seed, step, DCN_SITE_CROSS + c, n, D, p_cross[c]), dropout_scale(p_cross[c]))
     return masks
 
 
@@ -146,7 +151,7 @@ def decays(key: str) -> bool:
 
 def check_dcn_pairs(users, items, labels, user_num: int, item_num: int):
     """check_pairs with the DCN entries' limit of pairs a call."""
-    return check_pairs(users, items, labels, user_num, item_num, max_pairs=DCN_MAX_PAIRS)
+    return check_pairs(users, items, labels, user_num, item_num, max_pairs=DCN_MAX_PAIRS, who="dcn")
 
 
 def _ln(u, gamma, beta, eps):

@@ -11,18 +11,18 @@ BCEWithLogitsLoss, gradient clipping at 5, AdamW, validation ROC AUC with early 
   fit_dcn       epochs of sampled pairs, validation AUC / loss, early stopping, the best parameters restored
 
 Without dropout_seed a model with emb_dropout or dropout != 0 is refused ("dropout is not covered"); validation, evaluate_ctr and the forward
-entry are eval-mode arithmetic and never drop.  The model, the layout, the masks and the numpy yardstick are stated in dcn_head.py and dcn.py."""
+entry are eval-mode arithmetic and never drop.  The model, the layout, the masks and the numpy yardstick are stated in dcn_head.py and dcn.py;
+what this training shares with the NCF head's -- ng_sample, the bases PairGrad and PairTrainer, the epoch loop fit_pairs -- lives in pair_train.py."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnDropoutC, DcnHeadC
+from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnDropoutC, DcnHeadC  # noqa: F401
 from .dcn_head import (ITEM_KEY, check_dcn_covered, check_dcn_dropout, check_dcn_p, check_dcn_pairs, dcn_dropout_masks, dcn_layout, dcn_layout_slots,  # noqa: F401
-                       decays)
-from .ncf_head import check_ids
-from .ncf_train import ng_sample, normalize_item_table  # noqa: F401
+                       dcn_per_layer, decays)
+from .pair_train import (PairGrad, PairTrainer, bce_with_logits_host, check_ids, check_seed, fit_pairs, ng_sample,  # noqa: F401
+                         normalize_item_table)
 
 
 def _model_dims(model, dropout_ok: bool = False):
@@ -41,7 +41,7 @@ def model_dropout(model):
     return p_emb, p_deep, p_cross
 
 
-class DcnGrad:
+class DcnGrad(PairGrad):
     """pmgt_dcn_train_grad over one flat parameter buffer: __call__(users, items, labels) writes `grads` whole and returns (loss [1],
     logits [n]) as device tensors; forward(users, items) is pmgt_dcn_forward -> logits [n], the same bits.  Nothing is copied to the host,
     nothing waits.  `params` and `grads` are fp32 device tensors of dcn_layout's parameter count (grads None: forward only); the workspace
@@ -49,81 +49,33 @@ class DcnGrad:
     With `dropout` = (rng, p_emb, p_deep, p_cross) the gradient entry is pmgt_dcn_train_grad_dropout, the model in training mode: rng an
     int64 [2] device tensor {seed, step} that the kernels read at every call, the p's (one, or one per layer) in [0, 1); forward() never drops."""
 
+    who, where, max_pairs = "dcn", "the parameters' device", DCN_MAX_PAIRS
+    flat_text = "dcn: {name} must be a contiguous fp32 device tensor [{count}]"
+    layout_entry, layout_name, slots = "pmgt_dcn_layout", "dcn_layout", staticmethod(dcn_layout_slots)
+
     def __init__(self, factor_num: int, deep_layers: int, cross_layers: int, use_layer_norm: bool, layer_norm_eps: float, user_num: int,
                  item_num: int, params, grads=None, dropout=None):
-        import torch
-        self.lib = _lib.hip()
+        lib = self.lib = _lib.hip()
         self.layout, self.count = dcn_layout(factor_num, deep_layers, cross_layers, use_layer_norm, user_num, item_num)
         eps = float(np.float32(layer_norm_eps))
         if not eps >= 0.0:
             raise ValueError(f"dcn: layer_norm_eps = {layer_norm_eps!r} is NaN or negative")
-        for name, t in (("params", params), ("grads", grads)):
-            if t is None and name == "grads":
-                continue
-            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (self.count,)
-                    or not t.is_contiguous() or t.device != params.device):
-                raise ValueError(f"dcn: {name} must be a contiguous fp32 device tensor [{self.count}]")
-        self.params, self.grads = params, grads
-        self.shape = (int(factor_num), int(deep_layers), int(cross_layers), int(bool(use_layer_norm)))
-        self.user_num, self.item_num = int(user_num), int(item_num)
+        super().__init__((int(factor_num), int(deep_layers), int(cross_layers), int(bool(use_layer_norm))), user_num, item_num, params, grads,
+                         params.device if getattr(params, "is_cuda", False) else None)      # (None: no tensor is on it, params is refused)
         self._head = DcnHeadC(*self.shape, eps, 0, self.user_num, self.item_num, params.data_ptr(), None if grads is None else grads.data_ptr())
-        offs = (C.c_int64 * DCN_TENSORS)()
-        count = int(self.lib.pmgt_dcn_layout(*self.shape, self.user_num, self.item_num, offs))
-        if count != self.count or list(offs) != dcn_layout_slots(self.layout):
-            raise RuntimeError("dcn: the library's parameter layout differs from dcn_layout")
-        self._ws, self._ws_pairs = None, 0
-        self.rng = self._drop = None
+        self._sizing = lib.pmgt_dcn_workspace_bytes
+        if grads is not None:
+            self._entry = lib.pmgt_dcn_train_grad
         if dropout is not None:
             rng, p_emb, p_deep, p_cross = dropout
-            if (not isinstance(rng, torch.Tensor) or rng.dtype != torch.int64 or tuple(rng.shape) != (2,) or rng.device != params.device
-                    or not rng.is_contiguous()):
-                raise ValueError("dcn: the dropout rng must be a contiguous int64 tensor [2] = {seed, step} on the parameters' device")
-            p_deep = [p_deep] * self.shape[1] if np.isscalar(p_deep) else list(p_deep)
-            p_cross = [p_cross] * self.shape[2] if np.isscalar(p_cross) else list(p_cross)
-            if len(p_deep) != self.shape[1] or len(p_cross) != self.shape[2]:
-                raise ValueError(f"dcn: {len(p_deep)} deep and {len(p_cross)} cross dropouts for {self.shape[1]} deep and {self.shape[2]} "
-                                 "cross layers")
-            self.rng = rng
-            self._drop = DcnDropoutC(rng.data_ptr(), check_dcn_p(p_emb, "emb_dropout"))
+            rng_ptr = self._check_rng(rng)
+            p_deep, p_cross = dcn_per_layer(p_deep, p_cross, self.shape[1], self.shape[2])
+            self._drop = DcnDropoutC(rng_ptr, check_dcn_p(p_emb, "emb_dropout"))
             for l, p in enumerate(p_deep):
                 self._drop.p_deep[l] = check_dcn_p(p, f"the dropout of deep layer {l}")
             for c, p in enumerate(p_cross):
                 self._drop.p_cross[c] = check_dcn_p(p, f"the dropout of cross layer {c}")
-
-    def reserve(self, n: int) -> None:
-        import torch
-        if n <= self._ws_pairs:
-            return
-        nbytes = int(self.lib.pmgt_dcn_workspace_bytes(*self.shape, int(n)))
-        if nbytes < 0:
-            raise ValueError(f"dcn: n = {n} pairs outside [1, {DCN_MAX_PAIRS}]")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("dcn: the workspace cannot grow inside a capture; call reserve(n) first")
-        self._ws, self._ws_pairs = torch.empty(nbytes, dtype=torch.uint8, device=self.params.device), int(n)
-
-    def _check(self, tensors):
-        import torch
-        n = int(tensors[0].shape[0])
-        for t, dt in zip(tensors, (torch.int64, torch.int64, torch.float32)):
-            if t.dtype != dt or tuple(t.shape) != (n,) or t.device != self.params.device or not t.is_contiguous():
-                raise ValueError("dcn: users, items (int64) and labels (fp32) must be contiguous [n] tensors on the parameters' device")
-        self.reserve(n)
-        return n
-
-    def __call__(self, users, items, labels, loss=None, logits=None):
-        import torch
-        if self.grads is None:
-            raise ValueError("dcn: this DcnGrad was made without a gradient buffer")
-        n = self._check((users, items, labels))
-        dev = self.params.device
-        loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
-        logits = torch.empty(n, dtype=torch.float32, device=dev) if logits is None else logits
-        front = (C.byref(self._head), users.data_ptr(), items.data_ptr(), labels.data_ptr(), n, loss.data_ptr(), logits.data_ptr())
-        if self._drop is None:
-            _lib.check(self.lib.pmgt_dcn_train_grad(*front, self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
-        else:
-            _lib.check(self.lib.pmgt_dcn_train_grad_dropout(*front, C.byref(self._drop), self._ws.data_ptr(), self._ws.numel(), _lib.stream()))
-        return loss, logits
+            self._entry, self._extra = lib.pmgt_dcn_train_grad_dropout, (C.byref(self._drop),)
 
     def forward(self, users, items, logits=None):
         import torch
@@ -134,7 +86,7 @@ class DcnGrad:
         return logits
 
 
-class DcnTrainer:
+class DcnTrainer(PairTrainer):
     """AdamW on a dcn.DCN, all on the device.  Every trained parameter -- both embedding tables, the deep net, the cross weights, the
     LayerNorms, the output layer -- moves into ONE flat fp32 buffer (dcn_layout) and the model's nn.Parameters are re-pointed at views of
     it, so model.forward and state_dict see the trained weights with no copy.  `cross_net.layers.c.bias`, which the forward never reads,
@@ -150,128 +102,30 @@ class DcnTrainer:
     {seed, step}, and `step_count` is a view of rng[1:2]: the pmgt_op_adamw call that ends every step advances the mask stream, so eager
     and replayed steps draw fresh masks with no host write.  Still five launches.  Without a seed a model with dropout is refused."""
 
+    who, max_pairs = "dcn", DCN_MAX_PAIRS
+    layouts_differ = "the state was saved for a model of another shape or LayerNorm setting (the layouts differ)"
+
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = None,
                  item_init=None, dropout_seed: int = None):
         import torch
-        import torch.nn as nn
-        if dropout_seed is not None and (isinstance(dropout_seed, bool) or not isinstance(dropout_seed, (int, np.integer))
-                                         or not -2 ** 63 <= dropout_seed < 2 ** 63):
-            raise ValueError(f"dcn: dropout_seed = {dropout_seed!r} must be an integer that fits int64")
+        if dropout_seed is not None:
+            check_seed(dropout_seed, "dcn")
         dims = _model_dims(model, dropout_ok=dropout_seed is not None)
         drop_p = None if dropout_seed is None else model_dropout(model)
         dev = model.user_embeddings.weight.device
         if dev.type != "cuda":
             raise ValueError("dcn: the model must be on a GPU")
-        self.model = model
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
-        self.max_grad_norm = float(max_grad_norm or 0.0)
-        self.layout, self.count = dcn_layout(*dims)
         E = model.factor_num << model.deep_layers
         if item_init is not None and (not isinstance(item_init, torch.Tensor) or item_init.dtype != torch.float32
                                       or tuple(item_init.shape) != (model.item_num, E)):
             raise ValueError(f"dcn: item_init must be an fp32 tensor [{model.item_num}, {E}]")
-        self.params = torch.zeros(self.count, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
-        if self.dropout_seed is None:
-            self.rng, self.step_count = None, torch.zeros(1, dtype=torch.int64, device=dev)
-        else:
-            self.rng = torch.tensor([self.dropout_seed, 0], dtype=torch.int64, device=dev)
-            self.step_count = self.rng[1:2]                  # the optimizer's step counter IS the step of the mask stream
-        self.decay = torch.zeros(self.count, dtype=torch.uint8, device=dev)
-        self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
-        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
+        super().__init__(model, dev, *dcn_layout(*dims), lr, weight_decay, betas, eps, max_grad_norm, dropout_seed)
         named = dict(model.named_parameters())
-        with torch.no_grad():
-            for key, (off, shape) in self.layout.items():
-                view = self.params[off: off + int(np.prod(shape))].view(shape)
-                view.copy_(item_init.detach() if key == ITEM_KEY and item_init is not None else named[key].detach())
-                mod = model.get_submodule(key.rsplit(".", 1)[0])
-                setattr(mod, key.rsplit(".", 1)[1], nn.Parameter(view, requires_grad=True))
-                if decays(key):
-                    self.decay[off: off + int(np.prod(shape))] = 1
+        self._adopt(lambda key: item_init if key == ITEM_KEY and item_init is not None else named[key], lambda key: True, decays)
         self.grad_fn = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, self.params, self.grads,
                                dropout=None if self.rng is None else (self.rng, *drop_p))
         model._dcn_flat = self.params                        # evaluate_ctr reads the trained parameters in place
         model._dcn_dropout_seeded = self.rng is not None     # ... and, of a model trained with its dropout, in eval mode
-        self._graph = self._static = self._logit_buf = None
-
-    def views(self, flat) -> dict:
-        """{state_dict key: view of `flat`} for a buffer of the layout (params, grads, exp_avg, ...)."""
-        return {k: flat[off: off + int(np.prod(shape))].view(shape) for k, (off, shape) in self.layout.items()}
-
-    def step(self, users, items, labels, loss=None):
-        """One optimizer step on the pairs (device tensors: int64 [n], int64 [n], fp32 [n]; ids inside the tables, check_dcn_pairs checks
-        them on the host) -> the loss before the step as a device tensor [1].  Five launches enqueued; no host copy, no synchronisation."""
-        loss, _ = self.grad_fn(users, items, labels, loss=loss, logits=self._logits(int(users.shape[0])))
-        _lib.check(self.grad_fn.lib.pmgt_op_adamw(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-                                                  self.exp_avg_sq.data_ptr(), self.decay.data_ptr(), self.count, self.lr, self.weight_decay,
-                                                  self.betas[0], self.betas[1], self.eps, self.max_grad_norm, self.step_count.data_ptr(),
-                                                  self._scal.data_ptr(), self._part.data_ptr(), _lib.stream()))
-        return loss
-
-    def _logits(self, n: int):
-        import torch
-        if self._logit_buf is None or self._logit_buf.numel() < n:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("dcn: buffers cannot grow inside a capture")
-            self._logit_buf = torch.empty(n, dtype=torch.float32, device=self.params.device)
-        return self._logit_buf[:n]
-
-    def capture(self, n: int):
-        """Captures step() on `n` pairs into a graph over static input buffers -> (users, items, labels, loss): write a batch into the first
-        three, replay(), read the last.  One stream.  Every buffer is created before the capture, and one warm-up step runs eagerly on the
-        zeroed static batch with the parameters, the moments and the step counter put back afterwards: capturing leaves the state as it was."""
-        import torch
-        if not 1 <= int(n) <= DCN_MAX_PAIRS:
-            raise ValueError(f"dcn: n = {n} pairs outside [1, {DCN_MAX_PAIRS}]")
-        dev = self.params.device
-        self._static = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
-                        torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
-        self.grad_fn.reserve(n)
-        self._logits(n)
-        saved = self.state_dict()
-        self.step(*self._static[:3], loss=self._static[3])
-        self.load_state_dict(saved)
-        torch.cuda.synchronize(dev)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.step(*self._static[:3], loss=self._static[3])
-        return self._static
-
-    def replay(self):
-        if self._graph is None:
-            raise RuntimeError("dcn: capture(n) comes before replay()")
-        self._graph.replay()
-        return self._static[3]
-
-    def state_dict(self) -> dict:
-        """The flat parameters, both moments, the step counter and the layout (which names the shape and the LayerNorm setting); with
-        dropout, the seed (with "step", the whole state of the mask stream)."""
-        sd = {"params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
-              "step": self.step_count.clone(), "layout": {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()}}
-        if self.dropout_seed is not None:
-            sd["dropout_seed"] = self.dropout_seed
-        return sd
-
-    def load_state_dict(self, sd: dict) -> None:
-        import torch
-        if {k: (off, tuple(shape)) for k, (off, shape) in self.layout.items()} != dict(sd["layout"]):
-            raise ValueError("dcn: the state was saved for a model of another shape or LayerNorm setting (the layouts differ)")
-        if sd.get("dropout_seed") != self.dropout_seed:
-            raise ValueError(f"dcn: the state was saved with dropout_seed = {sd.get('dropout_seed')!r}, this trainer has {self.dropout_seed!r}")
-        with torch.no_grad():
-            self.params.copy_(sd["params"])
-            self.exp_avg.copy_(sd["exp_avg"])
-            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-            self.step_count.copy_(sd["step"])
-
-
-def bce_with_logits_host(logits: np.ndarray, labels: np.ndarray) -> float:
-    """The mean of max(z, 0) - z y + log1p(exp(-|z|)) in float64."""
-    z, y = np.asarray(logits, dtype=np.float64), np.asarray(labels, dtype=np.float64)
-    return float((np.maximum(z, 0) - z * y + np.log1p(np.exp(-np.abs(z)))).mean())
 
 
 def _flat_of(model):
@@ -360,8 +214,6 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     masks a pure function of the seed and the count of steps taken; validation stays in eval mode and never drops.  Without it such a
     model is refused.
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), auc, loss, best (whether it improved)."""
-    import torch
-    from .fit_loop import BestCheckpoint, EarlyStopping, epoch_order, monitor_of
     if early_criterion not in ("auc", "loss"):
         raise ValueError(f"early_criterion={early_criterion!r}: expected 'auc' or 'loss'")
     if not 1 <= int(batch_size) <= DCN_MAX_PAIRS or max_epochs < 1:
@@ -376,47 +228,15 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     check_ids("items", pairs[:, 1], model.item_num, "fit_dcn")
     trainer = DcnTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm, item_init=item_init,
                          dropout_seed=dropout_seed)
-    dev = trainer.params.device
-    monitor, mode = monitor_of(early_criterion)
-    stopper = EarlyStopping(monitor, patience, mode)
-    keeper = BestCheckpoint(ckpt_dir or "", monitor, mode)
-    if ckpt_dir:
-        os.makedirs(ckpt_dir, exist_ok=True)
-    best_params, history = None, []
-    was_training = model.training
-    model.eval()
-    try:
-        for epoch in range(int(max_epochs)):
-            users, items, labels = ng_sample(pairs, model.user_num, model.item_num, num_ng, seed + epoch)
-            order = epoch_order(len(users), seed, epoch)
-            users_d, items_d, labels_d = (torch.from_numpy(np.ascontiguousarray(a[order])).to(dev) for a in (users, items, labels))
-            n_steps = (len(order) + batch_size - 1) // batch_size
-            losses = torch.empty(n_steps, 1, dtype=torch.float32, device=dev)
-            for s in range(n_steps):
-                lo, hi = s * batch_size, min((s + 1) * batch_size, len(order))
-                trainer.step(users_d[lo:hi], items_d[lo:hi], labels_d[lo:hi], loss=losses[s])
-            try:
-                ev = evaluate_ctr(model, *valid, batch_size=eval_batch_size, metrics="device")
-            except ValueError as e:
-                raise ValueError(f"fit_dcn: epoch {epoch}: validation: {e}") from e
-            row = {"epoch": epoch, "train_loss": float(losses.double().mean().item()), "auc": ev["auc"], "loss": ev["loss"]}
-            write, remove = keeper.update(epoch, row[early_criterion])
-            row["best"] = write is not None
-            if write is not None:
-                best_params = trainer.params.detach().clone()
-                if ckpt_dir:
-                    torch.save({"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
-                                "metrics": dict(row)}, write)
-                    if remove and os.path.exists(remove):
-                        os.remove(remove)
-            history.append(row)
-            if log is not None:
-                log(row)
-            if stopper.update(row[early_criterion], epoch):
-                break
-        if best_params is not None:
-            with torch.no_grad():
-                trainer.params.copy_(best_params)
-    finally:
-        model.train(was_training)
-    return history
+
+    def validate(epoch: int) -> dict:
+        try:
+            ev = evaluate_ctr(model, *valid, batch_size=eval_batch_size, metrics="device")
+        except ValueError as e:
+            raise ValueError(f"fit_dcn: epoch {epoch}: validation: {e}") from e
+        return {"auc": ev["auc"], "loss": ev["loss"]}
+
+    def checkpoint(epoch: int, row: dict) -> dict:
+        return {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "metrics": dict(row)}
+
+    return fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log)

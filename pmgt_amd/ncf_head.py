@@ -2,13 +2,17 @@
 the ranking evaluation (evaluation.py): which heads the kernels cover, the flat parameter layout, the refusals of the ids and tables that the
 kernels read unchecked, and the two numpy references that every NCF kernel is judged against (ncf_head_host: users x catalogue;
 ncf_head_grad_host: loss, logits and every gradient of a list of pairs, under the masks of ncf_dropout_masks when the head is trained with
-dropout).  Pure numpy and the bindings module: importing this loads no GPU library."""
+dropout).  What the head shares with the other pair head, the DCN -- check_ids, check_pairs, head_weights, the dropout RNG (ncf_dropout_keep is
+pair_train.dropout_keep) -- lives in pair_train.py and is re-exported here.  Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
-from ._lib import NCF_FACTORS, NCF_KINDS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER, NCF_TRAIN_MAX_PAIRS
+from ._lib import NCF_FACTORS, NCF_KINDS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER
+from .pair_train import _fmix32, check_dropout_p, check_ids, check_pairs, dropout_keep as ncf_dropout_keep  # noqa: F401
+from .pair_train import dropout_scale as ncf_dropout_scale, head_weights, per_layer
 
 HEAD_PREFIXES = ("mlp_user_embeddings.", "mlp_layers.", "predict_layer.", "gmf_user_embeddings.", "gmf_item_embeddings.")
 TABLE_KEY = "item_table"                         # the trained table's name in the layouts, the gradients and the checkpoints
+LAYER_DROPOUTS = "{} layer dropouts for {} layers"       # per_layer's refusal of a list of another length
 
 
 def head_shape(weights: dict):
@@ -81,12 +85,6 @@ def layout_slots(layout: dict):
     return [layout[k][0] if k in layout else -1 for k in slots]
 
 
-def check_ids(what: str, ids: np.ndarray, limit: int, who: str) -> None:
-    """ValueError in the name of `who` when an id of `ids` (`what`: "users", ...) lies outside [0, limit): the kernels read by them unchecked."""
-    if ids.size and (ids.min() < 0 or ids.max() >= limit):
-        raise ValueError(f"{who}: {what} in [{int(ids.min())}, {int(ids.max())}] outside [0, {limit})")
-
-
 def check_item_table(table, item_num, d: int, device, who: str) -> None:
     """ValueError in the name of `who` unless `table` is an fp32 torch tensor [item_num, d] on `device` (None: any row count from 1 / any GPU)."""
     import torch
@@ -94,26 +92,6 @@ def check_item_table(table, item_num, d: int, device, who: str) -> None:
     ok = ok and (table.shape[0] >= 1 if item_num is None else table.shape[0] == item_num)
     if not (ok and (table.is_cuda if device is None else table.device == device)):
         raise ValueError(f"{who}: the item table must be an fp32 tensor [{item_num or 'I >= 1'}, {d}] on {device or 'a GPU'}")
-
-
-def check_pairs(users, items, labels, user_num: int, item_num: int, max_pairs: int = NCF_TRAIN_MAX_PAIRS):
-    """(users int64 [n], items int64 [n], labels fp32 [n]) as the kernels read them; ValueError for shapes that differ, n outside
-    [1, max_pairs] and ids outside the tables."""
-    users, items = np.ascontiguousarray(users, dtype=np.int64), np.ascontiguousarray(items, dtype=np.int64)
-    labels = np.ascontiguousarray(labels, dtype=np.float32)
-    n = len(users)
-    if users.ndim != 1 or items.shape != (n,) or labels.shape != (n,):
-        raise ValueError(f"ncf_train: users {users.shape}, items {items.shape} and labels {labels.shape} must be one [n]")
-    if not 1 <= n <= max_pairs:
-        raise ValueError(f"ncf_train: n = {n} pairs outside [1, {max_pairs}]")
-    check_ids("users", users, user_num, "ncf_train")
-    check_ids("items", items, item_num, "ncf_train")
-    return users, items, labels
-
-
-def head_weights(weights: dict, dtype) -> dict:
-    """`weights` (arrays or CPU tensors keyed like the model's state_dict; None entries dropped) as numpy arrays of `dtype`."""
-    return {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(dtype) for k, v in weights.items() if v is not None}
 
 
 def mlp_stack(w: dict, x: np.ndarray, num_layers: int) -> list:
@@ -124,63 +102,12 @@ def mlp_stack(w: dict, x: np.ndarray, num_layers: int) -> list:
     return hs
 
 
-def _fmix32(h: int) -> int:
-    """The murmur3 finaliser (fmix32 of csrc/common.h) on a Python int."""
-    h &= 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    return h ^ (h >> 16)
-
-
-def check_dropout_p(p, what: str) -> float:
-    """`p` as the fp32 value the kernels take; ValueError unless it lies in [0, 1) (a NaN does not)."""
-    q = float(np.float32(p))
-    if not 0.0 <= q < 1.0:
-        raise ValueError(f"ncf_train: {what} = {p!r} outside [0, 1)")
-    return q
-
-
-def ncf_dropout_keep(seed: int, step: int, site: int, rows: int, cols: int, p: float) -> np.ndarray:
-    """bool [rows, cols]: True where the kernels keep element (row, col) of dropout site `site` (make_drop_key and drop_keep4 of
-    csrc/common.h restated in uint32 arithmetic, bit for bit; what pmgt_op_dropout_keep writes).  seed / step: the int64 values of the
-    device {seed, step} pair.  One hash pair (x, y) decides the 4 columns of group col >> 2 with 16 bits each; an element is kept when its
-    16 bits are >= thr >> 16, thr = (uint32)(double(float32 p) 2^32) saturated.  p = 0 keeps everything."""
-    p = check_dropout_p(p, "p")
-    if not p > 0.0:
-        return np.ones((rows, cols), dtype=bool)
-    seed, step, site = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF
-    k0 = _fmix32((seed & 0xFFFFFFFF) ^ ((site * 0x9E3779B1) & 0xFFFFFFFF))
-    k1 = _fmix32((seed >> 32) + (step & 0xFFFFFFFF) * 0x7FEB352D + (step >> 32) + site)
-    t = p * 4294967296.0
-    thr = 0xFFFFFFFF if t >= 4294967295.0 else int(t)
-    u32 = np.uint32
-    r, cg = np.arange(rows, dtype=u32)[:, None], np.arange((cols + 3) // 4, dtype=u32)[None, :]
-    with np.errstate(over="ignore"):
-        x = r * u32(0x9E3779B1) + cg * u32(0x85EBCA77) + u32(k0)
-        x ^= x >> u32(15)
-        x *= u32(0x2C1B3C6D)
-        x ^= x >> u32(12)
-        y = x * u32(0x297A2D39) + u32(k1)
-        y ^= y >> u32(15)
-    lanes = np.stack([x & u32(0xFFFF), x >> u32(16), y & u32(0xFFFF), y >> u32(16)], axis=2)
-    return (lanes >= u32(thr >> 16)).reshape(rows, -1)[:, :cols]
-
-
-def ncf_dropout_scale(p: float) -> np.float32:
-    """What a kept element is multiplied by: the fp32 value 1 / (1 - p)."""
-    return np.float32(1.0) / (np.float32(1.0) - np.float32(p))
-
-
 def ncf_dropout_masks(seed: int, step: int, n: int, factor_num: int, num_layers: int, kind: str, p_emb: float, p_layer) -> dict:
     """The masks pmgt_ncf_train_grad_dropout draws for a call on `n` pairs -> {site name: (bool keep [n, cols], fp32 scale)}:
     "emb" [n, 2 d] (the user half first), "layer<l>" [n, d >> l] for every layer and, NeuMF-end, "gmf" [n, factor_num] at p_emb with a
     mask of its own.  p_layer: one p for every layer or a sequence of num_layers.  What ncf_head_grad_host(masks=...) applies."""
     check_head_covered(factor_num, num_layers, kind)
-    p_layer = [p_layer] * num_layers if np.isscalar(p_layer) else list(p_layer)
-    if len(p_layer) != num_layers:
-        raise ValueError(f"ncf_train: {len(p_layer)} layer dropouts for {num_layers} layers")
+    p_layer = per_layer(p_layer, num_layers, LAYER_DROPOUTS, "ncf_train")
     d = factor_num << (num_layers - 1)
     masks = {"emb": (ncf_dropout_keep(seed, step, NCF_SITE_EMB, n, 2 * d, p_emb), ncf_dropout_scale(p_emb))}
     if kind == "NeuMF-end":
