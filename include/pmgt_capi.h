@@ -440,6 +440,23 @@ typedef struct pmgt_ncf_dropout {
 int pmgt_ncf_train_grad_dropout(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
                                 float* loss, float* logits, float* table_grad /* NULL: frozen table */, const pmgt_ncf_dropout* drop,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+/* THE HEAD ON PER-PAIR ITEM ROWS (fine-tuning the encoder through the head, pmgt/pmgt_ncf/models.py:77-105: every pair has a sampled context
+ * of its own, so its item embedding is the CLS state of THAT context and no row of a table).  The function is the dropout entry's above
+ * (drop NULL: no dropout) with one difference: the item half of layer 0's input of pair p is row p of x_item, fp32 [n][d], contiguous, 16-byte
+ * aligned, where the other entries read table[items[p]].  `items` still addresses gmf_item_embeddings (NeuMF-end); head->table is NOT READ
+ * (it may be NULL) and head->item_num is the row count of gmf_item.  Written: everything the table entry writes but the table's gradient
+ * (loss, logits, the head's gradient buffer whole, with the same bits as that entry's when x_item[p] = table[items[p]]) and d_item fp32
+ * [n][d], 16-byte aligned, whole: row p = d loss / d x_item[p], with dropout under the emb mask exactly as table_grad is.  NOTHING IS SUMMED
+ * ACROSS PAIRS: two pairs on one item keep separate rows.  Sites, rows and columns of the masks are unchanged (row = the pair's index).
+ * LAUNCHES: TWO, the kernels of the table entry (the second gains one role that copies the item half of the per-pair data gradient out of
+ * the workspace); no atomic, no sync, no allocation, capturable, the same bits for the same inputs.  Workspace:
+ * pmgt_ncf_train_rows_workspace_bytes (the table entry's size).  Refused (-2) before anything is launched: what the entries above refuse
+ * (but the table), a NULL or misaligned x_item or d_item.
+ * Added without a bump of the ABI version: two entries, nothing existing moved. */
+int64_t pmgt_ncf_train_rows_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n);
+int pmgt_ncf_train_grad_rows(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                             float* logits, const float* x_item, float* d_item, const pmgt_ncf_dropout* drop /* NULL: none */,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The DEEP & CROSS NETWORK of the reference's click-through experiment ON THE DEVICE (pmgt/dcn/models.py, scripts/run_dcn.sh): for n
  * (user, item, label) pairs the logits (pmgt_dcn_forward) or the mean loss, the logits and the gradient of that loss with respect to

@@ -242,6 +242,33 @@ int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const 
 int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                           float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                           const pmgt_step_guard* guard, void* stream);
+/* Global-norm clip + AdamW over up to PMGT_ADAM_MAX_SEGMENTS disjoint flat fp32 buffers AS ONE OPTIMIZER: the norm is taken over all
+ * segments (the partials of the plain step's own norm kernel per segment, summed in fp64 by the prepare lane), there is one clip
+ * coefficient, one increment of *step and one pair of bias corrections.  Per segment both the step size and the decay rate are multiplied
+ * by lr_scale (an encoder fine-tuned through a head at a learning rate of its own); lr_scale = 0 leaves that segment's p untouched bit
+ * for bit while its m and v move.  With ONE segment and lr_scale == 1 the call gives the plain entry's bits (p, m, v, step, scal[0..3]).
+ * scal [8]: [0..3] as the plain entry, [4] = lr; part [count * 1024] floats of scratch.  An empty segment (n = 0) is skipped.  Launches:
+ * one norm launch and one update launch per non-empty segment, one prepare launch; no sync, no allocation, capturable.
+ * Refused (-2) before any launch: count outside [1, PMGT_ADAM_MAX_SEGMENTS], a NULL pointer, n < 0, lr_scale not finite or negative. */
+#define PMGT_ADAM_MAX_SEGMENTS 8
+typedef struct pmgt_adam_segment {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    const uint8_t* decay;
+    int64_t n;
+    float lr_scale;
+} pmgt_adam_segment;
+int pmgt_op_adamw_segments(const pmgt_adam_segment* segments, int count, float lr, float wd, float b1, float b2, float eps, float max_norm,
+                           int64_t* step, float* scal, float* part, void* stream);
+/* The two-way glue between an encoder output [n][S][d] in the engine dtype (PMGT_DTYPE_F32 or PMGT_DTYPE_BF16) and the fp32 rows [n][d] a head
+ * reads and differentiates.  Gather: x[p][:] = (float) last_hidden[p][0][:], the CLS state of sequence p.  Scatter: d_last [n][S][d] is
+ * written WHOLE -- token 0 of sequence p gets d_item[p] (fp32 -> bf16 round-to-nearest-even), every other element +0.0.  16-byte accesses
+ * where d is a multiple of 8, element by element otherwise.  One launch each.  Refused (-2): a NULL pointer, n, S or d below 1, a dtype
+ * that is neither, n S d beyond 2^40. */
+int pmgt_op_cls_gather(int dtype, const void* last_hidden, int64_t n, int S, int d, float* x, void* stream);
+int pmgt_op_cls_scatter(int dtype, const float* d_item, int64_t n, int S, int d, void* d_last, void* stream);
 /* The append entry of the validation metrics in pmgt_capi.h, on ready scores: no sigmoid, everything else the same (negative, subnormal, infinite and NaN scores reach
  * the key function as they are) */
 int pmgt_op_eval_append_scores(void* workspace, int64_t capacity, const float* scores, const float* labels, const float* loss, int64_t offset,

@@ -96,6 +96,15 @@ class NcfDropoutC(C.Structure):
     _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_layer", C.c_float * 4)]
 
 
+class AdamSegmentC(C.Structure):
+    """pmgt_adam_segment (include/pmgt_ops.h): one flat buffer of pmgt_op_adamw_segments."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("decay", C.c_void_p), ("n", C.c_int64),
+                ("lr_scale", C.c_float)]
+
+
+ADAM_MAX_SEGMENTS = 8      # PMGT_ADAM_MAX_SEGMENTS
+
+
 class DcnHeadC(C.Structure):
     """pmgt_dcn_head (include/pmgt_capi.h)."""
     _fields_ = [("factor_num", C.c_int), ("deep_layers", C.c_int), ("cross_layers", C.c_int), ("use_layer_norm", C.c_int),
@@ -146,6 +155,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
+    "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
     "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
     "pmgt_dcn_train_grad_dropout",
 ]
@@ -161,6 +171,7 @@ OPS_SYMBOLS = [
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
     "pmgt_op_adamw_guarded", "pmgt_op_eval_append_scores", "pmgt_op_eval_small_max",
     "pmgt_op_linear_rows", "pmgt_op_layernorm_bwd_rows", "pmgt_op_gemm_tn_bias_rows",
+    "pmgt_op_adamw_segments", "pmgt_op_cls_gather", "pmgt_op_cls_scatter",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -312,6 +323,12 @@ def hip():
     L.pmgt_ncf_train_table_workspace_bytes.argtypes = [i, i, i, i64]
     L.pmgt_ncf_train_grad_table.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]      # (... logits, table_grad, workspace ...)
     L.pmgt_ncf_train_grad_dropout.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... table_grad or NULL, drop ...)
+    L.pmgt_ncf_train_rows_workspace_bytes.restype = i64
+    L.pmgt_ncf_train_rows_workspace_bytes.argtypes = [i, i, i, i64]
+    L.pmgt_ncf_train_grad_rows.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... logits, x_item, d_item, drop or NULL, workspace ...)
+    L.pmgt_op_adamw_segments.argtypes = [C.POINTER(AdamSegmentC), i, f, f, f, f, f, f, vp, vp, vp, vp]
+    L.pmgt_op_cls_gather.argtypes = [i, vp, i64, i, i, vp, vp]
+    L.pmgt_op_cls_scatter.argtypes = [i, vp, i64, i, i, vp, vp]
     L.pmgt_dcn_layout.restype = i64
     L.pmgt_dcn_layout.argtypes = [i, i, i, i, i64, i64, vp]
     L.pmgt_dcn_workspace_bytes.restype = i64

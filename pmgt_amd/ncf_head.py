@@ -1,8 +1,8 @@
 """What the head of a PMGT_NCF is (pmgt/pmgt_ncf/models.py:91-105), stated once for the scoring (recommend.py), the training (ncf_train.py) and
 the ranking evaluation (evaluation.py): which heads the kernels cover, the flat parameter layout, the refusals of the ids and tables that the
-kernels read unchecked, and the two numpy references that every NCF kernel is judged against (ncf_head_host: users x catalogue;
+kernels read unchecked, and the numpy references that every NCF kernel is judged against (ncf_head_host: users x catalogue;
 ncf_head_grad_host: loss, logits and every gradient of a list of pairs, under the masks of ncf_dropout_masks when the head is trained with
-dropout).  What the head shares with the other pair head, the DCN -- check_ids, check_pairs, head_weights, the dropout RNG (ncf_dropout_keep is
+dropout; ncf_head_rows_grad_host: the same on an item row per pair, with the gradient of those rows).  What the head shares with the other pair head, the DCN -- check_ids, check_pairs, head_weights, the dropout RNG (ncf_dropout_keep is
 pair_train.dropout_keep) -- lives in pair_train.py and is re-exported here.  Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
@@ -141,25 +141,15 @@ def ncf_head_host(weights: dict, users, table, dtype=np.float64) -> np.ndarray:
     return out
 
 
-def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False, masks: dict = None):
-    """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
-    `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
-    model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
-    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order.
-    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule.
-    masks: None, or {site: (bool keep [n, cols], scale)} as ncf_dropout_masks names them -- the head in TRAINING mode under these masks,
-    m = keep * scale in `dtype`: x0 = m_emb [user ; item], h_(l+1) = relu(m_l (W_l h_l + b_l)), gmf = m_gmf (gmf_u gmf_i), and the
-    gradients of that function (d x0 carries m_emb to the embedding rows and the table).  A site that is missing is not dropped."""
-    w = head_weights(weights, dtype)
+def _head_grad(w: dict, x_item: np.ndarray, users, items, y, dtype, m: dict):
+    """The one statement of the trained head's mathematics, shared by ncf_head_grad_host (x_item = table[items]) and
+    ncf_head_rows_grad_host (x_item given per pair): `w` in `dtype`, x_item [n, d] the item half of layer 0's input, m = {site: mask in
+    `dtype`} -> (loss, logits, the head's gradients, d loss / d x0 [n, 2 d] per pair, under the emb mask)."""
     factor, num_layers, kind, d = head_shape(w)
-    table = np.asarray(table).astype(dtype)
-    users, items, y = check_pairs(users, items, labels, len(w["mlp_user_embeddings.weight"]), len(table), max_pairs=1 << 40)
-    y = y.astype(dtype)
     n = len(users)
     one = dtype(1)
-    m = {} if masks is None else {k: np.asarray(keep, dtype=bool).astype(dtype) * dtype(scale) for k, (keep, scale) in masks.items()}
-    x0 = np.concatenate([w["mlp_user_embeddings.weight"][users], table[items]], axis=1)
-    if masks is None:
+    x0 = np.concatenate([w["mlp_user_embeddings.weight"][users], x_item], axis=1)
+    if not m:
         hs = mlp_stack(w, x0, num_layers)
     else:
         hs = [x0 * m["emb"] if "emb" in m else x0]
@@ -196,8 +186,47 @@ def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.floa
         dh = dh * m["emb"]
     grads["mlp_user_embeddings.weight"] = np.zeros_like(w["mlp_user_embeddings.weight"])
     np.add.at(grads["mlp_user_embeddings.weight"], users, dh[:, :d])
+    assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype and dh.dtype == dtype
+    return dtype(loss), z, grads, dh
+
+
+def _masks_as(masks, dtype) -> dict:
+    return {} if masks is None else {k: np.asarray(keep, dtype=bool).astype(dtype) * dtype(scale) for k, (keep, scale) in masks.items()}
+
+
+def ncf_head_grad_host(weights: dict, table, users, items, labels, dtype=np.float64, table_grad: bool = False, masks: dict = None):
+    """PMGT_NCF.head with dropout 0 on the pairs (users[p], items[p]) over the frozen `table` [I, d], the mean BCE-with-logits loss against
+    `labels` and its gradient, every operation in `dtype` -> (loss, logits [n], {state_dict key: gradient}).  `weights` is keyed like the
+    model's state_dict (see ncf_head_host).  The loss is max(z, 0) - z y + log1p(exp(-|z|)), dlogit = (sigmoid(z) - y) / n with the sigmoid
+    in its overflow-free form, the ReLU passes where h > 0, and rows of the embedding tables hit by several pairs are summed in pair order.
+    table_grad=True: the gradients also hold TABLE_KEY ("item_table"), d loss / d table [I, d], by the same rule.
+    masks: None, or {site: (bool keep [n, cols], scale)} as ncf_dropout_masks names them -- the head in TRAINING mode under these masks,
+    m = keep * scale in `dtype`: x0 = m_emb [user ; item], h_(l+1) = relu(m_l (W_l h_l + b_l)), gmf = m_gmf (gmf_u gmf_i), and the
+    gradients of that function (d x0 carries m_emb to the embedding rows and the table).  A site that is missing is not dropped."""
+    w = head_weights(weights, dtype)
+    d = head_shape(w)[3]
+    table = np.asarray(table).astype(dtype)
+    users, items, y = check_pairs(users, items, labels, len(w["mlp_user_embeddings.weight"]), len(table), max_pairs=1 << 40)
+    loss, z, grads, dh = _head_grad(w, table[items], users, items, y.astype(dtype), dtype, _masks_as(masks, dtype))
     if table_grad:
         grads[TABLE_KEY] = np.zeros_like(table)
         np.add.at(grads[TABLE_KEY], items, dh[:, d:])
-    assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype
-    return dtype(loss), z, grads
+        assert grads[TABLE_KEY].dtype == dtype
+    return loss, z, grads
+
+
+def ncf_head_rows_grad_host(weights: dict, x_item, users, items, labels, dtype=np.float64, masks: dict = None):
+    """ncf_head_grad_host for a head whose item input is A ROW PER PAIR (pmgt_ncf_train_grad_rows: the CLS state of the pair's own context):
+    layer 0 reads x_item[p] [n, d] where that function reads table[items[p]], the GMF branch (NeuMF-end) still reads
+    gmf_item_embeddings[items[p]] -> (loss, logits [n], {state_dict key: gradient}, d_item [n, d]).  Row p of d_item is d loss / d x_item[p],
+    under the emb mask when `masks` holds one; nothing is summed across pairs.  The same rules and the same code as ncf_head_grad_host: with
+    x_item = table[items] the first three results are that function's, and d_item summed per item is its "item_table" gradient."""
+    w = head_weights(weights, dtype)
+    _, _, kind, d = head_shape(w)
+    x_item = np.asarray(x_item).astype(dtype)
+    item_num = len(w["gmf_item_embeddings.weight"]) if kind == "NeuMF-end" else 1 << 62      # (an MLP head reads no row by item id)
+    users, items, y = check_pairs(users, items, labels, len(w["mlp_user_embeddings.weight"]), item_num, max_pairs=1 << 40)
+    if x_item.shape != (len(users), d):
+        raise ValueError(f"ncf_train: x_item {x_item.shape} must be [n, d] = [{len(users)}, {d}]")
+    loss, z, grads, dh = _head_grad(w, x_item, users, items, y.astype(dtype), dtype, _masks_as(masks, dtype))
+    return loss, z, grads, np.ascontiguousarray(dh[:, d:])

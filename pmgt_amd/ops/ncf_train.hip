@@ -43,6 +43,15 @@
 //            the passed gradient by 1 / (1 - p_l) and draws no layer mask again
 //   gmf      gprod = m_g (gmf_u gmf_i), a mask of its own at emb_dropout's p: stored dropped, drawn again for the per-pair GMF gradients
 // A site whose p is 0 draws nothing and multiplies by nothing.
+//
+// PER-PAIR ITEM ROWS (pmgt_ncf_train_grad_rows: the head on top of an encoder that is trained with it, every pair with a context and so an
+// item embedding of its own), still TWO launches: the TABLE instantiations with two run-time differences.  Launch 1 reads the item half of
+// layer 0's input from row `pair` of x_item [n][d] instead of table[items[pair]], and the weight task of layer 0 reads the same rows (NtSrc
+// by the pair index).  Launch 2 sums no table rows; its extra role
+//   item   copies the item half of dx [n][2 d] into the caller's d_item [n][d], 16 bytes a thread: one row per pair, nothing summed
+// so two pairs on one item keep their own gradient rows.  The other entries launch no block of this role and keep their bits.
+#include <climits>
+
 #include "ncf_head.h"
 
 namespace pmgt {
@@ -61,6 +70,7 @@ struct NtLayer {
 struct NtPairsArgs {
     NtLayer layer[NT_MAX_LAYERS];
     const float *u_mlp, *table, *gu, *gi, *wp, *bp;
+    const float* x_item;                     // rows entry: layer 0's item half of pair p is row p of this [n][d]; else NULL (table[items[p]])
     const int64_t *users, *items;
     const float* labels;
     float *dx, *gprod, *ggu, *ggi, *pz;      // workspace: [n][d] (trained table: [n][2 d]), [n][F] x 3, [n][2] = (dlogit, loss of the pair)
@@ -99,7 +109,9 @@ struct NtGradsArgs {
     const int *order_u, *order_i;
     const float *dx, *ggu, *ggi;
     float *g_u_mlp, *g_gu, *g_gi, *g_table, *loss;                   // g_table: the trained table's gradient, else NULL
+    float* d_item;                                                   // rows entry: [n][d], the item half of dx per pair; else NULL
     int n, d, factor, neumf, ntasks, weight_blocks, row_blocks;      // row_blocks per kind (user, item)
+    int item_first, item_blocks;                                     // rows entry: the first block and the count of the `item` role; else (INT_MAX, 0)
 };
 
 __device__ __forceinline__ float4 ld4(const float* p, bool ok) {
@@ -261,7 +273,7 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     const bool valid = pair < n;
     const int64_t uid = valid ? a.users[pair] : 0, iid = valid ? a.items[pair] : 0;
     const float* urow = a.u_mlp + uid * d;
-    const float* irow = a.table + iid * d;
+    const float* irow = a.x_item ? a.x_item + (int64_t)pair * d : a.table + iid * d;
     DropKey kemb = drop_off(), kgmf = drop_off(), klay = drop_off();
     if constexpr (DROP) {
         kemb = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB});
@@ -371,6 +383,16 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
     __shared__ float s_acc[NT_WAVES][16][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
     int bid = blockIdx.x;
+    if (bid >= a.item_first) {                               // ---- item (rows entry): d_item [n][d] = the item half of dx [n][2 d], 16 bytes a thread
+        const int q = a.d >> 2;                              // (d is a multiple of 8)
+        const float4* src = reinterpret_cast<const float4*>(a.dx);
+        float4* dst = reinterpret_cast<float4*>(a.d_item);
+        for (int64_t i = (int64_t)(bid - a.item_first) * NT_THREADS + tid; i < (int64_t)n * q; i += (int64_t)a.item_blocks * NT_THREADS) {
+            const int64_t pr = i / q;
+            dst[i] = src[pr * 2 * q + q + (i - pr * q)];
+        }
+        return;
+    }
     if (bid >= a.weight_blocks) {                            // ---- rows: segment sums of the per-pair embedding gradients in pair order
         bid -= a.weight_blocks;
         const int kind = bid / a.row_blocks;
@@ -383,7 +405,7 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
         const int d = a.d, F = a.factor;
         const int Fg = a.neumf ? F : 0;                      // the GMF rows of this kind
         const int dxw = TABLE ? 2 * d : d;
-        const int width = kind ? Fg + (TABLE ? d : 0) : d + Fg;
+        const int width = kind ? Fg + (TABLE && a.g_table ? d : 0) : d + Fg;      // (the rows entry has dx [n][2 d] and no table to sum into)
         for (int c = lane; c < width; c += 64) {
             const float* src;                                // the per-pair rows, `sw` floats apart
             float* dst;                                      // the table's rows, `w` floats wide
@@ -529,21 +551,26 @@ static int64_t nt_workspace_bytes(int factor_num, int num_layers, int kind, int6
     return nt_workspace_floats(s, n, table) * (int64_t)sizeof(float);
 }
 
-// every gradient entry; want_table: the table is trained and table_grad [item_num][d] is written whole; drop: NULL or the dropout of the call
+// every gradient entry; want_table: the table is trained and table_grad [item_num][d] is written whole; drop: NULL or the dropout of the call;
+// rows: the rows entry -- layer 0's item half is x_item [n][d] by the pair index, head->table is not read, d_item [n][d] is written whole
 static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
                    float* loss, float* logits, bool want_table, float* table_grad, const pmgt_ncf_dropout* drop, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
+                   int64_t workspace_bytes, void* stream, bool rows = false, const float* x_item = nullptr, float* d_item = nullptr) {
     PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
     NtShape s;
     if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, who, &s)) return rc;
     PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_NCF_TRAIN_MAX_PAIRS);
-    PMGT_CHECK(head->table && head->params && head->grads && users && items && labels && loss && workspace, -2, "%s: NULL buffer", who);
+    PMGT_CHECK((rows || head->table) && head->params && head->grads && users && items && labels && loss && workspace, -2, "%s: NULL buffer", who);
     PMGT_CHECK(!want_table || table_grad, -2, "%s: NULL table_grad", who);
-    PMGT_CHECK((((uintptr_t)head->table | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace | (uintptr_t)table_grad) & 15) == 0,
-               -2, "%s: the table, the parameters, the gradients (the table's included) and the workspace must be 16-byte aligned", who);
+    PMGT_CHECK(!rows || (x_item && d_item), -2, "%s: NULL x_item or d_item", who);
+    const uintptr_t table_bits = rows ? ((uintptr_t)x_item | (uintptr_t)d_item) : (uintptr_t)head->table;
+    PMGT_CHECK(((table_bits | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace | (uintptr_t)table_grad) & 15) == 0, -2,
+               "%s: the table (the rows entry: x_item and d_item), the parameters, the gradients (the table's included) and the workspace must be "
+               "16-byte aligned", who);
     PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
                "%s: misaligned buffer", who);
-    const int64_t need = nt_workspace_floats(s, n, want_table) * (int64_t)sizeof(float);
+    const bool wide = want_table || rows;                    // dx covers all 2 d columns of layer 0's input
+    const int64_t need = nt_workspace_floats(s, n, wide) * (int64_t)sizeof(float);
     PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
     NtDrop dr = {};
     bool drop_on = false;                                    // every p 0: the instantiations without dropout
@@ -576,7 +603,7 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
         pa.layer[l].act = ws, ws += n * out;
         pa.layer[l].dz = ws, ws += n * out;
     }
-    const int dxw = want_table ? 2 * d : d;
+    const int dxw = wide ? 2 * d : d;
     pa.dx = ws, ws += n * dxw;
     pa.gprod = ws, ws += n * F;
     pa.ggu = ws, ws += n * F;
@@ -585,7 +612,8 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     pa.order_u = (int*)ws, ws += (n + 3) / 4 * 4;
     pa.order_i = (int*)ws;
     pa.u_mlp = P + off[0];
-    pa.table = head->table;
+    pa.table = rows ? nullptr : head->table;
+    pa.x_item = x_item;
     pa.gu = s.neumf ? P + off[1] : nullptr;
     pa.gi = s.neumf ? P + off[2] : nullptr;
     pa.wp = P + off[OFF_WP];
@@ -609,7 +637,7 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
         NtTask& t = ga.task[l];
         t.a = pa.layer[l].dz;
         t.m = out;
-        if (l == 0) t.b = NtSrc{pa.u_mlp, users, d, pa.table, items, d};
+        if (l == 0) t.b = rows ? NtSrc{pa.u_mlp, users, d, x_item, nullptr, d} : NtSrc{pa.u_mlp, users, d, pa.table, items, d};
         else t.b = NtSrc{pa.layer[l - 1].act, nullptr, 2 * out, nullptr, nullptr, 0};
         t.gw = G + off[3 + 2 * l];
         t.gb = G + off[4 + 2 * l];
@@ -646,20 +674,23 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
 
     hipStream_t st = (hipStream_t)stream;
     const int kinds = (s.neumf || want_table) ? 2 : 1;       // MLP over a frozen table has no rows indexed by item: its item order is not read
+    ga.d_item = d_item;
+    ga.item_first = rows ? ga.weight_blocks + kinds * ga.row_blocks : INT_MAX;
+    ga.item_blocks = rows ? (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(n * (d / 4), NT_THREADS)) : 0;
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
     if (drop_on) {
-        if (want_table) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+        if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
         else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
     }
-    else if (want_table) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+    else if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
     else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
     PMGT_LAUNCH_OK();
-    const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks);
+    const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks + ga.item_blocks);
     if (drop_on && dr.p_emb > 0.f) {                         // (launch 2 draws the emb mask only)
-        if (want_table) hipLaunchKernelGGL((ncf_train_grads_kernel<true, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+        if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
         else hipLaunchKernelGGL((ncf_train_grads_kernel<false, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
     }
-    else if (want_table) hipLaunchKernelGGL((ncf_train_grads_kernel<true, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+    else if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
     else hipLaunchKernelGGL((ncf_train_grads_kernel<false, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
     PMGT_LAUNCH_OK();
     return 0;
@@ -694,6 +725,17 @@ int pmgt_ncf_train_grad_dropout(const pmgt_ncf_train* head, const int64_t* users
     const char* who = "pmgt_ncf_train_grad_dropout";
     PMGT_CHECK(drop != nullptr, -2, "%s: NULL drop", who);
     return nt_grad(who, head, users, items, labels, n, loss, logits, table_grad != nullptr, table_grad, drop, workspace, workspace_bytes, stream);
+}
+
+int64_t pmgt_ncf_train_rows_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n) {
+    return nt_workspace_bytes(factor_num, num_layers, kind, n, true, "pmgt_ncf_train_rows_workspace_bytes");
+}
+
+int pmgt_ncf_train_grad_rows(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                             float* logits, const float* x_item, float* d_item, const pmgt_ncf_dropout* drop, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+    return nt_grad("pmgt_ncf_train_grad_rows", head, users, items, labels, n, loss, logits, false, nullptr, drop, workspace, workspace_bytes,
+                   stream, true, x_item, d_item);
 }
 
 }  // extern "C"

@@ -14,6 +14,11 @@
 // (torch.nn.utils.clip_grad_norm_ on fp32 gradients reports the same Inf norm for those).
 // Kept out of csrc/: the plain step and every kernel bench.py measures (and fingerprints there) stay byte for byte what they were.  The
 // gradient-norm partials are csrc/optim.hip's own kernel, so every form is the same three launches, no sync, no allocation.
+// Segments (pmgt_op_adamw_segments): up to PMGT_ADAM_MAX_SEGMENTS disjoint flat buffers clipped by ONE global norm and stepped by one counter,
+// each at a rate of its own -- an encoder fine-tuned through a head, two buffers, the encoder's learning rate its own.  One norm launch and
+// one update launch per segment around one prepare launch.
+#include <cmath>
+
 #include "../../include/pmgt_ops.h"
 #include "../csrc/optim.h"
 
@@ -133,6 +138,59 @@ __global__ __launch_bounds__(256) void adamw_step_kernel(float* __restrict__ p, 
     }
 }
 
+// ---- several flat buffers as ONE optimizer (pmgt_op_adamw_segments): the norm over all of them, one clip coefficient, one step counter, one
+// pair of bias corrections; per segment a rate of its own.  The partials of segment s are sqnorm_part_kernel's, at part + 1024 s.
+struct SegParts {
+    int count;
+    int nparts[PMGT_ADAM_MAX_SEGMENTS];
+};
+
+// adam_prepare_kernel of csrc/optim.hip over the partials of every segment: a lane adds its partials of segment 0, then of segment 1, ..., in
+// fp64 (ONE segment: that kernel's sum in that kernel's order, so the same bits); scal[4] = lr as the scheduled form leaves it
+__global__ __launch_bounds__(64) void adam_prepare_segments_kernel(const float* __restrict__ part, const SegParts sp, float max_norm, float lr,
+                                                                   float b1, float b2, int64_t* __restrict__ step, float* __restrict__ scal) {
+    double s = 0.0;
+    for (int k = 0; k < sp.count; ++k)
+        for (int i = threadIdx.x; i < sp.nparts[k]; i += 64) s += (double)part[k * 1024 + i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) {
+        const int64_t t = step[0] + 1;
+        step[0] = t;
+        const double norm = sqrt(s);
+        double coef = 1.0;
+        if (max_norm > 0.f) coef = fmin((double)max_norm / (norm + 1e-6), 1.0);
+        const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+        scal[0] = (float)coef;
+        scal[1] = (float)((double)lr / bc1);
+        scal[2] = (float)(1.0 / sqrt(bc2));
+        scal[3] = (float)norm;
+        scal[4] = lr;
+    }
+}
+
+// adamw_kernel of csrc/optim.hip, the same fp32 arithmetic in the same order, on one segment: the step size is scal[1] * lr_scale and the
+// decay term's rate lr_seg = lr * lr_scale (the host's fp32 product); lr_scale == 1 multiplies by exactly 1: that kernel's bits.
+// lr_scale == 0: p * (1 - 0) - 0 * (m / denom) = p bit for bit (denom >= eps > 0), while m and v move.
+__global__ __launch_bounds__(256) void adamw_segment_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const uint8_t* __restrict__ decay, int64_t n, float lr_seg,
+                                                            float wd, float b1, float b2, float eps, float lr_scale,
+                                                            const float* __restrict__ scal) {
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float coef = scal[0], step_size = scal[1] * lr_scale, inv_sqrt_bc2 = scal[2];
+    const int cnt = (int)min((int64_t)4, n - i);
+    for (int k = 0; k < cnt; ++k) {
+        const int64_t j = i + k;
+        const float gg = g[j] * coef;
+        float pp = p[j] * (1.f - lr_seg * (decay[j] ? wd : 0.f));
+        const float mm = m[j] * b1 + gg * (1.f - b1);
+        const float vv = v[j] * b2 + gg * gg * (1.f - b2);
+        const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
+        pp -= step_size * (mm / denom);
+        p[j] = pp; m[j] = mm; v[j] = vv;
+    }
+}
+
 __global__ __launch_bounds__(256) void lr_schedule_kernel(const LrSchedule sched, float lr, int64_t first_step, int n, float* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = (float)scheduled_lr(sched, (double)lr, first_step + i);
@@ -240,6 +298,39 @@ int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const ui
     StepGuard gd;
     if (int rc = guard_from(guard, "pmgt_op_adamw_guarded", &gd)) return rc;
     return adamw_step_derived(adam_args(p, g, m, v, decay, n, lr, wd, b1, b2, eps, max_norm, step, scal, part), s, &gd, (hipStream_t)stream);
+}
+
+int pmgt_op_adamw_segments(const pmgt_adam_segment* segments, int count, float lr, float wd, float b1, float b2, float eps, float max_norm,
+                           int64_t* step, float* scal, float* part, void* stream) {
+    const char* who = "pmgt_op_adamw_segments";
+    PMGT_CHECK(count >= 1 && count <= PMGT_ADAM_MAX_SEGMENTS, -2, "%s: %d segments outside [1, %d]", who, count, PMGT_ADAM_MAX_SEGMENTS);
+    PMGT_CHECK(segments && step && scal && part, -2, "%s: NULL argument", who);
+    SegParts sp = {};
+    sp.count = count;
+    for (int k = 0; k < count; ++k) {
+        const pmgt_adam_segment& s = segments[k];
+        PMGT_CHECK(s.n >= 0, -2, "%s: segment %d has n = %lld", who, k, (long long)s.n);
+        PMGT_CHECK(s.p && s.g && s.m && s.v && s.decay, -2, "%s: segment %d has a NULL pointer", who, k);
+        PMGT_CHECK(std::isfinite(s.lr_scale) && s.lr_scale >= 0.f, -2, "%s: segment %d has lr_scale = %g, not finite or negative", who, k,
+                   (double)s.lr_scale);
+        sp.nparts[k] = (int)std::min<int64_t>(1024, cdiv64(s.n, 1024));
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k < count; ++k) {
+        if (sp.nparts[k] == 0) continue;                     // (an empty segment adds nothing to the norm and steps nothing)
+        hipLaunchKernelGGL(sqnorm_part_kernel, dim3(sp.nparts[k]), dim3(256), 0, st, segments[k].g, segments[k].n, part + 1024 * k);
+        PMGT_LAUNCH_OK();
+    }
+    hipLaunchKernelGGL(adam_prepare_segments_kernel, dim3(1), dim3(64), 0, st, part, sp, max_norm, lr, b1, b2, step, scal);
+    PMGT_LAUNCH_OK();
+    for (int k = 0; k < count; ++k) {
+        const pmgt_adam_segment& s = segments[k];
+        if (s.n == 0) continue;
+        hipLaunchKernelGGL(adamw_segment_kernel, dim3((unsigned)cdiv64(cdiv64(s.n, 4), 256)), dim3(256), 0, st, s.p, s.g, s.m, s.v, s.decay, s.n,
+                           lr * s.lr_scale, wd, b1, b2, eps, s.lr_scale, scal);
+        PMGT_LAUNCH_OK();
+    }
+    return 0;
 }
 
 int pmgt_op_lr_schedule(const pmgt_lr_schedule* sched, float lr, int64_t first_step, int n, float* out, void* stream) {

@@ -7,7 +7,9 @@ ncf_train.py) and the Deep & Cross Network (dcn_head.py, dcn_train.py):
   PairTrainer        the flat buffers of AdamW, the {seed, step} tensor, step() = the gradient entry + pmgt_op_adamw, capture / replay, the state
   fit_pairs          the epoch loop: sampled pairs, steps on slices, validation, early stopping, the best parameters kept and restored
 
-Every refusal speaks in the name of the head that asked (`who`: "ncf_train", "dcn").  torch is imported inside functions: importing this
+finetune.py builds on the same two bases for the NCF head that is trained TOGETHER WITH the encoder (PairGrad over the per-pair rows entry,
+PairTrainer for the head's half of the buffers and of the state); its step and its epoch loop are its own.
+Every refusal speaks in the name of the head that asked (`who`: "ncf_train", "dcn", "finetune").  torch is imported inside functions: importing this
 loads no GPU library."""
 import ctypes as C
 import os
