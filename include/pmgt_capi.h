@@ -457,6 +457,51 @@ int64_t pmgt_ncf_train_rows_workspace_bytes(int factor_num, int num_layers, int 
 int pmgt_ncf_train_grad_rows(const pmgt_ncf_train* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                              float* logits, const float* x_item, float* d_item, const pmgt_ncf_dropout* drop /* NULL: none */,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/* THE REFERENCE'S STAND-ALONE NCF CLASS (pmgt/ncf/models.py; pmgt_amd/ncf.py restates it): the model owns its four embedding tables,
+ * its layer may carry a LayerNorm, and it has two more kinds.  With d = factor_num 2^(num_layers - 1), per pair (u, i):
+ *   h_0 = m_e [embed_user_MLP[u] ; embed_item_MLP[i]],   h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))      (LN_l absent without use_layer_norm)
+ *   g = m_g (embed_user_GMF[u] * embed_item_GMF[i])
+ *   z = predict_layer . h_L (MLP),  . g (GMF),  . [g ; h_L] (NeuMF-end; NeuMF-pre is trained exactly as NeuMF-end),  + predict_layer.bias
+ * LN is torch.nn.LayerNorm (biased variance, (x - mean) / sqrt(var + eps) gamma + beta); the dropout sits BEFORE it.  The masks, their
+ * sites and the RNG are pmgt_ncf_train_grad_dropout's; kind GMF draws the gmf site alone.
+ * THE PARAMETERS are ONE flat fp32 buffer holding only what the kind trains, the gradients another of the same layout;
+ * pmgt_ncf_model_layout gives the offsets in floats (-1: not trained) in the slot order
+ *   0 embed_user_MLP   1 embed_user_GMF   2 embed_item_GMF   3 + 4 l: W_l, b_l, gamma_l, beta_l   19, 20 predict_layer.weight, .bias
+ *   21 embed_item_MLP (train_items: behind the rest, its offset rounded up to a multiple of 8 floats)
+ * and returns the count.  Without LayerNorm, kinds MLP / NeuMF-end / NeuMF-pre, the layout is pmgt_ncf_train_layout's followed by the table,
+ * and the call IS pmgt_ncf_train_grad / _table / _dropout on the same buffers: their bits, their workspace sizes.  Kind GMF reads and
+ * trains no MLP tensor (item_table, table_grad and train_items are ignored; d is not limited).
+ * m->item_table is embed_item_MLP.weight [item_num][d] and may point into params; with train_items, table_grad [item_num][d] is written
+ * whole and may point into grads.  Written: loss (one float), logits (fp32 [n] or NULL), the gradient buffer whole (rows of an embedding
+ * table that no pair touches hold +0.0; rows hit by several pairs are summed in pair order).  TWO launches, no atomic, no sync, no
+ * allocation, capturable, the same bits for the same inputs.  Workspace: pmgt_ncf_model_workspace_bytes, 16-byte aligned.
+ * Refused (-2) before anything is launched: factor_num not 8 / 16 / 32 / 64, num_layers outside [1, 4], d > 256 (not GMF), an unknown
+ * kind, a layer_norm_eps that is not finite or negative, n outside [1, PMGT_NCF_TRAIN_MAX_PAIRS], a NULL or misaligned buffer (16 bytes
+ * for the float buffers, 8 for the ids and the rng), a short workspace, a p that is NaN or outside [0, 1), any p > 0 without the rng.
+ * Added without a bump of pmgt_abi_version(): one struct, three entries, nothing existing moved. */
+enum {
+    PMGT_NCF_GMF = 2,                             /* the kinds after PMGT_NCF_MLP and PMGT_NCF_NEUMF_END */
+    PMGT_NCF_NEUMF_PRE = 3,
+    PMGT_NCF_MODEL_TENSORS = 22                   /* the slots of pmgt_ncf_model_layout */
+};
+typedef struct pmgt_ncf_model {
+    int factor_num, num_layers;
+    int kind;                                     /* PMGT_NCF_MLP, _NEUMF_END, _GMF, _NEUMF_PRE */
+    int use_layer_norm;
+    float layer_norm_eps;
+    int train_items;                              /* embed_item_MLP is trained: table_grad is written */
+    int64_t user_num, item_num;
+    const float* item_table;                      /* embed_item_MLP.weight [item_num][d]; only read; may point into params */
+    const float* params;                          /* the flat parameters */
+    float* grads;                                 /* the flat gradients, written whole */
+    float* table_grad;                            /* train_items: [item_num][d], written whole; may point into grads */
+} pmgt_ncf_model;
+int64_t pmgt_ncf_model_layout(int factor_num, int num_layers, int kind, int use_layer_norm, int train_items, int64_t user_num, int64_t item_num,
+                              int64_t* offsets);
+int64_t pmgt_ncf_model_workspace_bytes(int factor_num, int num_layers, int kind, int use_layer_norm, int train_items, int64_t n);
+int pmgt_ncf_model_train_grad(const pmgt_ncf_model* m, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
+                              float* logits /* or NULL */, const pmgt_ncf_dropout* drop /* or NULL */, void* workspace, int64_t workspace_bytes,
+                              void* stream);
 
 /* The DEEP & CROSS NETWORK of the reference's click-through experiment ON THE DEVICE (pmgt/dcn/models.py, scripts/run_dcn.sh): for n
  * (user, item, label) pairs the logits (pmgt_dcn_forward) or the mean loss, the logits and the gradient of that loss with respect to

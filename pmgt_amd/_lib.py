@@ -91,6 +91,13 @@ class NcfTrainC(C.Structure):
                 ("item_num", C.c_int64), ("table", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p)]
 
 
+class NcfModelC(C.Structure):
+    """pmgt_ncf_model (include/pmgt_capi.h): kind = index in NCF_MODEL_KINDS."""
+    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("use_layer_norm", C.c_int), ("layer_norm_eps", C.c_float),
+                ("train_items", C.c_int), ("user_num", C.c_int64), ("item_num", C.c_int64), ("item_table", C.c_void_p), ("params", C.c_void_p),
+                ("grads", C.c_void_p), ("table_grad", C.c_void_p)]
+
+
 class NcfDropoutC(C.Structure):
     """pmgt_ncf_dropout (include/pmgt_capi.h): rng = the device {seed, step} pair."""
     _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_layer", C.c_float * 4)]
@@ -121,6 +128,7 @@ NCF_KINDS = ("MLP", "NeuMF-end")      # PMGT_NCF_* in order
 NCF_MAX_LAYERS, NCF_MAX_USERS = 4, 1 << 20      # PMGT_NCF_MAX_LAYERS, PMGT_NCF_MAX_USERS
 NCF_FACTORS, NCF_MAX_D = (8, 16, 32, 64), 256      # the covered heads (pmgt_ncf_score's comment): factor_num, d = factor_num * 2^(num_layers - 1)
 NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS = 65536, 13      # PMGT_NCF_TRAIN_*
+NCF_MODEL_KINDS, NCF_MODEL_TENSORS = ("MLP", "NeuMF-end", "GMF", "NeuMF-pre"), 22      # PMGT_NCF_* in order (pmgt_ncf_model.kind), PMGT_NCF_MODEL_TENSORS
 NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER = 64, 65, 72      # NCF_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the trained head; layer l = NCF_SITE_LAYER + l
 DCN_MAX_DEEP, DCN_MAX_CROSS, DCN_TENSORS, DCN_MAX_PAIRS = 4, 6, 38, 65536      # PMGT_DCN_*
 DCN_SITE_EMB, DCN_SITE_DEEP, DCN_SITE_CROSS = 64, 72, 80      # DCN_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the DCN; deep layer l = DCN_SITE_DEEP + l, cross layer c = DCN_SITE_CROSS + c
@@ -156,6 +164,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
+    "pmgt_ncf_model_layout", "pmgt_ncf_model_workspace_bytes", "pmgt_ncf_model_train_grad",
     "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
     "pmgt_dcn_train_grad_dropout",
 ]
@@ -326,6 +335,11 @@ def hip():
     L.pmgt_ncf_train_rows_workspace_bytes.restype = i64
     L.pmgt_ncf_train_rows_workspace_bytes.argtypes = [i, i, i, i64]
     L.pmgt_ncf_train_grad_rows.argtypes = [C.POINTER(NcfTrainC), vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... logits, x_item, d_item, drop or NULL, workspace ...)
+    L.pmgt_ncf_model_layout.restype = i64
+    L.pmgt_ncf_model_layout.argtypes = [i, i, i, i, i, i64, i64, vp]
+    L.pmgt_ncf_model_workspace_bytes.restype = i64
+    L.pmgt_ncf_model_workspace_bytes.argtypes = [i, i, i, i, i, i64]
+    L.pmgt_ncf_model_train_grad.argtypes = [C.POINTER(NcfModelC), vp, vp, vp, i64, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... logits, drop or NULL, workspace ...)
     L.pmgt_op_adamw_segments.argtypes = [C.POINTER(AdamSegmentC), i, f, f, f, f, f, f, vp, vp, vp, vp]
     L.pmgt_op_cls_gather.argtypes = [i, vp, i64, i, i, vp, vp]
     L.pmgt_op_cls_scatter.argtypes = [i, vp, i64, i, i, vp, vp]

@@ -275,9 +275,14 @@ def evaluate_ranking(model, sampler, users, candidates, labels, counts, ks=(10, 
         raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
     ks = check_ks(ks)
     users, candidates, labels, counts = check_candidates(model, users, candidates, labels, counts, "evaluate_ranking")
-    dev = model.engine.device
+    from .ncf import NCF
+    if isinstance(model, NCF):                               # the stand-alone model: its own item table, no encoder (`sampler` is not used)
+        dev, width = model.predict_layer.weight.device, model.factor_num << (model.num_layers - 1)
+        table = model.embed_item_MLP.weight.detach() if table is None else table
+    else:
+        dev, width = model.engine.device, model.config.hidden_size
     if table is not None:
-        check_item_table(table, model.item_num, model.config.hidden_size, dev, "evaluate_ranking")
+        check_item_table(table, model.item_num, width, dev, "evaluate_ranking")
     was_training = model.training
     model.eval()
     try:
