@@ -502,6 +502,40 @@ int64_t pmgt_ncf_model_workspace_bytes(int factor_num, int num_layers, int kind,
 int pmgt_ncf_model_train_grad(const pmgt_ncf_model* m, const int64_t* users, const int64_t* items, const float* labels, int64_t n, float* loss,
                               float* logits /* or NULL */, const pmgt_ncf_dropout* drop /* or NULL */, void* workspace, int64_t workspace_bytes,
                               void* stream);
+/* THE STAND-ALONE NCF CLASS SCORED AGAINST THE WHOLE CATALOGUE (the eval-mode head of the model above for n users x n_items items; what
+ * pmgt_ncf_score is to PMGT_NCF).  With pu and pi the caller's split of layer 0 exactly as pmgt_ncf_score states it (pu = embed_user_MLP[users]
+ * W0u^T [n][d], pi = item_table W0e^T + b_0 [n_items][d]), per pair (r, j):
+ *   h_1 = relu(LN_0(pu[r] + pi[j])),   h_(l+1) = relu(LN_l(W_l h_l + b_l)) for l = 1 .. num_layers - 1      (LN_l absent without use_layer_norm)
+ *   scores[r][j] = predict . h_L (MLP),  . g (GMF),  . [g ; h_L] (NeuMF-end, NeuMF-pre)  + predict_bias,   g = gmf_user[users[r]] * gmf_item[j]
+ * LN is the LayerNorm of pmgt_ncf_model_train_grad: two passes (mean, then the squared deviations), biased variance, 1 / sqrt(var + eps).
+ * fp32 end to end on the exact f32-input matrix instruction; one float stored per pair; no atomic, the same bits for the same inputs;
+ * entries [r][n_items .. row_stride) are not written.  A NaN in a row of pi (or of gmf_item) reaches every score of that item and no other.
+ * WITHOUT LayerNorm, kinds MLP / NeuMF-end / NeuMF-pre, the call IS pmgt_ncf_score on the same buffers: its bits.  Kind GMF reads
+ * predict_weight [factor_num], the two GMF tables and users only (pu, pi and every layer pointer are ignored, num_layers is not limited).
+ * A user id outside [0, user_num) (read by the kinds with a GMF branch) is never dereferenced: its row of scores is NaN.
+ * Covered: factor_num 8, 16, 32 or 64; kinds but GMF: num_layers 1 .. PMGT_NCF_MAX_LAYERS and d <= 256; 1 <= n <= PMGT_NCF_MAX_USERS,
+ * 1 <= n_items <= 2^31 - 2, row_stride >= n_items.  Refused (-2) before anything is launched, writing nothing: a model outside these
+ * limits, an unknown kind, a layer_norm_eps that is not finite or negative, a NULL or misaligned buffer, use_layer_norm without gamma /
+ * beta of every layer, a kind with the GMF branch without its tables, more workgroups than a grid holds.
+ * Added without a bump of pmgt_abi_version(): one struct, one entry, nothing existing moved. */
+typedef struct pmgt_ncf_model_head {
+    int factor_num, num_layers;
+    int kind;                                     /* PMGT_NCF_MLP, _NEUMF_END, _GMF, _NEUMF_PRE */
+    int use_layer_norm;
+    float layer_norm_eps;
+    int reserved;
+    int64_t user_num;                             /* rows of gmf_user */
+    const float* weight[PMGT_NCF_MAX_LAYERS];     /* the Linear of layer i [d >> i][d >> (i - 1)]; [0] is the caller's (the split layer) */
+    const float* bias[PMGT_NCF_MAX_LAYERS];       /* [0] is the caller's too: it is in pi */
+    const float* gamma[PMGT_NCF_MAX_LAYERS];      /* use_layer_norm: the LayerNorm of layer i [d >> i], layer 0 included */
+    const float* beta[PMGT_NCF_MAX_LAYERS];
+    const float* predict_weight;                  /* predict_layer.weight [factor_num], both branches [2 factor_num] = [gmf | mlp] */
+    const float* predict_bias;                    /* predict_layer.bias [1] */
+    const float* gmf_user;                        /* embed_user_GMF.weight [user_num][factor_num]; kind MLP: NULL */
+    const float* gmf_item;                        /* embed_item_GMF.weight [n_items][factor_num]; kind MLP: NULL */
+} pmgt_ncf_model_head;
+int pmgt_ncf_model_score(const pmgt_ncf_model_head* head, const float* pu, const float* pi, const int64_t* users, int64_t n, int64_t n_items,
+                         float* scores, int64_t row_stride, void* stream);
 
 /* The DEEP & CROSS NETWORK of the reference's click-through experiment ON THE DEVICE (pmgt/dcn/models.py, scripts/run_dcn.sh): for n
  * (user, item, label) pairs the logits (pmgt_dcn_forward) or the mean loss, the logits and the gradient of that loss with respect to

@@ -98,6 +98,14 @@ class NcfModelC(C.Structure):
                 ("grads", C.c_void_p), ("table_grad", C.c_void_p)]
 
 
+class NcfModelHeadC(C.Structure):
+    """pmgt_ncf_model_head (include/pmgt_capi.h): kind = index in NCF_MODEL_KINDS; device pointers of the NCF class's parameters in state_dict layout."""
+    _fields_ = [("factor_num", C.c_int), ("num_layers", C.c_int), ("kind", C.c_int), ("use_layer_norm", C.c_int), ("layer_norm_eps", C.c_float),
+                ("reserved", C.c_int), ("user_num", C.c_int64), ("weight", C.c_void_p * 4), ("bias", C.c_void_p * 4), ("gamma", C.c_void_p * 4),
+                ("beta", C.c_void_p * 4), ("predict_weight", C.c_void_p), ("predict_bias", C.c_void_p), ("gmf_user", C.c_void_p),
+                ("gmf_item", C.c_void_p)]
+
+
 class NcfDropoutC(C.Structure):
     """pmgt_ncf_dropout (include/pmgt_capi.h): rng = the device {seed, step} pair."""
     _fields_ = [("rng", C.c_void_p), ("p_emb", C.c_float), ("p_layer", C.c_float * 4)]
@@ -164,7 +172,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
-    "pmgt_ncf_model_layout", "pmgt_ncf_model_workspace_bytes", "pmgt_ncf_model_train_grad",
+    "pmgt_ncf_model_layout", "pmgt_ncf_model_workspace_bytes", "pmgt_ncf_model_train_grad", "pmgt_ncf_model_score",
     "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
     "pmgt_dcn_train_grad_dropout",
 ]
@@ -340,6 +348,7 @@ def hip():
     L.pmgt_ncf_model_workspace_bytes.restype = i64
     L.pmgt_ncf_model_workspace_bytes.argtypes = [i, i, i, i, i, i64]
     L.pmgt_ncf_model_train_grad.argtypes = [C.POINTER(NcfModelC), vp, vp, vp, i64, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... logits, drop or NULL, workspace ...)
+    L.pmgt_ncf_model_score.argtypes = [C.POINTER(NcfModelHeadC), vp, vp, vp, i64, i64, vp, i64, vp]
     L.pmgt_op_adamw_segments.argtypes = [C.POINTER(AdamSegmentC), i, f, f, f, f, f, f, vp, vp, vp, vp]
     L.pmgt_op_cls_gather.argtypes = [i, vp, i64, i, i, vp, vp]
     L.pmgt_op_cls_scatter.argtypes = [i, vp, i64, i, i, vp, vp]

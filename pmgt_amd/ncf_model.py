@@ -219,3 +219,35 @@ def ncf_model_grad_host(weights: dict, users, items, labels, dtype=np.float64, l
             np.add.at(grads[ITEM_MLP], items, dh[:, d:])
     assert all(g.dtype == dtype for g in grads.values()) and z.dtype == dtype
     return dtype(loss), z, grads
+
+
+def ncf_model_scores_host(weights: dict, users, table=None, dtype=np.float64, layer_norm_eps: float = 1e-12, kind: str = None) -> np.ndarray:
+    """NCF.head in eval mode for every user of `users` against the whole catalogue -> logits [len(users), I] with (users[r], item j) at
+    [r, j], every operation in `dtype`, layer 0 on the UNSPLIT concatenation: the yardstick of pmgt_ncf_model_score.  The pair rows are those
+    of ncf_model_grad_host on users = repeat(users, I), items = tile(arange(I), n), so the logits are that function's, bit for bit.
+    `weights` is keyed like the NCF class's state_dict; `table` [I, d] stands in for embed_item_MLP.weight (None: that tensor).  Kind GMF
+    reads no MLP tensor and refuses a `table`; NeuMF-pre is scored as NeuMF-end."""
+    w = head_weights(weights, dtype)
+    _, num_layers, kind, ln = ncf_model_shape(w, kind)
+    mlp, gmf = reads_mlp(kind), reads_gmf(kind)
+    if mlp and table is not None:
+        w[ITEM_MLP] = np.asarray(table.detach().cpu().numpy() if hasattr(table, "detach") else table).astype(dtype)
+    elif table is not None:
+        raise ValueError("ncf_model: kind 'GMF' reads no item table")
+    n_items = len(w[ITEM_MLP] if mlp else w[ITEM_GMF])
+    if gmf and len(w[ITEM_GMF]) < n_items:
+        raise ValueError("ncf_model: embed_item_GMF.weight has fewer rows than the item table")
+    users = np.asarray(users, dtype=np.int64)
+    if users.ndim != 1 or (len(users) and not (0 <= users.min() and users.max() < len(w[USER_MLP] if mlp else w[USER_GMF]))):
+        raise ValueError("ncf_model: users must be one-dimensional ids inside the user tables")
+    n = len(users)
+    pu, pi = np.repeat(users, n_items), np.tile(np.arange(n_items, dtype=np.int64), n)
+    feats = []
+    if gmf:
+        feats.append(w[USER_GMF][pu] * w[ITEM_GMF][pi])
+    if mlp:
+        feats.append(_mlp_forward(w, pu, pi, num_layers, ln, layer_norm_eps, {})[0][-1])
+    feat = feats[0] if len(feats) == 1 else np.concatenate(feats, axis=1)
+    z = feat @ w[OUT_W].reshape(-1) + w[OUT_B][0]
+    assert z.dtype == dtype
+    return z.reshape(n, n_items)

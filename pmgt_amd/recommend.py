@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import NCF_FACTORS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_MAX_USERS, TOPK_FLAG_NAN, TOPK_FLAG_SHORT, TOPK_MAX_K  # noqa: F401
 from .evaluation import score_key
+from .ncf_model import check_ncf_model_covered
 from .ncf_head import check_head_covered, check_ids, check_item_table, head_shape, head_state, ncf_head_host  # noqa: F401
 
 SCORE_WORKSPACE_BYTES = 256 << 20                # recommend(batch_users=None): the [batch, I] fp32 score rows stay within this
@@ -147,6 +148,89 @@ class NcfScorer:
         return out
 
 
+class NcfModelScorer:
+    """NcfScorer for the reference's stand-alone NCF class (ncf.py): the fused eval-mode head with or without LayerNorm, kinds MLP, GMF,
+    NeuMF-end and NeuMF-pre (scored as NeuMF-end), by pmgt_ncf_model_score.  `weights`: the model's parameters as fp32 DEVICE tensors keyed
+    like its state_dict (a whole state_dict serves: pass kind=, which a state_dict alone does not tell); `table` [I, d] fp32 on the same
+    device stands in for embed_item_MLP.weight (None: that tensor).  Pi = table W0e^T + b0 is computed once; score(users) computes Pu and
+    launches.  Kind GMF has no Pi / Pu and refuses a `table`.  Nothing in here copies to the host or waits for the device."""
+
+    def __init__(self, weights: dict, table=None, kind: str = None, layer_norm_eps: float = 1e-12):
+        import torch
+        from . import ncf_model as M
+        self.lib = _lib.hip()
+        self.factor, self.num_layers, self.kind, self.ln = M.ncf_model_shape(weights, kind)
+        mlp, gmf = M.reads_mlp(self.kind), M.reads_gmf(self.kind)
+        M.check_ncf_model_covered(self.factor, self.num_layers if mlp else 1, self.kind, layer_norm_eps)      # (GMF: whatever layers the weights hold)
+        self.d = self.factor << (self.num_layers - 1) if mlp else 0
+        need = [M.OUT_W, M.OUT_B] + ([M.USER_GMF, M.ITEM_GMF] if gmf else [])
+        if mlp:
+            need += [M.USER_MLP] + [k for i in range(self.num_layers) for k in M.layer_keys(i, self.ln)]
+            if table is None:
+                table = weights[M.ITEM_MLP].detach()
+            check_item_table(table, None, self.d, None, "ncf_model_score")
+            device = table.device
+        else:
+            if table is not None:
+                raise ValueError("ncf_model_score: kind 'GMF' reads no item table")
+            device = weights[M.ITEM_GMF].device
+            if device.type != "cuda":
+                raise ValueError("ncf_model_score: the weights must be on a GPU")
+        self.w = {}
+        for key in need:
+            t = weights[key]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device:
+                raise ValueError(f"ncf_model_score: {key} must be an fp32 tensor on the table's device")
+            self.w[key] = t.detach().contiguous()
+        self.device = device
+        self.n_items = int(table.shape[0] if mlp else self.w[M.ITEM_GMF].shape[0])
+        self.user_num = int(self.w[M.USER_MLP if mlp else M.USER_GMF].shape[0])
+        if tuple(self.w[M.OUT_W].shape) != (1, self.factor * (2 if mlp and gmf else 1)):
+            raise ValueError(f"ncf_model_score: predict_layer.weight {tuple(self.w[M.OUT_W].shape)} does not fit kind {self.kind!r}")
+        if gmf and (self.w[M.ITEM_GMF].shape[0] < self.n_items or self.w[M.USER_GMF].shape[0] != self.user_num
+                    or self.w[M.ITEM_GMF].shape[1] != self.factor):
+            raise ValueError("ncf_model_score: the GMF tables do not fit the MLP tables")
+        h = _lib.NcfModelHeadC()
+        h.factor_num, h.num_layers, h.kind, h.user_num = self.factor, max(self.num_layers, 1), _lib.NCF_MODEL_KINDS.index(self.kind), self.user_num
+        h.use_layer_norm, h.layer_norm_eps = int(self.ln), float(layer_norm_eps)
+        self.pi = self._w0u_t = None
+        if mlp:
+            for i in range(self.num_layers):
+                keys = M.layer_keys(i, self.ln)
+                out = self.d >> i
+                if tuple(self.w[keys[0]].shape) != (out, 2 * out) or any(tuple(self.w[k].shape) != (out,) for k in keys[1:]):
+                    raise ValueError(f"ncf_model_score: the tensors of layer {i} must be [{out}, {2 * out}] and [{out}]")
+                if i:
+                    h.weight[i], h.bias[i] = self.w[keys[0]].data_ptr(), self.w[keys[1]].data_ptr()
+                if self.ln:
+                    h.gamma[i], h.beta[i] = self.w[keys[2]].data_ptr(), self.w[keys[3]].data_ptr()
+            w0, b0 = (self.w[k] for k in M.layer_keys(0, self.ln)[:2])
+            self._w0u_t = w0[:, :self.d].t().contiguous()
+            self.pi = torch.addmm(b0, table, w0[:, self.d:].t()).contiguous()
+        h.predict_weight, h.predict_bias = self.w[M.OUT_W].data_ptr(), self.w[M.OUT_B].data_ptr()
+        if gmf:
+            h.gmf_user, h.gmf_item = self.w[M.USER_GMF].data_ptr(), self.w[M.ITEM_GMF].data_ptr()
+        self._user_mlp = self.w[M.USER_MLP] if mlp else None
+        self._head = h
+
+    def score(self, users, out=None):
+        """NcfScorer.score's contract: users int64 [n] on the device -> scores fp32 [n, row_stride]; `out` is written in place."""
+        import torch
+        n = int(users.shape[0])
+        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.device or not users.is_contiguous() or n < 1:
+            raise ValueError("ncf_model_score: users must be a contiguous int64 tensor [n >= 1] on the table's device")
+        if out is None:
+            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
+                or out.device != self.device:
+            raise ValueError(f"ncf_model_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
+        pu = self._user_mlp.index_select(0, users) @ self._w0u_t if self.pi is not None else None
+        _lib.check(self.lib.pmgt_ncf_model_score(C.byref(self._head), pu.data_ptr() if pu is not None else 0,
+                                                 self.pi.data_ptr() if pu is not None else 0, users.data_ptr(), n, self.n_items,
+                                                 out.data_ptr(), int(out.shape[1]), _lib.stream()))
+        return out
+
+
 class TopkRows:
     """pmgt_topk_rows over score rows of `n_items` live entries, up to `max_rows` rows a call, with an optional exclusion CSR over user ids
     (indptr int64 [user_num + 1], items int32; validated on the host by check_csr).  select(scores, users) -> (items int32 [n, k], scores
@@ -223,6 +307,9 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     impl="device": pmgt_ncf_score then pmgt_topk_rows per batch; nothing is copied to the host and nothing waits inside the loop, one copy
       at the end fetches items, scores and flags.  impl="host": the yardstick -- `model.head` on chunks of pair rows, the full score rows
       copied out, topk_host.
+    model may also be the reference's stand-alone NCF class (ncf.py; any kind, with or without LayerNorm): `sampler` is then unused (pass
+      None), the device is that of the parameters, `table` defaults to model.embed_item_MLP.weight (a trainer's table serves, no copy; kind
+      GMF reads none and refuses one), impl="device" is NcfModelScorer + TopkRows in the same loop, and impl="host" on a CPU model needs no GPU.
     Raises ValueError for users or excluded ids outside the model's tables, k outside [1, 1024], a user with a NaN score among their
     eligible items (naming how many users), and -- impl="device" only -- a head shape the kernel does not cover."""
     if impl not in ("host", "device"):
@@ -233,45 +320,64 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
         raise ValueError(f"recommend: users {users.shape} must be [U >= 1]")
     check_ids("users", users, model.user_num, "recommend")
     indptr, excl = exclusion_csr(exclude, model.user_num, model.item_num)
+    import torch
+    from .ncf import NCF
+    standalone = isinstance(model, NCF)                       # the reference's stand-alone class: its own tables, no encoder, no sampler
     if impl == "device":
-        check_head_covered(model.factor_num, model.num_layers, model.model)
+        if standalone:
+            check_ncf_model_covered(model.factor_num, 1 if model.model == "GMF" else model.num_layers, model.model, model.layer_norm_eps)
+        else:
+            check_head_covered(model.factor_num, model.num_layers, model.model)
     if batch_users is not None and (not isinstance(batch_users, (int, np.integer)) or batch_users < 1):
         raise ValueError(f"recommend: batch_users = {batch_users!r} must be a positive integer or None")
-    import torch
-    from .evaluation import encode_catalogue
     n_users, n_items = len(users), model.item_num
     batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
-    if table is None:
-        was_training = model.training
-        model.eval()
-        try:
-            table = encode_catalogue(model, sampler, threads=threads, seed=seed)
-        finally:
-            model.train(was_training)
-    dev = model.engine.device
-    check_item_table(table, n_items, model.config.hidden_size, dev, "recommend")
-    if impl == "host":
-        was_training = model.training
-        model.eval()
-        try:
-            s = host_scores(model, table, users)
-        finally:
-            model.train(was_training)
-        items, scores, flags = topk_host(s, k, indptr, excl, users)
+    if standalone:
+        dev = model.predict_layer.weight.device
+        if model.model == "GMF":
+            if table is not None:
+                raise ValueError("recommend: kind 'GMF' reads no item table")
+        else:
+            if table is None:
+                table = model.embed_item_MLP.weight.detach()
+            check_item_table(table, n_items, model.factor_num << (model.num_layers - 1), dev, "recommend")
     else:
-        with torch.no_grad():
-            scorer = NcfScorer(head_state(model), table)
-            picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
-            users_d = torch.from_numpy(users).to(dev)
-            out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
-                   torch.empty(n_users, dtype=torch.int32, device=dev))
-            work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
-            for lo in range(0, n_users, batch):
-                hi = min(lo + batch, n_users)
-                scorer.score(users_d[lo:hi], out=work)
-                picker.select(work[: hi - lo], users_d[lo:hi], out=tuple(t[lo:hi] for t in out))
-            items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
-        flags = flags.view(np.uint32)
+        if table is None:
+            from .evaluation import encode_catalogue
+            was_training = model.training
+            model.eval()
+            try:
+                table = encode_catalogue(model, sampler, threads=threads, seed=seed)
+            finally:
+                model.train(was_training)
+        dev = model.engine.device
+        check_item_table(table, n_items, model.config.hidden_size, dev, "recommend")
+    was_training, set_mode = model.training, impl == "host" or standalone
+    if set_mode:
+        model.eval()
+    try:
+        if impl == "host":
+            # (kind GMF: model.head ignores the item rows; an empty table carries the item count and the device)
+            s = host_scores(model, torch.empty(n_items, 0, device=dev) if table is None else table, users)
+            items, scores, flags = topk_host(s, k, indptr, excl, users)
+        else:
+            with torch.no_grad():
+                scorer = NcfModelScorer(model.state_dict(), table, model.model, model.layer_norm_eps) if standalone \
+                    else NcfScorer(head_state(model), table)
+                picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
+                users_d = torch.from_numpy(users).to(dev)
+                out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
+                       torch.empty(n_users, dtype=torch.int32, device=dev))
+                work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
+                for lo in range(0, n_users, batch):
+                    hi = min(lo + batch, n_users)
+                    scorer.score(users_d[lo:hi], out=work)
+                    picker.select(work[: hi - lo], users_d[lo:hi], out=tuple(t[lo:hi] for t in out))
+                items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
+            flags = flags.view(np.uint32)
+    finally:
+        if set_mode:
+            model.train(was_training)
     n_nan = int(np.count_nonzero(flags & TOPK_FLAG_NAN))
     if n_nan:
         raise ValueError(f"recommend: {n_nan} of {n_users} users have a NaN score among their eligible items")
