@@ -146,6 +146,15 @@ def test_bf16_mode_tracks_fp32(name):
     ref.pretrain_step(dev_batch(case["batch"]), training=True, backward=True, nfr_inject=inj)
     cos = torch.nn.functional.cosine_similarity(eng.grads, ref.grads, dim=0).item()
     assert cos > 0.99, cos
+    # ... and every quantity within the measured bf16 noise of the step (tests/bf16_measure_util.py): the full last layer, as this step ran it
+    from tests import bf16_measure_util as bm
+    _, inj_cpu = inject_for(case)
+    got = bm.engine_quantities(eng, out)
+    o64 = bm.run_oracle(case, inj_cpu)
+    e16 = bm.run_oracle(case, inj_cpu, store=bm.make_store(case["cfg"], bm.tokens_of(case), False, case["n_nodes"]))
+    rt = bm.ratios(got, o64, e16)
+    print(f"bf16 step measure {name} (full last layer): worst {bm.worst(rt)}")
+    assert not bm.failing(rt), bm.failing(rt)
 
 
 def test_device_nfr_masking_statistics_and_dropout_training():
