@@ -621,6 +621,38 @@ typedef struct pmgt_dcn_dropout {
 int pmgt_dcn_train_grad_dropout(const pmgt_dcn_head* head, const int64_t* users, const int64_t* items, const float* labels, int64_t n,
                                 float* loss, float* logits /* or NULL */, const pmgt_dcn_dropout* drop, void* workspace,
                                 int64_t workspace_bytes, void* stream);
+/* THE DCN SCORED AGAINST THE WHOLE CATALOGUE (the eval-mode model above for n users x n_items items; what pmgt_ncf_model_score is to the
+ * NCF class).  The deep net is the NCF tower with d = E, layers L and last width 2 F: pu = user_embeddings[users] W_0[:, :E]^T [n][E] and
+ * pi = item_table W_0[:, E:]^T + b_0 [n_items][E] are the caller's split of deep layer 0, and per pair (r, j)
+ *   h_1 = relu(LN_0(pu[r] + pi[j])),   h_(l+1) = relu(LN_l(W_l h_l + b_l)) for l = 1 .. L - 1      (LN_l absent without use_layer_norm)
+ * on the exact f32-input matrix instruction (L = 1: a vector kernel, one pair a thread), LN with two passes, biased variance and
+ * 1 / sqrt(var + eps).  THE CROSS NET COLLAPSES because its layer adds x0: with w_C := output_weight[:D], the half of a D-vector [0, E) for
+ * a user row and [E, D) for an item row, and for a table row v of a half
+ *   d_c(v) = sum_j v_j g_c[j],   g_0 = w_0[half],   g_c = w_c[half] (no LayerNorm) or gamma_(c-1)[half] * w_c[half] (LayerNorm),   c = 1 .. C
+ *   without LayerNorm   a = 1;  for c = 0 .. C-1: a = a (d_c(u) + d_c(i)) + 1;   z_cross = a (d_C(u) + d_C(i))
+ *   with LayerNorm      mu(v) the row mean, q(v) = sum_j (v_j - mu(v))^2,  m0 = (mu(u) + mu(i)) / 2,
+ *                       v0 = (q(u) + q(i) + E ((mu(u) - m0)^2 + (mu(i) - m0)^2)) / D;   s = d_0(u) + d_0(i);
+ *                       for c = 0 .. C-1: k = s + 1, t = k / sqrt(k^2 v0 + eps), s = t (d_(c+1)(u) + d_(c+1)(i) - m0 K_c) + B_c;   z_cross = s
+ *                       K_c = sum_D gamma_c w_(c+1),  B_c = sum_D beta_c w_(c+1)
+ *   scores[r][j] = (z_cross + output_weight[D:] . h_L) + output_bias
+ * pmgt_dcn_score_rows writes, for `rows` rows of a table [rows][E] of `half` (0: user rows, 1: item rows), PMGT_DCN_SCORE_ROW_STRIDE floats
+ * a row: [0] mu, [1] q (both 0 without LayerNorm, never read then), [2 + c] d_c for c = 0 .. C, zeros behind.  One wave a row, a fixed
+ * order of sums.  The caller runs it once over the item table and once a call over the gathered user rows user_embeddings[users].
+ * pmgt_dcn_score reads those two arrays (user_rows [n][stride], item_rows [n_items][stride]) and, with LayerNorm, consts: K_c at [c] and
+ * B_c at [PMGT_DCN_MAX_CROSS + c], 2 PMGT_DCN_MAX_CROSS device floats (without LayerNorm it is not read and may be NULL).  Of head->params
+ * it reads the deep layers 1 .. L - 1, every deep LayerNorm, output_weight[D:] and output_bias -- a trainer's flat buffer serves in place;
+ * neither embedding table is read (head->item_num only addresses the layout; n_items is the row count of pi and item_rows).
+ * fp32 end to end; one float stored per pair; no atomic, the same bits for the same inputs; entries [r][n_items .. row_stride) are not
+ * written.  A NaN in an item's row reaches every score of that item and no other, a NaN in a user's row that user's scores only.  A user
+ * id outside [0, user_num) is never dereferenced: its row of scores is NaN.
+ * Refused (-2) before anything is launched, writing nothing: a shape outside pmgt_dcn_train_grad's, n outside [1, PMGT_NCF_MAX_USERS],
+ * n_items or rows < 1, row_stride < n_items, half not 0 or 1, a NULL or misaligned buffer (parameters, pu, pi, tables and row scalars: 16
+ * bytes; users: 8; scores and consts: 4), a layer_norm_eps that is NaN, negative or infinite, more workgroups than a grid holds.
+ * Added without a bump of pmgt_abi_version(): two entries, nothing existing moved. */
+enum { PMGT_DCN_SCORE_ROW_STRIDE = 12 };             /* floats a row of pmgt_dcn_score_rows: a multiple of 4, at least PMGT_DCN_MAX_CROSS + 3 */
+int pmgt_dcn_score_rows(const pmgt_dcn_head* head, const float* table, int64_t rows, int half, float* out, void* stream);
+int pmgt_dcn_score(const pmgt_dcn_head* head, const float* pu, const float* pi, const float* user_rows, const float* item_rows,
+                   const float* consts, const int64_t* users, int64_t n, int64_t n_items, float* scores, int64_t row_stride, void* stream);
 
 /* Weight averaging ON THE DEVICE over the flat parameter buffer: the StochasticWeightAveraging callback's running mean
  * (pmgt/callbacks.py:44-381 over swa_init / swa_step / swap_swa_params, pmgt/utils/train.py:39-85) and a per-step exponential average

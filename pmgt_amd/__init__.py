@@ -1,10 +1,10 @@
 """pmgt_amd — MI355X-native PMGT pre-training hot path (HIP kernels behind the reference's Python surface)."""
 from .configuration_pmgt import PMGTConfig  # noqa: F401
 # (binds the name `recommend` to the function: the submodule stays reachable as `from pmgt_amd.recommend import ...`)
-from .recommend import NcfModelScorer, ncf_head_host, recommend, topk_host  # noqa: F401
+from .recommend import DcnScorer, NcfModelScorer, ncf_head_host, recommend, topk_host  # noqa: F401
 from .ncf_train import (NcfHeadTrainer, fit_ncf, ncf_dropout_keep, ncf_dropout_masks, ncf_head_grad_host, ng_sample,  # noqa: F401
                         normalize_item_table)
-from .dcn_head import check_dcn_covered, dcn_dropout_masks, dcn_head_grad_host, dcn_head_host, dcn_layout  # noqa: F401
+from .dcn_head import check_dcn_covered, dcn_dropout_masks, dcn_head_grad_host, dcn_head_host, dcn_layout, dcn_scores_host  # noqa: F401
 from .dcn import DCN  # noqa: F401
 from .dcn_train import DcnGrad, DcnTrainer, evaluate_ctr, fit_dcn  # noqa: F401
 from .ncf_model import check_ncf_model_covered, ncf_model_grad_host, ncf_model_layout, ncf_model_scores_host  # noqa: F401
@@ -16,4 +16,4 @@ __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_gr
            "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks", "DCN", "DcnGrad", "DcnTrainer", "evaluate_ctr", "fit_dcn",
            "check_dcn_covered", "dcn_layout", "dcn_head_host", "dcn_head_grad_host", "dcn_dropout_masks", "ncf_head_rows_grad_host", "PmgtNcfTrainer", "finetune_batches", "fit_pmgt_ncf",
            "check_ncf_model_covered", "ncf_model_grad_host", "ncf_model_layout", "NcfModelGrad", "NcfModelTrainer", "fit_ncf_model",
-           "ncf_model_scores_host", "NcfModelScorer"]
+           "ncf_model_scores_host", "NcfModelScorer", "dcn_scores_host", "DcnScorer"]

@@ -140,6 +140,7 @@ NCF_MODEL_KINDS, NCF_MODEL_TENSORS = ("MLP", "NeuMF-end", "GMF", "NeuMF-pre"), 2
 NCF_SITE_EMB, NCF_SITE_GMF, NCF_SITE_LAYER = 64, 65, 72      # NCF_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the trained head; layer l = NCF_SITE_LAYER + l
 DCN_MAX_DEEP, DCN_MAX_CROSS, DCN_TENSORS, DCN_MAX_PAIRS = 4, 6, 38, 65536      # PMGT_DCN_*
 DCN_SITE_EMB, DCN_SITE_DEEP, DCN_SITE_CROSS = 64, 72, 80      # DCN_SITE_* of ops/ncf_head.h (documented in include/pmgt_capi.h): the dropout sites of the DCN; deep layer l = DCN_SITE_DEEP + l, cross layer c = DCN_SITE_CROSS + c
+DCN_SCORE_ROW_STRIDE = 12      # PMGT_DCN_SCORE_ROW_STRIDE: floats a row of pmgt_dcn_score_rows (mu, q, d_0 .. d_C, zeros)
 DCN_FACTORS, DCN_MAX_E = (8, 16, 32, 64), 256      # the covered shapes (pmgt_dcn_train_grad's comment): factor_num, E = factor_num * 2^deep_layers
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 
@@ -174,7 +175,7 @@ HIP_SYMBOLS = [
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
     "pmgt_ncf_model_layout", "pmgt_ncf_model_workspace_bytes", "pmgt_ncf_model_train_grad", "pmgt_ncf_model_score",
     "pmgt_dcn_layout", "pmgt_dcn_workspace_bytes", "pmgt_dcn_forward", "pmgt_dcn_train_grad",
-    "pmgt_dcn_train_grad_dropout",
+    "pmgt_dcn_train_grad_dropout", "pmgt_dcn_score_rows", "pmgt_dcn_score",
 ]
 OPS_SYMBOLS = [
     "pmgt_op_gemm_nt", "pmgt_op_gemm_tn_slab_elems", "pmgt_op_gemm_tn", "pmgt_op_gemm_tn_bias", "pmgt_op_colsum",
@@ -358,6 +359,8 @@ def hip():
     L.pmgt_dcn_workspace_bytes.argtypes = [i, i, i, i, i64]
     L.pmgt_dcn_forward.argtypes = [C.POINTER(DcnHeadC), vp, vp, i64, vp, vp, i64, vp]
     L.pmgt_dcn_train_grad.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, i64, vp, vp, vp, i64, vp]
+    L.pmgt_dcn_score_rows.argtypes = [C.POINTER(DcnHeadC), vp, i64, i, vp, vp]      # (head, table, rows, half, out, stream)
+    L.pmgt_dcn_score.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, vp, vp, vp, i64, i64, vp, i64, vp]      # (head, pu, pi, user_rows, item_rows, consts, users, n, n_items, scores, row_stride, stream)
     L.pmgt_dcn_train_grad_dropout.argtypes = [C.POINTER(DcnHeadC), vp, vp, vp, i64, vp, vp, C.POINTER(DcnDropoutC), vp, i64, vp]      # (... logits or NULL, drop ...)
     _hip = L
     return L

@@ -11,6 +11,22 @@ IN TRAINING MODE (pmgt_dcn_train_grad_dropout; masks m = 0 or 1 / (1 - p) per el
   x0 = m_e [user ; item],   x^(c+1) = LN_c(m_c (x0 s_c) + x0),   h_(l+1) = relu(LN_l(m_l (W_l h_l + b_l)))
 the added x0 is the dropped x0, not masked again, and the deep dropout sits BEFORE the LayerNorm (dropped zeros enter its statistics).
 What the DCN shares with the other pair head, the NCF head -- the id and pair checks, head_weights, the dropout RNG -- lives in pair_train.py.
+
+SCORED AGAINST THE WHOLE CATALOGUE (dcn_scores_host: the yardstick, by the formulae above on pair rows; pmgt_dcn_score: the kernel, by the
+form below).  The deep net is the NCF tower with layer 0 split into a per-user and a per-item product.  The cross net COLLAPSES, because the
+layer adds x0: every cross state is a scalar multiple of x0 (no LayerNorm) or an affine image of the centred x0 (LayerNorm), so every s_c
+and the output dot split into one scalar per user row plus one per item row.  With wo = output_layer.weight, w_C := wo[:D], the "half" of a
+D-vector [0, E) for a user row and [E, D) for an item row, and for a table row v of a half
+    d_c(v) = sum_j v_j g_c[j],   g_0 = w_0[half],   g_c = w_c[half] (no LayerNorm)  or  gamma_(c-1)[half] * w_c[half] (LayerNorm),  c = 1 .. C:
+  without LayerNorm   a = 1;   for c = 0 .. C-1:  a = a (d_c(u) + d_c(i)) + 1;   z_cross = a (d_C(u) + d_C(i))
+  with LayerNorm      mu(v) the row mean, q(v) = sum_j (v_j - mu(v))^2,
+                      m0 = (mu(u) + mu(i)) / 2,   v0 = (q(u) + q(i) + E ((mu(u) - m0)^2 + (mu(i) - m0)^2)) / D      (pooled; no E[x^2] - m^2)
+                      s = d_0(u) + d_0(i);   for c = 0 .. C-1:  k = s + 1,  t = k / sqrt(k^2 v0 + eps),
+                                                                s = t (d_(c+1)(u) + d_(c+1)(i) - m0 K_c) + B_c;      z_cross = s
+                      K_c = sum_D gamma_c w_(c+1),  B_c = sum_D beta_c w_(c+1):  2 C constants of the model
+  z = (z_cross + wo[D:] . h_L) + output_layer.bias
+About 6 C flops a pair instead of 6 C D, and nothing D-wide is formed per pair outside the deep tower.  dcn_score_constants and
+dcn_row_scalars_host state K_c, B_c, g_c and the row scalars in numpy (the yardstick of pmgt_dcn_score_rows).
 Pure numpy and the bindings module: importing this loads no GPU library."""
 import numpy as np
 
@@ -278,3 +294,61 @@ def dcn_head_grad_host(weights: dict, users, items, labels, dtype=np.float64, la
     np.add.at(grads[ITEM_KEY], items, dx0[:, E:])
     assert all(v.dtype == dtype for v in grads.values()) and z.dtype == dtype
     return dtype(loss), z, grads
+
+
+def dcn_scores_host(weights: dict, users, table=None, dtype=np.float64, layer_norm_eps: float = 1e-12, pair_chunk: int = 1 << 16) -> np.ndarray:
+    """DCN.forward in eval mode for every user of `users` against the whole catalogue -> logits [len(users), I] in `dtype` with (users[r],
+    item j) at [r, j]: the yardstick of pmgt_dcn_score.  _forward on the pair rows users = repeat(u, I), items = tile(arange(I), len(u)) of
+    chunks u of whole users (about pair_chunk pairs each), so a block is dcn_head_host's logits of those pair rows, bit for bit.
+    `table` [I, E] stands in for item_embeddings.weight (None: that tensor)."""
+    w = head_weights(weights, dtype)
+    if table is not None:
+        table = np.asarray(table.detach().cpu().numpy() if hasattr(table, "detach") else table).astype(dtype)
+        if table.ndim != 2 or table.shape[1] != w[USER_KEY].shape[1] or len(table) < 1:
+            raise ValueError(f"dcn: the item table {table.shape} must be [I >= 1, E = {w[USER_KEY].shape[1]}]")
+        w[ITEM_KEY] = table
+    users = np.asarray(users, dtype=np.int64)
+    if users.ndim != 1:
+        raise ValueError(f"dcn: users {users.shape} must be one-dimensional")
+    check_ids("users", users, len(w[USER_KEY]), "dcn")
+    n, n_items = len(users), len(w[ITEM_KEY])
+    out = np.empty((n, n_items), dtype=dtype)
+    per = max(1, int(pair_chunk) // n_items)
+    item_ids = np.arange(n_items, dtype=np.int64)
+    for lo in range(0, n, per):
+        u = users[lo: lo + per]
+        out[lo: lo + len(u)] = _forward(w, np.repeat(u, n_items), np.tile(item_ids, len(u)), layer_norm_eps)[-1].reshape(len(u), n_items)
+    return out
+
+
+def dcn_score_constants(weights: dict, dtype=np.float64):
+    """The model constants of the collapsed cross net (the module's header) -> (g [2][C + 1][E]: g_c of the user half and of the item half,
+    K [C], B [C]); K and B are zeros without LayerNorm."""
+    w = head_weights(weights, dtype)
+    _, _, C, ln = dcn_shape(w)
+    E = w[USER_KEY].shape[1]
+    D = 2 * E
+    ws = [w[f"cross_net.layers.{c}.weight"].reshape(-1) for c in range(C)] + [w[OUT_W].reshape(-1)[:D]]
+    g, K, B = np.empty((2, C + 1, E), dtype=dtype), np.zeros(C, dtype=dtype), np.zeros(C, dtype=dtype)
+    for c in range(C + 1):
+        full = ws[c]
+        if ln and c:
+            p = f"cross_net.layers.{c - 1}.layer_norm."
+            full = w[p + "weight"] * ws[c]
+            K[c - 1], B[c - 1] = full.sum(dtype=dtype), (w[p + "bias"] * ws[c]).sum(dtype=dtype)
+        g[0, c], g[1, c] = full[:E], full[E:]
+    return g, K, B
+
+
+def dcn_row_scalars_host(weights: dict, rows, half: int, dtype=np.float64) -> np.ndarray:
+    """What pmgt_dcn_score_rows writes for the table rows `rows` [m, E] of `half` (0: users, 1: items) -> [m, C + 3] = mu, q, d_0 .. d_C;
+    mu and q are 0 without LayerNorm."""
+    _, _, C, ln = dcn_shape(weights)
+    g = dcn_score_constants(weights, dtype)[0][half]
+    v = np.asarray(rows, dtype=dtype)
+    out = np.zeros((len(v), C + 3), dtype=dtype)
+    if ln:
+        mu = v.mean(axis=1)
+        out[:, 0], out[:, 1] = mu, ((v - mu[:, None]) ** 2).sum(axis=1)
+    out[:, 2:] = v @ g.T
+    return out

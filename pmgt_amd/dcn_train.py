@@ -128,10 +128,11 @@ class DcnTrainer(PairTrainer):
         model._dcn_dropout_seeded = self.rng is not None     # ... and, of a model trained with its dropout, in eval mode
 
 
-def _flat_of(model):
-    """The flat parameter buffer a DcnTrainer gave the model, or a fresh one gathered from its parameters."""
+def _flat_of(model, dropout_ok: bool = False):
+    """The flat parameter buffer a DcnTrainer gave the model, or a fresh one gathered from its parameters.  dropout_ok: the caller runs
+    eval-mode arithmetic only (recommend), so a model with dropout is not refused."""
     import torch
-    dims = _model_dims(model, dropout_ok=bool(getattr(model, "_dcn_dropout_seeded", False)))
+    dims = _model_dims(model, dropout_ok=dropout_ok or bool(getattr(model, "_dcn_dropout_seeded", False)))
     layout, count = dcn_layout(*dims)
     named = dict(model.named_parameters())
     first = named[next(iter(layout))]

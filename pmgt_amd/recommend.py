@@ -15,6 +15,7 @@ from ._lib import NCF_FACTORS, NCF_MAX_D, NCF_MAX_LAYERS, NCF_MAX_USERS, TOPK_FL
 from .evaluation import score_key
 from .ncf_model import check_ncf_model_covered
 from .ncf_head import check_head_covered, check_ids, check_item_table, head_shape, head_state, ncf_head_host  # noqa: F401
+from .dcn_head import ITEM_KEY, USER_KEY, check_dcn_covered, dcn_layout, dcn_scores_host, dcn_shape  # noqa: F401
 
 SCORE_WORKSPACE_BYTES = 256 << 20                # recommend(batch_users=None): the [batch, I] fp32 score rows stay within this
 
@@ -231,6 +232,103 @@ class NcfModelScorer:
         return out
 
 
+class DcnScorer:
+    """NcfModelScorer for the Deep & Cross Network (dcn.py): the fused eval-mode model by pmgt_dcn_score, the deep tower on the NCF scoring
+    tile and the collapsed cross net (dcn_head.py's header) in its epilogue.  `weights_or_flat`: the model's parameters as fp32 DEVICE
+    tensors keyed like its state_dict (a whole state_dict serves; they are gathered into one flat buffer of dcn_layout once), or a pair
+    (dims, flat) = ((factor_num, deep_layers, cross_layers, use_layer_norm, user_num, item_num), the flat fp32 parameter buffer of that
+    layout) -- a DcnTrainer's `params` is then READ IN PLACE, no copy.  `table` [I, E] fp32 on the same device stands in for
+    item_embeddings.weight (None: that tensor).  Built once: Pi = table W0i^T + b0, the item rows' scalars (pmgt_dcn_score_rows) and the 2 C
+    constants K_c, B_c (torch: plumbing); they are a snapshot of the parameters at construction.  score(users) gathers the user rows,
+    computes Pu and their scalars and launches.  Nothing in here copies to the host or waits for the device."""
+
+    def __init__(self, weights_or_flat, table=None, layer_norm_eps: float = 1e-12):
+        import torch
+        if isinstance(weights_or_flat, dict):
+            w = weights_or_flat
+            factor, deep, cross, ln = dcn_shape(w)
+            check_dcn_covered(factor, deep, cross)
+            dims = (factor, deep, cross, ln, int(w[USER_KEY].shape[0]), int(w[ITEM_KEY].shape[0]))
+            layout, count = dcn_layout(*dims)
+            device = w[USER_KEY].device
+            for key, (_, shape) in layout.items():
+                t = w[key]
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"dcn_score: {key} must be an fp32 tensor {tuple(shape)} on the user table's device")
+            flat = torch.empty(count, dtype=torch.float32, device=device)
+            for key, (off, shape) in layout.items():
+                flat[off: off + int(np.prod(shape))].view(shape).copy_(w[key].detach())
+        else:
+            dims, flat = weights_or_flat
+            dims = tuple(int(v) for v in dims)
+            check_dcn_covered(*dims[:3])
+            layout, count = dcn_layout(*dims[:3], bool(dims[3]), *dims[4:])
+            if not isinstance(flat, torch.Tensor) or flat.dtype != torch.float32 or tuple(flat.shape) != (count,) or not flat.is_contiguous():
+                raise ValueError(f"dcn_score: the flat parameters must be a contiguous fp32 tensor [{count}]")
+            flat = flat.detach()
+        eps = float(np.float32(layer_norm_eps))
+        if not (np.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"dcn_score: layer_norm_eps = {layer_norm_eps!r} is not finite or negative")
+        if flat.device.type != "cuda":
+            raise ValueError("dcn_score: the parameters must be on a GPU")
+        self.lib = _lib.hip()
+        self.factor, self.deep, self.cross, self.ln, self.user_num, _ = dims
+        self.ln = bool(self.ln)
+        self.d = E = self.factor << self.deep
+        self.device, self.flat = flat.device, flat
+
+        def view(key):
+            off, shape = layout[key]
+            return flat[off: off + int(np.prod(shape))].view(shape)
+        if table is None:
+            table = view(ITEM_KEY)
+        check_item_table(table, None, E, self.device, "dcn_score")
+        table = table.detach().contiguous()
+        if table.data_ptr() % 16:
+            table = table.clone()
+        self.n_items = int(table.shape[0])
+        self._user_table = view(USER_KEY)
+        w0 = view("deep_net.layers.0.linear.weight")
+        self._w0u_t = w0[:, :E].t().contiguous()
+        self.pi = torch.addmm(view("deep_net.layers.0.linear.bias"), table, w0[:, E:].t()).contiguous()
+        self._consts = torch.zeros(2 * _lib.DCN_MAX_CROSS, dtype=torch.float32, device=self.device)
+        if self.ln:
+            for c in range(self.cross):
+                nxt = view(f"cross_net.layers.{c + 1}.weight" if c + 1 < self.cross else "output_layer.weight").reshape(-1)[:2 * E]
+                p = f"cross_net.layers.{c}.layer_norm."
+                self._consts[c] = (view(p + "weight") * nxt).sum()
+                self._consts[_lib.DCN_MAX_CROSS + c] = (view(p + "bias") * nxt).sum()
+        self._head = _lib.DcnHeadC(self.factor, self.deep, self.cross, int(self.ln), eps, 0, self.user_num, int(dims[5]), flat.data_ptr(), None)
+        self.item_rows = self.rows(table, 1)
+
+    def rows(self, table, half: int):
+        """pmgt_dcn_score_rows: the scalars mu, q, d_0 .. d_C of the rows of `table` [rows, E] of `half` (0: users, 1: items)
+        -> fp32 [rows, DCN_SCORE_ROW_STRIDE]"""
+        import torch
+        out = torch.empty(int(table.shape[0]), _lib.DCN_SCORE_ROW_STRIDE, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pmgt_dcn_score_rows(C.byref(self._head), table.data_ptr(), int(table.shape[0]), half, out.data_ptr(), _lib.stream()))
+        return out
+
+    def score(self, users, out=None):
+        """NcfScorer.score's contract: users int64 [n] on the device -> scores fp32 [n, row_stride]; `out` is written in place."""
+        import torch
+        n = int(users.shape[0])
+        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.device or not users.is_contiguous() or n < 1:
+            raise ValueError("dcn_score: users must be a contiguous int64 tensor [n >= 1] on the parameters' device")
+        if out is None:
+            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
+                or out.device != self.device:
+            raise ValueError(f"dcn_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the parameters' device")
+        rows = self._user_table.index_select(0, users)
+        pu = rows @ self._w0u_t
+        user_rows = self.rows(rows, 0)
+        _lib.check(self.lib.pmgt_dcn_score(C.byref(self._head), pu.data_ptr(), self.pi.data_ptr(), user_rows.data_ptr(), self.item_rows.data_ptr(),
+                                           self._consts.data_ptr(), users.data_ptr(), n, self.n_items, out.data_ptr(), int(out.shape[1]),
+                                           _lib.stream()))
+        return out
+
+
 class TopkRows:
     """pmgt_topk_rows over score rows of `n_items` live entries, up to `max_rows` rows a call, with an optional exclusion CSR over user ids
     (indptr int64 [user_num + 1], items int32; validated on the host by check_csr).  select(scores, users) -> (items int32 [n, k], scores
@@ -295,6 +393,31 @@ def host_scores(model, table, users, pair_chunk: int = 1 << 18) -> np.ndarray:
     return np.concatenate(rows)
 
 
+def dcn_host_scores(model, table, users, pair_chunk: int = 1 << 18) -> np.ndarray:
+    """impl="host" for a dcn.DCN: `model.forward` on chunks of (user, item) pair rows, the full score rows [U, I] copied out.  With a
+    stand-in `table` the item half of x0 is gathered from it and the rest is forward's own modules (eval mode: no dropout)."""
+    import torch
+    dev = model.output_layer.weight.device
+    n_items = model.item_num
+    item_ids = torch.arange(n_items, device=dev)
+    per = max(1, pair_chunk // n_items)
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, len(users), per):
+            u = torch.from_numpy(np.ascontiguousarray(users[lo: lo + per])).to(dev)
+            m = len(u)
+            pu, pi = u[:, None].expand(m, n_items).reshape(-1), item_ids.repeat(m)
+            if table is None:
+                logits = model((pu, pi))
+            else:
+                x = x0 = torch.cat([model.user_embeddings(pu), table[pi]], dim=-1)
+                for layer in model.cross_net.layers:
+                    x = layer(x0, x)
+                logits = model.output_layer(torch.cat([x, model.deep_net.layers(x0)], dim=-1)).view(-1)
+            rows.append(logits.view(m, n_items).cpu().numpy())
+    return np.concatenate(rows)
+
+
 def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int = None, impl: str = "device", table=None, threads: int = 8,
               seed: int = 0):
     """For every user of `users`, the k best items of `model`'s whole catalogue (a PMGT_NCF) that are not in the user's exclusion list
@@ -310,6 +433,10 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     model may also be the reference's stand-alone NCF class (ncf.py; any kind, with or without LayerNorm): `sampler` is then unused (pass
       None), the device is that of the parameters, `table` defaults to model.embed_item_MLP.weight (a trainer's table serves, no copy; kind
       GMF reads none and refuses one), impl="device" is NcfModelScorer + TopkRows in the same loop, and impl="host" on a CPU model needs no GPU.
+    model may also be a dcn.DCN: `sampler` is unused, the device is that of the parameters, `table` [I, E] defaults to
+      model.item_embeddings.weight (the flat buffer of a DcnTrainer that holds the model is read in place), the model is scored in eval mode
+      -- a model with dropout without masks -- and the caller's mode is restored; impl="device" is DcnScorer + TopkRows in the same loop,
+      impl="host" is model.forward on chunks of pair rows + topk_host and needs no GPU on a CPU model.
     Raises ValueError for users or excluded ids outside the model's tables, k outside [1, 1024], a user with a NaN score among their
     eligible items (naming how many users), and -- impl="device" only -- a head shape the kernel does not cover."""
     if impl not in ("host", "device"):
@@ -322,9 +449,13 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     indptr, excl = exclusion_csr(exclude, model.user_num, model.item_num)
     import torch
     from .ncf import NCF
-    standalone = isinstance(model, NCF)                       # the reference's stand-alone class: its own tables, no encoder, no sampler
+    from .dcn import DCN
+    dcn = isinstance(model, DCN)
+    standalone = isinstance(model, NCF) or dcn                # the stand-alone classes: their own tables, no encoder, no sampler
     if impl == "device":
-        if standalone:
+        if dcn:
+            check_dcn_covered(model.factor_num, model.deep_layers, model.cross_layers)
+        elif standalone:
             check_ncf_model_covered(model.factor_num, 1 if model.model == "GMF" else model.num_layers, model.model, model.layer_norm_eps)
         else:
             check_head_covered(model.factor_num, model.num_layers, model.model)
@@ -332,7 +463,11 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
         raise ValueError(f"recommend: batch_users = {batch_users!r} must be a positive integer or None")
     n_users, n_items = len(users), model.item_num
     batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
-    if standalone:
+    if dcn:
+        dev = model.output_layer.weight.device
+        if table is not None:
+            check_item_table(table, n_items, model.factor_num << model.deep_layers, dev, "recommend")
+    elif standalone:
         dev = model.predict_layer.weight.device
         if model.model == "GMF":
             if table is not None:
@@ -356,14 +491,21 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     if set_mode:
         model.eval()
     try:
-        if impl == "host":
+        if impl == "host" and dcn:
+            items, scores, flags = topk_host(dcn_host_scores(model, table, users), k, indptr, excl, users)
+        elif impl == "host":
             # (kind GMF: model.head ignores the item rows; an empty table carries the item count and the device)
             s = host_scores(model, torch.empty(n_items, 0, device=dev) if table is None else table, users)
             items, scores, flags = topk_host(s, k, indptr, excl, users)
         else:
             with torch.no_grad():
-                scorer = NcfModelScorer(model.state_dict(), table, model.model, model.layer_norm_eps) if standalone \
-                    else NcfScorer(head_state(model), table)
+                if dcn:
+                    from .dcn_train import _flat_of
+                    scorer = DcnScorer(_flat_of(model, dropout_ok=True), table, model.layer_norm_eps)
+                elif standalone:
+                    scorer = NcfModelScorer(model.state_dict(), table, model.model, model.layer_norm_eps)
+                else:
+                    scorer = NcfScorer(head_state(model), table)
                 picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
                 users_d = torch.from_numpy(users).to(dev)
                 out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
