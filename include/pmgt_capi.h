@@ -360,6 +360,52 @@ int pmgt_topk_rows(const float* scores, int64_t row_stride, int64_t n, int64_t n
                    const int32_t* excluded, int64_t user_num, int64_t n_excluded, void* workspace, int32_t* out_items, float* out_scores,
                    uint32_t* out_flags, void* stream);
 
+/* EVALUATION ON THE WHOLE CATALOGUE ON THE DEVICE: the exact rank of every held-out (user, item) pair among the user's eligible items, and
+ * nDCG@k / Recall@k / HR@k / MRR from those ranks.  The reference evaluates on sampled candidate lists (pmgt/ncf/trainer.py:202-254); these
+ * entries apply its get_ndcg / get_recall (pmgt/metrics.py:16-37) to each user's whole-catalogue list without building that list.
+ *
+ * RANKS.  scores fp32 [n][row_stride] (n_items live entries; the rest is never read), users int64 [n], the exclusion CSR exactly as
+ * pmgt_topk_rows takes it (indptr = NULL: every item is eligible), and a held-out CSR over the same user ids: held_indptr int64
+ * [user_num + 1], held_items int32 [n_heldout] (the CALLER validates both on the host; entries outside are skipped, never dereferenced).
+ * With the composite c(j) = key(j) << 32 | (0xFFFFFFFF - j) of the selection above (a NaN score has key 0xFFFFFFFF), for row r of user
+ * u = users[r] and every held-out item p of u, at its place in the held-out CSR,
+ *   ranks[h] = 1 + #{ j eligible for u, j != p : c(j) > c(p) }
+ * = the 1-based place of p in pmgt_topk_rows' order with k = everything; the user's other held-out items count like any item.  A held-out
+ * item that is also excluded gets rank 0 and sets PMGT_RANK_HELDOUT_FLAG_EXCLUDED in out_flags[r]; a NaN among the row's eligible scores
+ * sets PMGT_TOPK_FLAG_NAN; out_flags uint32 [n] holds no other bit.  A ROW WHOSE USER HAS NO HELD-OUT ITEM (or an id outside
+ * [0, user_num)) WRITES NOTHING, its flag word included.  Duplicates in an exclusion list are harmless, AT A COST THAT DEPENDS ON ITS ORDER: a
+ * list of L entries in non-decreasing item order (what the Python surface builds) is walked once, L reads per chunk of held-out items; a
+ * list in any other order is still right, but every entry is compared with all entries before it, L^2 / 2 reads by the row's one
+ * workgroup per chunk -- sort long lists (tens of thousands of entries) before passing them.  A duplicate in a held-out list
+ * gets its item's rank at both places; a user in several rows is written by each of them.  One launch, one workgroup per row, no
+ * workspace: the row is read from memory once per chunk of PMGT_RANK_HELDOUT_CHUNK held-out items (more are handled by looping); integer
+ * counting only, so the result is a pure function of the inputs and bitwise repeatable.
+ * Refused (-2), writing nothing: n_items outside [1, 2^31 - 2], n < 1, row_stride < n_items, a NULL or misaligned buffer, user_num < 1,
+ * n_heldout < 0 or without its item array, an exclusion CSR without its item array.
+ *
+ * METRICS.  For the n_users evaluated users (device int64, ids in [0, user_num)) with n_pos = the length of the user's held-out list and
+ * the ranks above, per cut-off k of ks (host ints, 1 .. PMGT_RANK_MAX_KS strictly increasing values in [1, PMGT_RANK_MAX_K]):
+ *   recall_k = #{rank <= k} / n_pos,   dcg_k = the discounts disc[rank - 1] of the ranks <= k added in ascending rank in fp64,
+ *   ndcg_k = dcg_k / idcg[min(n_pos, k) - 1],   hit_k = (min rank <= k),   rr = 1 / min rank
+ * (rank 0 is no rank: it hits nothing; a user without a rank has rr = 0 and every record 0).  disc and idcg are DEVICE fp64 [ks[n_k - 1]]:
+ * the caller's tables 1 / log2(r + 2) and their running sum -- the device evaluates no logarithm.  records fp64 [3 n_k + 1][n_users]:
+ * rows ndcg_k .., recall_k .., hit_k .., rr.  header: 16 words of 8 bytes, fp64 [0 .. 3] the sums of ndcg per k, [4 .. 7] of recall,
+ * [8 .. 11] of hit, [12] of rr over the users in a fixed order (thread t of 256 adds the users t, t + 256, .. ascending, then a fixed
+ * tree), uint64 [13] n_users, [14] the users whose word of `flags` (uint32 [n_users], aligned with users; NULL: none) has
+ * PMGT_TOPK_FLAG_NAN, [15] those with PMGT_RANK_HELDOUT_FLAG_EXCLUDED.  Two launches, no atomic: the same inputs give the same bits.
+ * Refused (-2), writing nothing: a NULL or misaligned buffer (flags may be NULL), n_users < 1, user_num < 1, n_heldout < 1, ks outside
+ * those limits.
+ * Added without a bump of pmgt_abi_version(): two entries, nothing existing moved. */
+#define PMGT_RANK_HELDOUT_CHUNK 1024
+#define PMGT_RANK_HELDOUT_FLAG_EXCLUDED 4u
+#define PMGT_RANK_HELDOUT_HEADER_BYTES 128
+int pmgt_rank_heldout(const float* scores, int64_t row_stride, int64_t n, int64_t n_items, const int64_t* users, const int64_t* indptr,
+                      const int32_t* excluded, int64_t user_num, int64_t n_excluded, const int64_t* held_indptr, const int32_t* held_items,
+                      int64_t n_heldout, int32_t* ranks, uint32_t* out_flags, void* stream);
+int pmgt_rank_heldout_reduce(const int32_t* ranks, const int64_t* held_indptr, const int64_t* users, const uint32_t* flags, int64_t n_users,
+                             int64_t user_num, int64_t n_heldout, const int* ks, int n_k, const double* disc, const double* idcg,
+                             double* records, void* header, void* stream);
+
 /* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
  * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
  * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and

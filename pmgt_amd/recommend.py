@@ -27,33 +27,34 @@ def check_k(k) -> int:
     return int(k)
 
 
-def check_csr(indptr, items, user_num: int, item_num: int):
+def check_csr(indptr, items, user_num: int, item_num: int, who: str = "exclude", what: str = "excluded items"):
     """(indptr int64 [user_num + 1], items int32) validated as pmgt_topk_rows expects its CSR: indptr non-decreasing from 0 to len(items), items in
-    [0, item_num)."""
+    [0, item_num).  `who` and `what` name the list in the messages (the exclusion list unless told otherwise)."""
     indptr = np.ascontiguousarray(indptr, dtype=np.int64)
     items64 = np.ascontiguousarray(items, dtype=np.int64)
     if indptr.shape != (user_num + 1,) or items64.ndim != 1:
-        raise ValueError(f"exclude: indptr {indptr.shape} must be [user_num + 1 = {user_num + 1}] and items one-dimensional")
+        raise ValueError(f"{who}: indptr {indptr.shape} must be [user_num + 1 = {user_num + 1}] and items one-dimensional")
     if indptr[0] != 0 or indptr[-1] != len(items64) or (np.diff(indptr) < 0).any():
-        raise ValueError("exclude: indptr must be non-decreasing from 0 to len(items)")
-    check_ids("excluded items", items64, item_num, "exclude")
+        raise ValueError(f"{who}: indptr must be non-decreasing from 0 to len(items)")
+    check_ids(what, items64, item_num, who)
     return indptr, items64.astype(np.int32)
 
 
-def exclusion_csr(exclude, user_num: int, item_num: int):
+def exclusion_csr(exclude, user_num: int, item_num: int, who: str = "exclude", what: str = "excluded items"):
     """The exclusion CSR over user ids from `exclude`: None (nothing excluded), an iterable of (user, item) pairs -- typically the training
-    interactions --, or a ready (indptr, items) pair of arrays.  -> (indptr int64 [user_num + 1], items int32), each list sorted by item."""
+    interactions --, or a ready (indptr, items) pair of arrays.  -> (indptr int64 [user_num + 1], items int32), each list sorted by item.
+    `who` and `what` name the list in the messages: another list of pairs over the same ids (the held-out set) is built the same way."""
     if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in exclude) \
             and len(exclude[0]) == user_num + 1:
-        return check_csr(exclude[0], exclude[1], user_num, item_num)
+        return check_csr(exclude[0], exclude[1], user_num, item_num, who, what)
     pairs = np.asarray(exclude if isinstance(exclude, np.ndarray) else list(exclude or ()))
     if pairs.size == 0:
         return np.zeros(user_num + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
     if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
-        raise ValueError(f"exclude: expected (user, item) integer pairs, got an array of shape {pairs.shape} and dtype {pairs.dtype}")
+        raise ValueError(f"{who}: expected (user, item) integer pairs, got an array of shape {pairs.shape} and dtype {pairs.dtype}")
     pairs = pairs.astype(np.int64)
-    check_ids("users", pairs[:, 0], user_num, "exclude")
-    check_ids("excluded items", pairs[:, 1], item_num, "exclude")
+    check_ids("users", pairs[:, 0], user_num, who)
+    check_ids(what, pairs[:, 1], item_num, who)
     order = np.lexsort((pairs[:, 1], pairs[:, 0]))
     indptr = np.zeros(user_num + 1, dtype=np.int64)
     np.cumsum(np.bincount(pairs[:, 0], minlength=user_num), out=indptr[1:])
@@ -418,6 +419,81 @@ def dcn_host_scores(model, table, users, pair_chunk: int = 1 << 18) -> np.ndarra
     return np.concatenate(rows)
 
 
+class ModelDispatch:
+    """What recommend() and evaluate_catalogue() need to know of the model class, stated once: a PMGT_NCF (encoder + head over an encoded
+    catalogue table), the reference's stand-alone NCF class (ncf.py) or a dcn.DCN.  In the caller's order: check_covered() (impl="device":
+    the existing check_*_covered of the class), resolve_table() (the default table, check_item_table; sets .dev and .table), then inside the
+    caller's eval-mode block host_scores(users) or scorer().  `who` names the caller in the messages."""
+
+    def __init__(self, model, who: str):
+        from .ncf import NCF
+        from .dcn import DCN
+        self.model, self.who = model, who
+        self.dcn = isinstance(model, DCN)
+        self.standalone = isinstance(model, NCF) or self.dcn      # the stand-alone classes: their own tables, no encoder, no sampler
+        self.n_items = model.item_num
+        self.dev = self.table = None
+
+    def check_covered(self) -> None:
+        model = self.model
+        if self.dcn:
+            check_dcn_covered(model.factor_num, model.deep_layers, model.cross_layers)
+        elif self.standalone:
+            check_ncf_model_covered(model.factor_num, 1 if model.model == "GMF" else model.num_layers, model.model, model.layer_norm_eps)
+        else:
+            check_head_covered(model.factor_num, model.num_layers, model.model)
+
+    def resolve_table(self, sampler, table, threads: int, seed: int) -> None:
+        model, n_items, who = self.model, self.n_items, self.who
+        if self.dcn:
+            dev = model.output_layer.weight.device
+            if table is not None:
+                check_item_table(table, n_items, model.factor_num << model.deep_layers, dev, who)
+        elif self.standalone:
+            dev = model.predict_layer.weight.device
+            if model.model == "GMF":
+                if table is not None:
+                    raise ValueError(f"{who}: kind 'GMF' reads no item table")
+            else:
+                if table is None:
+                    table = model.embed_item_MLP.weight.detach()
+                check_item_table(table, n_items, model.factor_num << (model.num_layers - 1), dev, who)
+        else:
+            if table is None:
+                from .evaluation import encode_catalogue
+                was_training = model.training
+                model.eval()
+                try:
+                    table = encode_catalogue(model, sampler, threads=threads, seed=seed)
+                finally:
+                    model.train(was_training)
+            dev = model.engine.device
+            check_item_table(table, n_items, model.config.hidden_size, dev, who)
+        self.dev, self.table = dev, table
+
+    def sets_mode(self, impl: str) -> bool:
+        """Whether the caller puts the model into eval mode around the scoring (and restores the mode it had)."""
+        return impl == "host" or self.standalone
+
+    def host_scores(self, users) -> np.ndarray:
+        """impl="host": the full score rows [U, I] of `users` as numpy."""
+        import torch
+        if self.dcn:
+            return dcn_host_scores(self.model, self.table, users)
+        # (kind GMF: model.head ignores the item rows; an empty table carries the item count and the device)
+        return host_scores(self.model, torch.empty(self.n_items, 0, device=self.dev) if self.table is None else self.table, users)
+
+    def scorer(self):
+        """impl="device": the fused scorer of the class over the resolved table."""
+        model = self.model
+        if self.dcn:
+            from .dcn_train import _flat_of
+            return DcnScorer(_flat_of(model, dropout_ok=True), self.table, model.layer_norm_eps)
+        if self.standalone:
+            return NcfModelScorer(model.state_dict(), self.table, model.model, model.layer_norm_eps)
+        return NcfScorer(head_state(model), self.table)
+
+
 def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int = None, impl: str = "device", table=None, threads: int = 8,
               seed: int = 0):
     """For every user of `users`, the k best items of `model`'s whole catalogue (a PMGT_NCF) that are not in the user's exclusion list
@@ -448,64 +524,24 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     check_ids("users", users, model.user_num, "recommend")
     indptr, excl = exclusion_csr(exclude, model.user_num, model.item_num)
     import torch
-    from .ncf import NCF
-    from .dcn import DCN
-    dcn = isinstance(model, DCN)
-    standalone = isinstance(model, NCF) or dcn                # the stand-alone classes: their own tables, no encoder, no sampler
+    dispatch = ModelDispatch(model, "recommend")
     if impl == "device":
-        if dcn:
-            check_dcn_covered(model.factor_num, model.deep_layers, model.cross_layers)
-        elif standalone:
-            check_ncf_model_covered(model.factor_num, 1 if model.model == "GMF" else model.num_layers, model.model, model.layer_norm_eps)
-        else:
-            check_head_covered(model.factor_num, model.num_layers, model.model)
+        dispatch.check_covered()
     if batch_users is not None and (not isinstance(batch_users, (int, np.integer)) or batch_users < 1):
         raise ValueError(f"recommend: batch_users = {batch_users!r} must be a positive integer or None")
     n_users, n_items = len(users), model.item_num
     batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
-    if dcn:
-        dev = model.output_layer.weight.device
-        if table is not None:
-            check_item_table(table, n_items, model.factor_num << model.deep_layers, dev, "recommend")
-    elif standalone:
-        dev = model.predict_layer.weight.device
-        if model.model == "GMF":
-            if table is not None:
-                raise ValueError("recommend: kind 'GMF' reads no item table")
-        else:
-            if table is None:
-                table = model.embed_item_MLP.weight.detach()
-            check_item_table(table, n_items, model.factor_num << (model.num_layers - 1), dev, "recommend")
-    else:
-        if table is None:
-            from .evaluation import encode_catalogue
-            was_training = model.training
-            model.eval()
-            try:
-                table = encode_catalogue(model, sampler, threads=threads, seed=seed)
-            finally:
-                model.train(was_training)
-        dev = model.engine.device
-        check_item_table(table, n_items, model.config.hidden_size, dev, "recommend")
-    was_training, set_mode = model.training, impl == "host" or standalone
+    dispatch.resolve_table(sampler, table, threads, seed)
+    dev = dispatch.dev
+    was_training, set_mode = model.training, dispatch.sets_mode(impl)
     if set_mode:
         model.eval()
     try:
-        if impl == "host" and dcn:
-            items, scores, flags = topk_host(dcn_host_scores(model, table, users), k, indptr, excl, users)
-        elif impl == "host":
-            # (kind GMF: model.head ignores the item rows; an empty table carries the item count and the device)
-            s = host_scores(model, torch.empty(n_items, 0, device=dev) if table is None else table, users)
-            items, scores, flags = topk_host(s, k, indptr, excl, users)
+        if impl == "host":
+            items, scores, flags = topk_host(dispatch.host_scores(users), k, indptr, excl, users)
         else:
             with torch.no_grad():
-                if dcn:
-                    from .dcn_train import _flat_of
-                    scorer = DcnScorer(_flat_of(model, dropout_ok=True), table, model.layer_norm_eps)
-                elif standalone:
-                    scorer = NcfModelScorer(model.state_dict(), table, model.model, model.layer_norm_eps)
-                else:
-                    scorer = NcfScorer(head_state(model), table)
+                scorer = dispatch.scorer()
                 picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
                 users_d = torch.from_numpy(users).to(dev)
                 out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
