@@ -242,6 +242,18 @@ int pmgt_op_adamw_scheduled(float* p, const float* g, float* m, float* v, const 
 int pmgt_op_adamw_guarded(float* p, const float* g, float* m, float* v, const uint8_t* decay, int64_t n, float lr, float wd, float b1,
                           float b2, float eps, float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
                           const pmgt_step_guard* guard, void* stream);
+/* global-norm clip (max_norm <= 0: off) + SGD over a flat fp32 buffer: torch.optim.SGD without momentum, with COUPLED weight decay where the
+ * decay byte is 1, after clip_grad_norm_ and under a LambdaLR stepped per optimizer step (the reference's --optim sgd).  Three launches: the
+ * norm partials of pmgt_op_adamw, the prepare lane of pmgt_op_adamw_guarded (so clip, lr_t = lr * lambda(*step), the guard's decision, its
+ * counters and its log row are that entry's, bit for bit; lr_t is pmgt_op_lr_schedule's value), one update.  sched NULL: constant rate;
+ * guard NULL: unguarded.  scal [8]: [0] clip, [1] lr_t, [2] 1, [3] pre-clip norm, [4] lr_t, [5] skipped flag (guarded only), [6..7]
+ * untouched.  An applied step increments *step; a skipped one leaves *step and every byte of p alone, writes [0] = 0, [3] = the non-finite
+ * norm, [4] = the rate it would have used, and leaves [1] and [2] unwritten.  Per element, in fp32 with every product and sum rounded (no
+ * FMA): gc = g clip; d = decay ? gc + wd p : gc; p = p - lr_t d.  p and g need 4-byte alignment only; n == 0 runs the prepare lane alone.
+ * -2 before any launch: a NULL p, g, decay, step, scal or part; n < 0; lr, wd or max_norm not finite; what pmgt_op_adamw_guarded refuses
+ * of a schedule or guard that is given. */
+int pmgt_op_sgd(float* p, const float* g, const uint8_t* decay, int64_t n, float lr, float wd, float max_norm, int64_t* step, float* scal,
+                float* part, const pmgt_lr_schedule* sched, const pmgt_step_guard* guard, void* stream);
 /* Global-norm clip + AdamW over up to PMGT_ADAM_MAX_SEGMENTS disjoint flat fp32 buffers AS ONE OPTIMIZER: the norm is taken over all
  * segments (the partials of the plain step's own norm kernel per segment, summed in fp64 by the prepare lane), there is one clip
  * coefficient, one increment of *step and one pair of bias corrections.  Per segment both the step size and the decay rate are multiplied

@@ -190,7 +190,7 @@ OPS_SYMBOLS = [
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
     "pmgt_op_adamw_guarded", "pmgt_op_eval_append_scores", "pmgt_op_eval_small_max",
     "pmgt_op_linear_rows", "pmgt_op_layernorm_bwd_rows", "pmgt_op_gemm_tn_bias_rows",
-    "pmgt_op_adamw_segments", "pmgt_op_cls_gather", "pmgt_op_cls_scatter",
+    "pmgt_op_adamw_segments", "pmgt_op_cls_gather", "pmgt_op_cls_scatter", "pmgt_op_sgd",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -311,6 +311,7 @@ def hip():
     L.pmgt_op_adamw_scheduled.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), vp]
     L.pmgt_op_adamw_guarded.argtypes = [vp, vp, vp, vp, vp, i64, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), C.POINTER(StepGuardC), vp]
     L.pmgt_op_lr_schedule.argtypes = [C.POINTER(LrScheduleC), f, i64, i, vp, vp]
+    L.pmgt_op_sgd.argtypes = [vp, vp, vp, i64, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC), C.POINTER(StepGuardC), vp]
     L.pmgt_op_mirror.argtypes = [i, vp, vp, C.POINTER(MirrorDescC), i, i, vp]
     L.pmgt_op_nfr_generate.argtypes = [vp, i, i, i, f, f, vp, vp, vp, vp]
     L.pmgt_op_build_need_rows.argtypes = [i, i, i, vp, vp, vp, vp, vp, i64, vp]

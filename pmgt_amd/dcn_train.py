@@ -22,7 +22,7 @@ from ._lib import DCN_MAX_PAIRS, DCN_TENSORS, DcnDropoutC, DcnHeadC  # noqa: F40
 from .dcn_head import (ITEM_KEY, check_dcn_covered, check_dcn_dropout, check_dcn_p, check_dcn_pairs, dcn_dropout_masks, dcn_layout, dcn_layout_slots,  # noqa: F401
                        dcn_per_layer, decays)
 from .pair_train import (PairGrad, PairTrainer, bce_with_logits_host, check_ids, check_seed, fit_pairs, ng_sample,  # noqa: F401
-                         normalize_item_table)
+                         normalize_item_table, pair_trainer_options)
 
 
 def _model_dims(model, dropout_ok: bool = False):
@@ -100,13 +100,15 @@ class DcnTrainer(PairTrainer):
     step() is then a TRAINING-mode step whatever model.training says (pmgt_dcn_train_grad_dropout); validation, evaluate_ctr and
     grad_fn.forward stay eval-mode.  The masks come from the project's counter-based RNG over `trainer.rng`, an int64 [2] device tensor
     {seed, step}, and `step_count` is a view of rng[1:2]: the pmgt_op_adamw call that ends every step advances the mask stream, so eager
-    and replayed steps draw fresh masks with no host write.  Still five launches.  Without a seed a model with dropout is refused."""
+    and replayed steps draw fresh masks with no host write.  Still five launches.  Without a seed a model with dropout is refused.
+    optim, scheduler_type, num_warmup_steps, num_training_steps, nonfinite, step_log, max_skipped_in_a_row: PairTrainer's."""
 
     who, max_pairs = "dcn", DCN_MAX_PAIRS
     layouts_differ = "the state was saved for a model of another shape or LayerNorm setting (the layouts differ)"
 
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = None,
-                 item_init=None, dropout_seed: int = None):
+                 item_init=None, dropout_seed: int = None, optim: str = "adamw", scheduler_type: str = None,
+                 num_warmup_steps: int = None, num_training_steps: int = None, nonfinite: str = None, step_log: int = 0, max_skipped_in_a_row: int = 25):
         import torch
         if dropout_seed is not None:
             check_seed(dropout_seed, "dcn")
@@ -119,7 +121,9 @@ class DcnTrainer(PairTrainer):
         if item_init is not None and (not isinstance(item_init, torch.Tensor) or item_init.dtype != torch.float32
                                       or tuple(item_init.shape) != (model.item_num, E)):
             raise ValueError(f"dcn: item_init must be an fp32 tensor [{model.item_num}, {E}]")
-        super().__init__(model, dev, *dcn_layout(*dims), lr, weight_decay, betas, eps, max_grad_norm, dropout_seed)
+        super().__init__(model, dev, *dcn_layout(*dims), lr, weight_decay, betas, eps, max_grad_norm, dropout_seed,
+                         optim=optim, scheduler_type=scheduler_type, num_warmup_steps=num_warmup_steps,
+                         num_training_steps=num_training_steps, nonfinite=nonfinite, step_log=step_log, max_skipped_in_a_row=max_skipped_in_a_row)
         named = dict(model.named_parameters())
         self._adopt(lambda key: item_init if key == ITEM_KEY and item_init is not None else named[key], lambda key: True, decays)
         self.grad_fn = DcnGrad(*dims[:4], model.layer_norm_eps, model.user_num, model.item_num, self.params, self.grads,
@@ -202,7 +206,8 @@ def validation_seed(seed: int) -> int:
 def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, num_ng: int = 1, max_sample_items: int = 5, seed: int = 0,
             early_criterion: str = "auc", patience: int = 10, ckpt_dir: str = None, lr: float = 1e-3, weight_decay: float = 0.0,
             betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 5.0, eval_batch_size: int = 256, item_init=None, log=None,
-            dropout_seed: int = None):
+            dropout_seed: int = None, optim: str = "adamw", scheduler_type: str = None, scheduler_warmup: float = None, nonfinite: str = None,
+            step_log: int = 0, save_last: bool = False, resume_from=None):
     """Trains `model` (a dcn.DCN on a GPU) on the interaction list `train_pairs` [(user, item)], the reference's click-through fit: every
     epoch draws ng_sample(train_pairs, num_ng, seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's
     users, items and labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device
@@ -214,6 +219,9 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     given).  item_init: DcnTrainer's.  dropout_seed=<int> (DcnTrainer's): a model with emb_dropout / dropout > 0 is trained with them, the
     masks a pure function of the seed and the count of steps taken; validation stays in eval mode and never drops.  Without it such a
     model is refused.
+    optim, scheduler_type / scheduler_warmup (a ratio of the run's steps: pair_schedule_steps), nonfinite, step_log: PairTrainer's options,
+    the reference's --optim, --scheduler-type / --scheduler-warmup and --mp-enabled; save_last, resume_from: fit_pairs' (a preempted run
+    continues bit for bit from ckpt_dir/last.ckpt).
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), auc, loss, best (whether it improved)."""
     if early_criterion not in ("auc", "loss"):
         raise ValueError(f"early_criterion={early_criterion!r}: expected 'auc' or 'loss'")
@@ -228,7 +236,9 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     check_ids("users", pairs[:, 0], model.user_num, "fit_dcn")
     check_ids("items", pairs[:, 1], model.item_num, "fit_dcn")
     trainer = DcnTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm, item_init=item_init,
-                         dropout_seed=dropout_seed)
+                         dropout_seed=dropout_seed,
+                         **pair_trainer_options("fit_dcn", len(pairs), num_ng, batch_size, max_epochs, optim, scheduler_type,
+                                                scheduler_warmup, nonfinite, step_log))
 
     def validate(epoch: int) -> dict:
         try:
@@ -240,4 +250,5 @@ def fit_dcn(model, train_pairs, valid_pairs, batch_size: int, max_epochs: int, n
     def checkpoint(epoch: int, row: dict) -> dict:
         return {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "metrics": dict(row)}
 
-    return fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log)
+    return fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log,
+                     save_last=save_last, resume_from=resume_from)

@@ -256,8 +256,10 @@ class PmgtNcfTrainer(PairTrainer):
         return [self.engine.params[lo:hi] for lo, hi in self.segments]
 
     def state_dict(self) -> dict:
-        """PairTrainer's state of the head plus "encoder": the ranges, their parameters and moments, and engine.rng_state."""
+        """PairTrainer's state of the head plus "encoder": the ranges, their parameters and moments, and engine.rng_state.  This trainer
+        takes none of PairTrainer's optimizer options, so their keys ("optim", "schedule") are left out: the state keeps the format it had."""
         sd = super().state_dict()
+        del sd["optim"], sd["schedule"]
         sd["encoder"] = {"segments": list(self.segments), "params": [p.detach().clone() for p in self.encoder_params()],
                          "exp_avg": [m.clone() for m in self.enc_exp_avg], "exp_avg_sq": [v.clone() for v in self.enc_exp_avg_sq],
                          "rng_state": self.engine.rng_state.clone(), "dtype": self.engine.dtype_name}

@@ -18,7 +18,7 @@ from . import _lib
 from ._lib import NCF_MODEL_KINDS, NCF_TRAIN_MAX_PAIRS, NcfDropoutC, NcfModelC
 from .ncf_head import LAYER_DROPOUTS, check_item_table
 from .ncf_model import ITEM_MLP, check_ncf_model_covered, ncf_model_layout, ncf_model_layout_slots, reads_mlp
-from .pair_train import PairGrad, PairTrainer, check_dropout_p, check_pairs, check_seed, fit_pairs, per_layer
+from .pair_train import PairGrad, PairTrainer, check_dropout_p, check_pairs, check_seed, fit_pairs, pair_trainer_options, per_layer
 
 
 def decays(key: str) -> bool:
@@ -90,13 +90,15 @@ class NcfModelTrainer(PairTrainer):
     or "LayerNorm.weight" (get_optimizer's rule: under this class's names the LayerNorm gammas MLP_layers.{4i+2}.weight DO decay).
     max_grad_norm None or 0: no clipping.  dropout_seed=<int>: the model is trained WITH ITS DROPOUT (emb_dropout on the concatenated
     input and on the GMF product, each layer's Dropout behind its Linear and before its LayerNorm), NcfHeadTrainer's mask stream; without
-    a seed a model with dropout is refused.  step, capture / replay and the state are PairTrainer's."""
+    a seed a model with dropout is refused.  step, capture / replay and the state are PairTrainer's, and so are optim, scheduler_type,
+    num_warmup_steps, num_training_steps, nonfinite, step_log and max_skipped_in_a_row."""
 
     who, max_pairs = "ncf_model", NCF_TRAIN_MAX_PAIRS
     layouts_differ = "the state was saved for another model, or with the items frozen / trained the other way (the layouts differ)"
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = None,
-                 freeze_items: bool = False, dropout_seed: int = None):
+                 freeze_items: bool = False, dropout_seed: int = None, optim: str = "adamw", scheduler_type: str = None,
+                 num_warmup_steps: int = None, num_training_steps: int = None, nonfinite: str = None, step_log: int = 0, max_skipped_in_a_row: int = 25):
         p_emb, p_layer = model_dropout(model)
         if dropout_seed is None and (p_emb != 0 or any(p != 0 for p in p_layer)):
             raise ValueError("ncf_model: dropout in the model is not covered without dropout_seed (pass dropout_seed=<int> to train with "
@@ -113,7 +115,9 @@ class NcfModelTrainer(PairTrainer):
         mlp = reads_mlp(model.model)
         self.train_items = mlp and not freeze_items
         dims = (model.factor_num, model.num_layers, model.model, model.use_layer_norm, model.user_num, model.item_num)
-        super().__init__(model, dev, *ncf_model_layout(*dims, self.train_items), lr, weight_decay, betas, eps, max_grad_norm, dropout_seed)
+        super().__init__(model, dev, *ncf_model_layout(*dims, self.train_items), lr, weight_decay, betas, eps, max_grad_norm, dropout_seed,
+                         optim=optim, scheduler_type=scheduler_type, num_warmup_steps=num_warmup_steps,
+                         num_training_steps=num_training_steps, nonfinite=nonfinite, step_log=step_log, max_skipped_in_a_row=max_skipped_in_a_row)
         named = dict(model.named_parameters())
         self._adopt(lambda key: named[key], lambda key: True, decays)
         self.table = self.views(self.params)[ITEM_MLP] if self.train_items else model.embed_item_MLP.weight.detach().clone().contiguous()
@@ -125,7 +129,8 @@ class NcfModelTrainer(PairTrainer):
 def fit_ncf_model(model, train_pairs, valid, batch_size: int, max_epochs: int, num_ng: int = 4, seed: int = 0, early_criterion: str = "n20",
                   patience: int = 10, ckpt_dir: str = None, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                   max_grad_norm: float = 5.0, batch_users: int = 256, log=None, freeze_items: bool = False, dropout_seed: int = None,
-                  item_init=None):
+                  item_init=None, optim: str = "adamw", scheduler_type: str = None, scheduler_warmup: float = None, nonfinite: str = None,
+                  step_log: int = 0, save_last: bool = False, resume_from=None):
     """Trains `model` (an ncf.NCF on a GPU) on the interaction list `train_pairs` [(user, item)], fit_ncf's loop: every epoch draws
     ng_sample(seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); validation ranks `valid` = (users [U], candidates
     [U, C], labels [U, C], counts [U]) with rank_users + RankingMetrics on trainer.table -> n10, n20, r10, r20, loss; early_criterion:
@@ -134,6 +139,9 @@ def fit_ncf_model(model, train_pairs, valid, batch_size: int, max_epochs: int, n
     loads.  item_init [item_num, d]: exported item embeddings copied into embed_item_MLP first (--item-init-emb-path); refused unless the
     kind is MLP or NeuMF-end, as in the reference's check_args.  freeze_items, dropout_seed: NcfModelTrainer's.  A trained GMF and a
     trained MLP model then construct a NeuMF-pre: NCF(..., model="NeuMF-pre", GMF_model=gmf, MLP_model=mlp).
+    optim, scheduler_type / scheduler_warmup (a ratio of the run's steps: pair_schedule_steps), nonfinite, step_log: PairTrainer's options,
+    the reference's --optim, --scheduler-type / --scheduler-warmup and --mp-enabled; save_last, resume_from: fit_pairs' (a preempted run
+    continues bit for bit from ckpt_dir/last.ckpt).
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
     import torch
     from .evaluation import check_candidates, rank_users
@@ -155,7 +163,9 @@ def fit_ncf_model(model, train_pairs, valid, batch_size: int, max_epochs: int, n
         with torch.no_grad():
             model.embed_item_MLP.weight.copy_(item_init)
     trainer = NcfModelTrainer(model, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                              freeze_items=freeze_items, dropout_seed=dropout_seed)
+                              freeze_items=freeze_items, dropout_seed=dropout_seed,
+                              **pair_trainer_options("fit_ncf_model", len(pairs), num_ng, batch_size, max_epochs, optim, scheduler_type,
+                                                     scheduler_warmup, nonfinite, step_log))
     dev = trainer.params.device
     on_dev = [torch.from_numpy(a).to(dev) for a in valid]
     metrics = RankingMetrics(dev, len(valid[0]), (10, 20))
@@ -174,4 +184,5 @@ def fit_ncf_model(model, train_pairs, valid, batch_size: int, max_epochs: int, n
     def checkpoint(epoch: int, row: dict) -> dict:
         return {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "metrics": dict(row)}
 
-    return fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log)
+    return fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log,
+                     save_last=save_last, resume_from=resume_from)

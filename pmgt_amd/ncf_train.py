@@ -23,7 +23,7 @@ from ._lib import NCF_TRAIN_MAX_PAIRS, NCF_TRAIN_TENSORS, NcfDropoutC, NcfTrainC
 from .ncf_head import (HEAD_PREFIXES, LAYER_DROPOUTS, TABLE_KEY, check_head_covered, check_item_table, head_layout, head_shape,  # noqa: F401
                        head_state, layout_slots, ncf_dropout_keep, ncf_dropout_masks, ncf_head_grad_host, table_layout)
 from .pair_train import (PairGrad, PairTrainer, check_dropout_p, check_pairs, check_seed, fit_pairs, ng_sample, normalize_item_table,  # noqa: F401
-                         per_layer)
+                         pair_trainer_options, per_layer)
 
 
 class NcfHeadGrad(PairGrad):
@@ -86,13 +86,15 @@ class NcfHeadTrainer(PairTrainer):
     whatever model.training says -- model.head, rank_users and recommend stay what the model's mode makes them, eval for validation --, the
     masks come from the project's counter-based RNG over `trainer.rng`, an int64 [2] device tensor {seed, step}, and `step_count` is a view
     of rng[1:2]: the pmgt_op_adamw call that ends every step advances the mask stream, so eager and replayed steps draw fresh masks with no
-    host write.  Still five launches.  Without a seed a model with dropout is refused."""
+    host write.  Still five launches.  Without a seed a model with dropout is refused.
+    optim, scheduler_type, num_warmup_steps, num_training_steps, nonfinite, step_log, max_skipped_in_a_row: PairTrainer's."""
 
     who, max_pairs = "ncf_train", NCF_TRAIN_MAX_PAIRS
     layouts_differ = "the state was saved for another head, or with the table frozen / trained the other way (the layouts differ)"
 
     def __init__(self, model, table, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: float = None, train_table: bool = False, dropout_seed: int = None):
+                 max_grad_norm: float = None, train_table: bool = False, dropout_seed: int = None, optim: str = "adamw", scheduler_type: str = None,
+                 num_warmup_steps: int = None, num_training_steps: int = None, nonfinite: str = None, step_log: int = 0, max_skipped_in_a_row: int = 25):
         p_emb, p_layer = model.emb_dropout.p, [layer.dropout.p for layer in model.mlp_layers]
         if dropout_seed is None and (p_emb != 0 or any(p != 0 for p in p_layer)):
             raise ValueError("ncf_train: dropout in the head is not covered without dropout_seed (pass dropout_seed=<int> to train with "
@@ -108,7 +110,8 @@ class NcfHeadTrainer(PairTrainer):
         self.train_table = bool(train_table)
         dims = (model.factor_num, model.num_layers, model.model, model.user_num, model.item_num)
         super().__init__(model, dev, *(table_layout(*dims) if self.train_table else head_layout(*dims)), lr, weight_decay, betas, eps,
-                         max_grad_norm, dropout_seed)
+                         max_grad_norm, dropout_seed, optim=optim, scheduler_type=scheduler_type, num_warmup_steps=num_warmup_steps,
+                         num_training_steps=num_training_steps, nonfinite=nonfinite, step_log=step_log, max_skipped_in_a_row=max_skipped_in_a_row)
         named = dict(model.named_parameters())
         self._adopt(lambda key: table if key == TABLE_KEY else named[key], lambda key: key != TABLE_KEY, lambda key: not key.endswith(".bias"))
         head_count = head_layout(*dims)[1]                  # (the whole buffer when the table is frozen)
@@ -120,7 +123,9 @@ class NcfHeadTrainer(PairTrainer):
 
 def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, num_ng: int = 1, seed: int = 0, early_criterion: str = "n20",
             patience: int = 10, ckpt_dir: str = None, lr: float = 1e-4, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-            max_grad_norm: float = 5.0, batch_users: int = 256, log=None, train_table: bool = False, dropout_seed: int = None):
+            max_grad_norm: float = 5.0, batch_users: int = 256, log=None, train_table: bool = False, dropout_seed: int = None,
+            optim: str = "adamw", scheduler_type: str = None, scheduler_warmup: float = None, nonfinite: str = None,
+            step_log: int = 0, save_last: bool = False, resume_from=None):
     """Trains the head of `model` on the interaction list `train_pairs` [(user, item)] over the frozen `table`, the reference's downstream
     fit: every epoch draws ng_sample(seed + epoch) and visits it in the order fit_loop.epoch_order(seed, epoch); the epoch's users, items and
     labels are uploaded once and the steps run on slices (the last batch may be short), their losses stay on the device and are read once
@@ -133,6 +138,9 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
     `table` IS OVERWRITTEN -- recommend(table=table) and evaluate_ranking(table=table) then read the trained rows.
     dropout_seed=<int> (NcfHeadTrainer's): a model with emb_dropout / dropout > 0 is trained with them, the masks a pure function of the
     seed and the count of steps taken; validation stays in eval mode and never drops.  Without it such a model is refused.
+    optim, scheduler_type / scheduler_warmup (a ratio of the run's steps: pair_schedule_steps), nonfinite, step_log: PairTrainer's options,
+    the reference's --optim, --scheduler-type / --scheduler-warmup and --mp-enabled; save_last, resume_from: fit_pairs' (a preempted run
+    continues bit for bit from ckpt_dir/last.ckpt).
     -> the history, one dict per epoch: epoch, train_loss (mean over the steps), the five metrics, best (whether it improved)."""
     import torch
     from .evaluation import check_candidates, rank_users
@@ -145,7 +153,9 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
     check_pairs(pairs[:, 0], pairs[:, 1], np.ones(len(pairs), np.float32), model.user_num, model.item_num, max_pairs=1 << 40)
     valid = check_candidates(model, *valid, "fit_ncf: validation")
     trainer = NcfHeadTrainer(model, table, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                             train_table=train_table, dropout_seed=dropout_seed)
+                             train_table=train_table, dropout_seed=dropout_seed,
+                             **pair_trainer_options("fit_ncf", len(pairs), num_ng, batch_size, max_epochs, optim, scheduler_type,
+                                                    scheduler_warmup, nonfinite, step_log))
     dev = trainer.params.device
     on_dev = [torch.from_numpy(a).to(dev) for a in valid]
     metrics = RankingMetrics(dev, len(valid[0]), (10, 20))
@@ -168,7 +178,8 @@ def fit_ncf(model, table, train_pairs, valid, batch_size: int, max_epochs: int, 
             ckpt[TABLE_KEY] = trainer.table.detach().cpu()
         return ckpt
 
-    history = fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log)
+    history = fit_pairs(trainer, pairs, batch_size, max_epochs, num_ng, seed, early_criterion, patience, ckpt_dir, validate, checkpoint, log,
+                        save_last=save_last, resume_from=resume_from)
     if train_table:
         with torch.no_grad():
             table.copy_(trainer.table)                       # (the best epoch's: fit_pairs restored head and table, one buffer)

@@ -14,6 +14,8 @@
 // (torch.nn.utils.clip_grad_norm_ on fp32 gradients reports the same Inf norm for those).
 // Kept out of csrc/: the plain step and every kernel bench.py measures (and fingerprints there) stay byte for byte what they were.  The
 // gradient-norm partials are csrc/optim.hip's own kernel, so every form is the same three launches, no sync, no allocation.
+// The checked schedule and guard and the launch of the prepare lane are declared in optimizer_step.h: sgd_step.hip (pmgt_op_sgd) prepares its
+// step with this file's lane, so its clip, rate and guard are these kernels' bits.
 // Segments (pmgt_op_adamw_segments): up to PMGT_ADAM_MAX_SEGMENTS disjoint flat buffers clipped by ONE global norm and stepped by one counter,
 // each at a rate of its own -- an encoder fine-tuned through a head, two buffers, the encoder's learning rate its own.  One norm launch and
 // one update launch per segment around one prepare launch.
@@ -21,24 +23,11 @@
 
 #include "../../include/pmgt_ops.h"
 #include "../csrc/optim.h"
+#include "optimizer_step.h"
 
 namespace pmgt {
 
 __global__ void sqnorm_part_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part);      // csrc/optim.hip
-
-struct LrSchedule {
-    int type;                  // PMGT_LR_*
-    int64_t warmup, total;     // num_warmup_steps (W), num_training_steps (T)
-};
-
-struct StepGuard {
-    int64_t* counters;      // [4]: attempts, skipped, skipped in a row, reserved
-    float* log_f;           // [log_rows][PMGT_STEP_LOG_FLOATS] or NULL
-    int64_t* log_i;         // [log_rows][2] or NULL
-    int64_t log_rows;
-    const float* loss;      // device scalar or NULL
-    int skip_nonfinite;
-};
 
 // lr * lambda(s): LambdaLR's rate after s completed optimizer steps
 static __device__ double scheduled_lr(const LrSchedule sc, double lr, int64_t s) {
@@ -196,17 +185,22 @@ __global__ __launch_bounds__(256) void lr_schedule_kernel(const LrSchedule sched
     if (i < n) out[i] = (float)scheduled_lr(sched, (double)lr, first_step + i);
 }
 
+int launch_step_prepare(const float* part, int nparts, float max_norm, float lr, float b1, float b2, int64_t* step, float* scal,
+                        const LrSchedule& sched, const StepGuard* gd, hipStream_t st) {
+    const auto prepare = gd ? adam_prepare_step_kernel<true> : adam_prepare_step_kernel<false>;
+    hipLaunchKernelGGL(prepare, dim3(1), dim3(64), 0, st, part, nparts, max_norm, lr, b1, b2, step, scal, sched, gd ? *gd : StepGuard{});
+    PMGT_LAUNCH_OK();
+    return 0;
+}
+
 // adamw_step of csrc/optim.hip: norm partials -> prepare -> AdamW, three launches; gd = NULL: the scheduled form, else the guarded one
 static int adamw_step_derived(const AdamArgs& a, const LrSchedule& sched, const StepGuard* gd, hipStream_t st) {
     if (a.n <= 0) return 0;
     const int nparts = (int)std::min<int64_t>(1024, cdiv64(a.n, 1024));
-    const auto prepare = gd ? adam_prepare_step_kernel<true> : adam_prepare_step_kernel<false>;
     const auto update = gd ? adamw_step_kernel<true> : adamw_step_kernel<false>;
     hipLaunchKernelGGL(sqnorm_part_kernel, dim3(nparts), dim3(256), 0, st, a.g, a.n, a.part);
     PMGT_LAUNCH_OK();
-    hipLaunchKernelGGL(prepare, dim3(1), dim3(64), 0, st, a.part, nparts, a.max_norm, a.lr, a.b1, a.b2, a.step, a.scal, sched,
-                       gd ? *gd : StepGuard{});
-    PMGT_LAUNCH_OK();
+    if (int rc = launch_step_prepare(a.part, nparts, a.max_norm, a.lr, a.b1, a.b2, a.step, a.scal, sched, gd, st)) return rc;
     hipLaunchKernelGGL(update, dim3((unsigned)cdiv64(cdiv64(a.n, 4), 256)), dim3(256), 0, st, a.p, a.g, a.m, a.v, a.decay, a.n, a.wd, a.b1, a.b2,
                        a.eps, a.scal);
     PMGT_LAUNCH_OK();
@@ -214,7 +208,7 @@ static int adamw_step_derived(const AdamArgs& a, const LrSchedule& sched, const 
 }
 
 // null_is_constant: a NULL schedule is the constant rate (lambda = 1, so lr_t = (double)lr and the step is pmgt_optimizer_step's bit for bit)
-static int schedule_from(const pmgt_lr_schedule* in, bool null_is_constant, float lr, const char* who, LrSchedule* out) {
+int schedule_from(const pmgt_lr_schedule* in, bool null_is_constant, float lr, const char* who, LrSchedule* out) {
     if (in == nullptr && null_is_constant) {
         *out = LrSchedule{PMGT_LR_CONSTANT, 0, 0};
         return 0;
@@ -232,7 +226,7 @@ static int schedule_from(const pmgt_lr_schedule* in, bool null_is_constant, floa
     return 0;
 }
 
-static int guard_from(const pmgt_step_guard* in, const char* who, StepGuard* out) {
+int guard_from(const pmgt_step_guard* in, const char* who, StepGuard* out) {
     PMGT_CHECK(in != nullptr, -2, "%s: NULL guard", who);
     PMGT_CHECK(in->counters != nullptr, -2, "%s: NULL guard counters", who);
     PMGT_CHECK(in->log_rows >= 0, -2, "%s: log_rows = %lld is negative", who, (long long)in->log_rows);
