@@ -274,6 +274,29 @@ typedef struct pmgt_adam_segment {
 } pmgt_adam_segment;
 int pmgt_op_adamw_segments(const pmgt_adam_segment* segments, int count, float lr, float wd, float b1, float b2, float eps, float max_norm,
                            int64_t* step, float* scal, float* part, void* stream);
+/* pmgt_op_adamw_segments with the options of the single-buffer entries: the same segments stepped as ONE optimizer (one norm over all of
+ * them, one clip coefficient, one *step, a rate per segment), by AdamW or SGD, optionally under a learning-rate schedule and behind the
+ * step guard.  sched NULL: constant rate; guard NULL: unguarded.  PMGT_OPTIM_ADAMW with neither is pmgt_op_adamw_segments bit for bit
+ * (p, m, v, step, scal[0..4]); with ONE segment at lr_scale 1, PMGT_OPTIM_ADAMW is pmgt_op_adamw_guarded and PMGT_OPTIM_SGD is pmgt_op_sgd
+ * bit for bit, counters and log row included.
+ * The prepare lane is the single-buffer entries' own code over the partials of every segment (a lane adds segment 0's, then segment 1's,
+ * ..., in fp64): lr_t = lr * lambda(*step) is pmgt_op_lr_schedule's value, and scal [8] has the layout pmgt_op_adamw_guarded and pmgt_op_sgd
+ * document ([0] clip, [1] lr_t / bc1, [2] 1 / sqrt(bc2), [3] pre-clip joint norm, [4] lr_t, [5] skipped flag (guarded only), [6..7]
+ * untouched; SGD runs the lane with beta1 = beta2 = 0, so [1] = lr_t and [2] = 1).  An applied step increments *step; a skipped one leaves
+ * *step and every byte of every segment's p, m and v alone, writes [0] = 0, [3] = the non-finite norm, [4] = the rate it would have used.
+ * Per segment: AdamW as pmgt_op_adamw_segments states it, with the step size scal[1] * lr_scale and the decay rate the fp32 product
+ * scal[4] * lr_scale; SGD as pmgt_op_sgd states it at lr_t = scal[4] * lr_scale (one rounded fp32 product), m and v may be NULL and are
+ * never read, p and g need 4-byte alignment only (a range of a larger buffer takes the 16-byte body when p and g share their alignment).
+ * lr_scale = 0: AdamW leaves p untouched while m and v move; SGD with finite gradients leaves p untouched.
+ * part [count * 1024] floats of scratch.  An empty segment (n = 0) is skipped.  Launches: one norm launch and one update launch per
+ * non-empty segment, one prepare launch; no sync, no allocation, no atomics, capturable.
+ * Refused (-2) before any launch, nothing written: what pmgt_op_adamw_segments refuses (under SGD a NULL m or v is accepted); an optim that
+ * is neither value; lr, wd or max_norm not finite; what pmgt_op_adamw_guarded refuses of a schedule or guard that is given. */
+#define PMGT_OPTIM_ADAMW 0
+#define PMGT_OPTIM_SGD   1
+int pmgt_op_step_segments(const pmgt_adam_segment* segments, int count, int optim, float lr, float wd, float b1, float b2, float eps,
+                          float max_norm, int64_t* step, float* scal, float* part, const pmgt_lr_schedule* sched,
+                          const pmgt_step_guard* guard, void* stream);
 /* The two-way glue between an encoder output [n][S][d] in the engine dtype (PMGT_DTYPE_F32 or PMGT_DTYPE_BF16) and the fp32 rows [n][d] a head
  * reads and differentiates.  Gather: x[p][:] = (float) last_hidden[p][0][:], the CLS state of sequence p.  Scatter: d_last [n][S][d] is
  * written WHOLE -- token 0 of sequence p gets d_item[p] (fp32 -> bf16 round-to-nearest-even), every other element +0.0.  16-byte accesses

@@ -118,6 +118,7 @@ class AdamSegmentC(C.Structure):
 
 
 ADAM_MAX_SEGMENTS = 8      # PMGT_ADAM_MAX_SEGMENTS
+OPTIMS = ("adamw", "sgd")      # PMGT_OPTIM_* in order: the `optim` of pmgt_op_step_segments
 
 
 class DcnHeadC(C.Structure):
@@ -190,7 +191,7 @@ OPS_SYMBOLS = [
     "pmgt_op_adamw_scheduled", "pmgt_op_lr_schedule", "pmgt_op_nfr_generate", "pmgt_op_build_need_rows", "pmgt_op_dropout_keep",
     "pmgt_op_adamw_guarded", "pmgt_op_eval_append_scores", "pmgt_op_eval_small_max",
     "pmgt_op_linear_rows", "pmgt_op_layernorm_bwd_rows", "pmgt_op_gemm_tn_bias_rows",
-    "pmgt_op_adamw_segments", "pmgt_op_cls_gather", "pmgt_op_cls_scatter", "pmgt_op_sgd",
+    "pmgt_op_adamw_segments", "pmgt_op_cls_gather", "pmgt_op_cls_scatter", "pmgt_op_sgd", "pmgt_op_step_segments",
 ]
 # path options: pmgt_engine_set_option keys -> bit in the `path_opts` argument of the pmgt_op_* entries (include/pmgt_ops.h)
 OPT = {k: 1 << i for i, k in enumerate((
@@ -357,6 +358,8 @@ def hip():
     L.pmgt_ncf_model_train_grad.argtypes = [C.POINTER(NcfModelC), vp, vp, vp, i64, vp, vp, C.POINTER(NcfDropoutC), vp, i64, vp]      # (... logits, drop or NULL, workspace ...)
     L.pmgt_ncf_model_score.argtypes = [C.POINTER(NcfModelHeadC), vp, vp, vp, i64, i64, vp, i64, vp]
     L.pmgt_op_adamw_segments.argtypes = [C.POINTER(AdamSegmentC), i, f, f, f, f, f, f, vp, vp, vp, vp]
+    L.pmgt_op_step_segments.argtypes = [C.POINTER(AdamSegmentC), i, i, f, f, f, f, f, f, vp, vp, vp, C.POINTER(LrScheduleC),
+                                        C.POINTER(StepGuardC), vp]      # (segments, count, optim = index in OPTIMS, ...)
     L.pmgt_op_cls_gather.argtypes = [i, vp, i64, i, i, vp, vp]
     L.pmgt_op_cls_scatter.argtypes = [i, vp, i64, i, i, vp, vp]
     L.pmgt_dcn_layout.restype = i64

@@ -15,7 +15,8 @@
 // Kept out of csrc/: the plain step and every kernel bench.py measures (and fingerprints there) stay byte for byte what they were.  The
 // gradient-norm partials are csrc/optim.hip's own kernel, so every form is the same three launches, no sync, no allocation.
 // The checked schedule and guard and the launch of the prepare lane are declared in optimizer_step.h: sgd_step.hip (pmgt_op_sgd) prepares its
-// step with this file's lane, so its clip, rate and guard are these kernels' bits.
+// step with this file's lane, so its clip, rate and guard are these kernels' bits.  The schedule (scheduled_lr) and the lane's body
+// (prepare_step_lane) are device code of that header: segments_step.hip (pmgt_op_step_segments) runs the same lane over several segments.
 // Segments (pmgt_op_adamw_segments): up to PMGT_ADAM_MAX_SEGMENTS disjoint flat buffers clipped by ONE global norm and stepped by one counter,
 // each at a rate of its own -- an encoder fine-tuned through a head, two buffers, the encoder's learning rate its own.  One norm launch and
 // one update launch per segment around one prepare launch.
@@ -29,23 +30,8 @@ namespace pmgt {
 
 __global__ void sqnorm_part_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part);      // csrc/optim.hip
 
-// lr * lambda(s): LambdaLR's rate after s completed optimizer steps
-static __device__ double scheduled_lr(const LrSchedule sc, double lr, int64_t s) {
-    const double W = (double)sc.warmup, T = (double)sc.total, x = (double)s;
-    if (sc.type != PMGT_LR_CONSTANT && s < sc.warmup) return lr * (x / fmax(1.0, W));
-    const double q = (x - W) / fmax(1.0, T - W);
-    switch (sc.type) {
-        case PMGT_LR_LINEAR: return lr * fmax(0.0, (T - x) / fmax(1.0, T - W));
-        case PMGT_LR_COSINE: return lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * q)));                                  // half a cycle
-        case PMGT_LR_COSINE_WITH_RESTARTS: return q >= 1.0 ? 0.0 : lr * fmax(0.0, 0.5 * (1.0 + cos(M_PI * fmod(q, 1.0))));      // one cycle
-        case PMGT_LR_POLYNOMIAL: return lr * ((s > sc.total ? 1e-7 : (lr - 1e-7) * (1.0 - (x - W) / (T - W)) + 1e-7) / lr);    // power 1, lr_end 1e-7
-        default: return lr;                                                                                      // constant, constant_with_warmup
-    }
-}
-
-// adam_prepare_kernel of csrc/optim.hip with lr_t for lr: fp64, rounded once per slot.  Guarded adds the decision, the counters and the
-// log row; a skipped step leaves step[0], scal[1] and scal[2] alone (the bias corrections and the schedule count applied steps only) and
-// reports the rate it would have used.  The unguarded form neither reads nor writes scal[5..7], nor gd.
+// The prepare lane: one wave adds the norm partials in fp64; its first thread runs prepare_step_lane of optimizer_step.h (the clip, lr_t, the
+// bias corrections, the guard's decision, the counters and the log row).
 template <bool Guarded>
 __global__ __launch_bounds__(64) void adam_prepare_step_kernel(const float* __restrict__ part, int nparts, float max_norm, float lr, float b1,
                                                                float b2, int64_t* __restrict__ step, float* __restrict__ scal,
@@ -54,52 +40,7 @@ __global__ __launch_bounds__(64) void adam_prepare_step_kernel(const float* __re
     for (int i = threadIdx.x; i < nparts; i += 64) s += (double)part[i];
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (threadIdx.x != 0) return;
-    const double norm = sqrt(s);
-    bool bad = false, skip = false;
-    if constexpr (Guarded) {
-        bad = !isfinite(norm);
-        skip = bad && gd.skip_nonfinite != 0;
-    }
-    int64_t t = step[0];
-    double coef = 0.0, lr_t;
-    if (skip) {
-        lr_t = scheduled_lr(sched, (double)lr, t);
-        scal[0] = 0.f;
-    } else {
-        t += 1;
-        step[0] = t;
-        coef = 1.0;
-        if (max_norm > 0.f) coef = fmin((double)max_norm / (norm + 1e-6), 1.0);
-        const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-        lr_t = scheduled_lr(sched, (double)lr, t - 1);
-        scal[0] = (float)coef;
-        scal[1] = (float)(lr_t / bc1);
-        scal[2] = (float)(1.0 / sqrt(bc2));
-    }
-    scal[3] = (float)norm;
-    scal[4] = (float)lr_t;
-    if constexpr (Guarded) {
-        scal[5] = skip ? 1.f : 0.f;
-        const int64_t attempt = gd.counters[0];
-        gd.counters[0] = attempt + 1;
-        if (skip) {
-            gd.counters[1] += 1;
-            gd.counters[2] += 1;
-        } else {
-            gd.counters[2] = 0;
-        }
-        if (gd.log_rows > 0) {
-            const int64_t r = attempt % gd.log_rows;
-            float* f = gd.log_f + r * PMGT_STEP_LOG_FLOATS;
-            f[0] = gd.loss ? gd.loss[0] : __builtin_nanf("");
-            f[1] = (float)norm;
-            f[2] = (float)coef;
-            f[3] = (float)lr_t;
-            f[4] = skip ? 1.f : (bad ? 2.f : 0.f);
-            gd.log_i[r * 2 + 0] = attempt;
-            gd.log_i[r * 2 + 1] = t;
-        }
-    }
+    prepare_step_lane<Guarded>(s, max_norm, lr, b1, b2, step, scal, sched, gd);
 }
 
 // adamw_kernel of csrc/optim.hip, the same fp32 arithmetic in the same order, with the decay term's rate read from scal[4].  Guarded sits
@@ -129,11 +70,6 @@ __global__ __launch_bounds__(256) void adamw_step_kernel(float* __restrict__ p, 
 
 // ---- several flat buffers as ONE optimizer (pmgt_op_adamw_segments): the norm over all of them, one clip coefficient, one step counter, one
 // pair of bias corrections; per segment a rate of its own.  The partials of segment s are sqnorm_part_kernel's, at part + 1024 s.
-struct SegParts {
-    int count;
-    int nparts[PMGT_ADAM_MAX_SEGMENTS];
-};
-
 // adam_prepare_kernel of csrc/optim.hip over the partials of every segment: a lane adds its partials of segment 0, then of segment 1, ..., in
 // fp64 (ONE segment: that kernel's sum in that kernel's order, so the same bits); scal[4] = lr as the scheduled form leaves it
 __global__ __launch_bounds__(64) void adam_prepare_segments_kernel(const float* __restrict__ part, const SegParts sp, float max_norm, float lr,

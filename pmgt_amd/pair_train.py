@@ -376,13 +376,7 @@ class PairTrainer:
         loss, _ = self.grad_fn(users, items, labels, loss=loss, logits=self._logits(int(users.shape[0])))
         lib = self.grad_fn.lib
         tail = (self.step_count.data_ptr(), self._scal.data_ptr(), self._part.data_ptr())
-        sched = None if self._sched is None else C.byref(self._sched)
-        guard = None
-        if self._guard_state is not None:
-            rows, base = self.step_log_rows, self._guard_state.data_ptr()
-            gd = _lib.StepGuardC(base, base + 8 * (4 + 2 * rows) if rows else None, base + 8 * 4 if rows else None, rows, loss.data_ptr(),
-                                 1 if self.nonfinite == "skip" else 0)
-            guard = C.byref(gd)
+        sched, guard = self._step_options(loss)
         if self.optim == "sgd":
             _lib.check(lib.pmgt_op_sgd(self.params.data_ptr(), self.grads.data_ptr(), self.decay.data_ptr(), self.count, self.lr,
                                        self.weight_decay, self.max_grad_norm, *tail, sched, guard, _lib.stream()))
@@ -396,6 +390,16 @@ class PairTrainer:
         else:
             _lib.check(lib.pmgt_op_adamw(*adam, _lib.stream()))
         return loss
+
+    def _step_options(self, loss):
+        """(schedule, guard) as the optimizer entries take them, each a reference or None; the guard logs `loss`, the step's own."""
+        sched = None if self._sched is None else C.byref(self._sched)
+        if self._guard_state is None:
+            return sched, None
+        rows, base = self.step_log_rows, self._guard_state.data_ptr()
+        gd = _lib.StepGuardC(base, base + 8 * (4 + 2 * rows) if rows else None, base + 8 * 4 if rows else None, rows, loss.data_ptr(),
+                             1 if self.nonfinite == "skip" else 0)
+        return sched, C.byref(gd)
 
     def schedule(self):
         """(type, W, T) of the learning-rate schedule, or None."""
@@ -529,6 +533,46 @@ class PairTrainer:
 LAST_FORMAT = "pmgt_amd.fit_pairs"      # the "format" entry of a last.ckpt fit_pairs wrote
 
 
+# ---- what the epoch loops that write last.ckpt share (fit_pairs here, fit_pmgt_ncf of finetune.py) ---------------------------------------------
+def run_record(trainer, batch_size: int, num_ng: int, seed: int, early_criterion: str, patience: int, max_epochs: int) -> dict:
+    """The settings of a fit call that a resumed run must repeat: they fix the epoch order, the sampled pairs and the callbacks; with a
+    schedule, max_epochs too (it sets the schedule's length)."""
+    run = {"batch_size": int(batch_size), "num_ng": int(num_ng), "seed": int(seed), "early_criterion": early_criterion, "patience": int(patience)}
+    if trainer.schedule() is not None:
+        run["max_epochs"] = int(max_epochs)
+    return run
+
+
+def check_run_record(who: str, recorded: dict, run: dict) -> None:
+    """ValueError in the name of `who`, both values named, for the first setting of `run` that the checkpoint recorded differently."""
+    for k, v in run.items():
+        if recorded.get(k) != v:
+            raise ValueError(f"{who}(resume_from=...): the checkpoint was written with {k} = {recorded.get(k)!r}, this call has {v!r}: "
+                             "the epoch order, the sampled pairs and the schedule would not continue it")
+
+
+def load_last(who: str, path: str, dev, fmt: str) -> dict:
+    """The last.ckpt at `path` as plain data (torch.load(weights_only=True): tensors, dicts, lists, tuples, numbers, strings; no code is
+    unpickled); ValueError in the name of `who` for a file whose "format" is not `fmt`."""
+    import pickle
+    import torch
+    try:
+        ck = torch.load(path, map_location=dev, weights_only=True)
+    except pickle.UnpicklingError:
+        ck = None
+    if not isinstance(ck, dict) or ck.get("format") != fmt:
+        raise ValueError(f"{who}(resume_from=...): the checkpoint was not written by {who} (no epoch position in it)")
+    return ck
+
+
+def save_atomic(obj, path: str) -> None:
+    """torch.save to a temporary name beside `path`, then os.replace: a reader never sees half a file."""
+    import torch
+    tmp = path + ".tmp"
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
 def fit_pairs(trainer, pairs, batch_size: int, max_epochs: int, num_ng: int, seed: int, early_criterion: str, patience: int, ckpt_dir: str,
               validate, checkpoint, log=None, save_last: bool = False, resume_from=None) -> list:
     """The epoch loop of fit_ncf and fit_dcn over `trainer` (a PairTrainer) and the checked interaction list `pairs` int64 [P, 2]: every epoch
@@ -559,22 +603,11 @@ def fit_pairs(trainer, pairs, batch_size: int, max_epochs: int, num_ng: int, see
     if ckpt_dir:
         os.makedirs(ckpt_dir, exist_ok=True)
     last_path = os.path.join(ckpt_dir, "last.ckpt") if ckpt_dir else None
-    run = {"batch_size": int(batch_size), "num_ng": int(num_ng), "seed": int(seed), "early_criterion": early_criterion, "patience": int(patience)}
-    if trainer.schedule() is not None:
-        run["max_epochs"] = int(max_epochs)
+    run = run_record(trainer, batch_size, num_ng, seed, early_criterion, patience, max_epochs)
     best_params, history, first_epoch, stopped = None, [], 0, False
     if resume_from is not None:
-        import pickle
-        try:                                                 # (plain data -- tensors, dicts, lists, tuples, numbers, strings: no code is unpickled)
-            ck = torch.load(last_path if resume_from == "last" else resume_from, map_location=dev, weights_only=True)
-        except pickle.UnpicklingError:
-            ck = None
-        if not isinstance(ck, dict) or ck.get("format") != LAST_FORMAT:
-            raise ValueError("fit_pairs(resume_from=...): the checkpoint was not written by fit_pairs (no epoch position in it)")
-        for k, v in run.items():
-            if ck["run"].get(k) != v:
-                raise ValueError(f"fit_pairs(resume_from=...): the checkpoint was written with {k} = {ck['run'].get(k)!r}, this call has {v!r}: "
-                                 "the epoch order, the sampled pairs and the schedule would not continue it")
+        ck = load_last("fit_pairs", last_path if resume_from == "last" else resume_from, dev, LAST_FORMAT)
+        check_run_record("fit_pairs", ck["run"], run)
         trainer.load_state_dict(ck["trainer"])
         stopper.load_state_dict(ck["early_stopping"])
         keeper.load_state_dict(ck["best_checkpoint"])
@@ -607,11 +640,9 @@ def fit_pairs(trainer, pairs, batch_size: int, max_epochs: int, num_ng: int, see
             history.append(row)
             stopped = stopper.update(row[early_criterion], epoch)
             if save_last:
-                tmp = last_path + ".tmp"
-                torch.save({"format": LAST_FORMAT, "trainer": trainer.state_dict(), "epoch": epoch, "early_stopping": stopper.state_dict(),
-                            "best_checkpoint": keeper.state_dict(), "best_params": best_params, "history": history, "run": run,
-                            "stopped": stopped}, tmp)
-                os.replace(tmp, last_path)
+                save_atomic({"format": LAST_FORMAT, "trainer": trainer.state_dict(), "epoch": epoch, "early_stopping": stopper.state_dict(),
+                             "best_checkpoint": keeper.state_dict(), "best_params": best_params, "history": history, "run": run,
+                             "stopped": stopped}, last_path)
             if log is not None:
                 log(row)
             if stopped:

@@ -1,6 +1,6 @@
 """Learning-rate schedules of the reference's `--scheduler-type` / `--scheduler-warmup` (train.py:38-52): the multipliers of
 transformers 4.11.2 `optimization.py` (the version the reference pins) with the defaults `get_scheduler` leaves in place, as closed
-forms in Python.  The fused optimizer step evaluates the same forms on the device from its step counter (ops/optimizer_step.hip:
+forms in Python.  The fused optimizer step evaluates the same forms on the device from its step counter (ops/optimizer_step.h:
 scheduled_lr); this file is the host statement of them (`LambdaLR` for the Lightning-style path, expected values for the tests) and
 the one place the step counts are derived from the command-line arguments."""
 from __future__ import annotations
