@@ -406,6 +406,40 @@ int pmgt_rank_heldout_reduce(const int32_t* ranks, const int64_t* held_indptr, c
                              int64_t user_num, int64_t n_heldout, const int* ks, int n_k, const double* disc, const double* idcg,
                              double* records, void* header, void* stream);
 
+/* THE ITEM GRAPH FROM INTERACTIONS ON THE DEVICE (notebooks/PMGT.ipynb cell 20, "Construct Product Graph": C = A A^T over the binary
+ * item-by-user matrix, an edge wherever an off-diagonal C[i][j] >= min_count).  The caller passes the two CSR images of the DEDUPLICATED
+ * (user, item) pairs, all device memory: item_ptr int64 [num_item + 1] / item_users int32 [n_pairs] (compact user indices in [0, n_users),
+ * any order inside a row) and user_ptr int64 [n_users + 1] / user_items int32 [n_pairs], and work int64 [num_item]: work[i] = the sum over
+ * the users of item i of the number of items of that user (the length of the row's expansion; it only chooses the row's schedule and must
+ * not be below the truth).  Indices outside their ranges are skipped, never dereferenced.
+ *   pmgt_item_graph_count  deg_flags uint32 [num_item]: bits 0 .. 30 = the number of j != i with C[i][j] >= min_count, bit 31 = the row did
+ *                          not fit the LDS table and was counted by the dense fallback; *max_count (one uint32, ZERO on entry) = the
+ *                          largest off-diagonal count seen, by integer atomicMax.
+ *   pmgt_item_graph_fill   with row_ptr int64 [num_item + 1] the caller's exclusive scan of those degrees, total = row_ptr[num_item] and
+ *                          node_of_item int32 [num_item]: for every row its qualifying neighbours in ASCENDING item order at
+ *                          [row_ptr[i], row_ptr[i + 1]): indices = node_of_item[j], counts = C[i][j].  deg_flags is the count pass's, read.
+ * slots: the entries of one wave's hash table, a power of two in [PMGT_ITEM_GRAPH_MIN_SLOTS, PMGT_ITEM_GRAPH_MAX_SLOTS]
+ * (pmgt_item_graph_default_slots() is the library's choice); a table is filled to 3/4 at most: a row with work <= 3/4 slots is taken by
+ * one wave, a longer one by a workgroup with 4 slots entries, and a row with MORE THAN 3 slots DISTINCT NEIGHBOURS by the fallback -- the
+ * flag depends on the row alone.
+ * scratch: uint32 [scratch_rows][num_item rounded up to a multiple of 4], 16-byte aligned, ZERO on entry and zero again on return; one
+ * fallback workgroup per scratch row, 1 <= scratch_rows <= 65535.  Two launches an entry, integer arithmetic only, no sync, no
+ * allocation; counts are sums and the stored order comes from a sort: the same inputs give the same bits.
+ * Refused (-2) before anything is launched: num_item outside [1, 2^31 - 2], n_pairs outside [1, 2^31 - 1], n_users outside [1, n_pairs],
+ * min_count outside [1, 2^31 - 1], slots outside those limits, scratch_rows outside its limits, a NULL or misaligned buffer, total < 1.
+ * Added without a bump of pmgt_abi_version(): three entries, nothing existing moved. */
+#define PMGT_ITEM_GRAPH_MIN_SLOTS 16
+#define PMGT_ITEM_GRAPH_MAX_SLOTS 1024
+#define PMGT_ITEM_GRAPH_DEFAULT_SLOTS 1024
+int pmgt_item_graph_default_slots(void);
+int pmgt_item_graph_count(const int64_t* item_ptr, const int32_t* item_users, const int64_t* user_ptr, const int32_t* user_items,
+                          const int64_t* work, int64_t num_item, int64_t n_users, int64_t n_pairs, int64_t min_count, int slots,
+                          uint32_t* deg_flags, uint32_t* max_count, uint32_t* scratch, int64_t scratch_rows, void* stream);
+int pmgt_item_graph_fill(const int64_t* item_ptr, const int32_t* item_users, const int64_t* user_ptr, const int32_t* user_items,
+                         const int64_t* work, int64_t num_item, int64_t n_users, int64_t n_pairs, int64_t min_count, int slots,
+                         const uint32_t* deg_flags, const int64_t* row_ptr, const int32_t* node_of_item, int64_t total, int32_t* indices,
+                         int32_t* counts, uint32_t* scratch, int64_t scratch_rows, void* stream);
+
 /* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
  * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
  * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and

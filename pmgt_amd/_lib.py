@@ -145,6 +145,7 @@ DCN_SCORE_ROW_STRIDE = 12      # PMGT_DCN_SCORE_ROW_STRIDE: floats a row of pmgt
 DCN_FACTORS, DCN_MAX_E = (8, 16, 32, 64), 256      # the covered shapes (pmgt_dcn_train_grad's comment): factor_num, E = factor_num * 2^deep_layers
 TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 RANK_HELDOUT_CHUNK, RANK_HELDOUT_FLAG_EXCLUDED, RANK_HELDOUT_HEADER_BYTES = 1024, 4, 128      # PMGT_RANK_HELDOUT_*
+ITEM_GRAPH_MIN_SLOTS, ITEM_GRAPH_MAX_SLOTS = 16, 1024      # PMGT_ITEM_GRAPH_*_SLOTS
 
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
 AVG_STATE_BYTES = 32            # PMGT_AVG_STATE_BYTES: int64 n_upd; 32-bit words [2] skip word, [3] w_old, [4] w_new, [5..7] reserved
@@ -172,6 +173,7 @@ HIP_SYMBOLS = [
     "pmgt_weight_average_update", "pmgt_weight_swap",
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows", "pmgt_rank_heldout", "pmgt_rank_heldout_reduce",
+    "pmgt_item_graph_default_slots", "pmgt_item_graph_count", "pmgt_item_graph_fill",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
@@ -339,6 +341,11 @@ def hip():
     L.pmgt_rank_heldout.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp]
     # (ranks, held_indptr, users, flags, n_users, user_num, n_heldout, ks, n_k, disc, idcg, records, header, stream)
     L.pmgt_rank_heldout_reduce.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i, vp, vp, vp, vp, vp]
+    L.pmgt_item_graph_default_slots.argtypes = []
+    # (item_ptr, item_users, user_ptr, user_items, work, num_item, n_users, n_pairs, min_count, slots, deg_flags, max_count, scratch, scratch_rows, stream)
+    L.pmgt_item_graph_count.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i, vp, vp, vp, i64, vp]
+    # (... slots, deg_flags, row_ptr, node_of_item, total, indices, counts, scratch, scratch_rows, stream)
+    L.pmgt_item_graph_fill.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i, vp, vp, vp, i64, vp, vp, vp, i64, vp]
     L.pmgt_ncf_train_layout.restype = i64
     L.pmgt_ncf_train_layout.argtypes = [i, i, i, i64, i64, vp]
     L.pmgt_ncf_train_workspace_bytes.restype = i64
