@@ -440,6 +440,34 @@ int pmgt_item_graph_fill(const int64_t* item_ptr, const int32_t* item_users, con
                          const uint32_t* deg_flags, const int64_t* row_ptr, const int32_t* node_of_item, int64_t total, int32_t* indices,
                          int32_t* counts, uint32_t* scratch, int64_t scratch_rows, void* stream);
 
+/* NEAREST ITEMS FROM THE EMBEDDINGS ON THE DEVICE: the score of every (query item, catalogue item) pair from ONE table [n_items][d] of fp32
+ * rows (the encoder's CLS vectors), as their dot product or their cosine -- what the graph-structure objective scores a pair of nodes by
+ * (pmgt/pmgt/losses.py PMGTGraphConstructLoss: F.normalize, then a dot product).  The reference has no such path.  The rows of scores are
+ * what pmgt_topk_rows and pmgt_rank_heldout take, with the query items in the place of the users.
+ *
+ * NORMS.  inv_norm[j] = 1 / max(sqrt(sum_k table[j][k]^2), eps) in fp32, the clamp of F.normalize (its default eps is 1e-12), the sum in ONE
+ * fixed order: the fmaf chain over k = 0 .. d - 1 in ascending order from 0, which is dot(j, j) below bit for bit, so that the rounding of
+ * the long sum cancels between a dot product and the norms where two rows are alike and s(j, j) is 1 to a few roundings.  One thread a
+ * row, 64 rows a wave.  A row with a NaN gets a NaN.  One launch, no atomic.
+ *
+ * SCORES.  scores[r][j] = s(queries[r], j) for every r in [0, n) and j in [0, n_items), fp32 row-major with row_stride floats a row
+ * (entries [r][n_items .. row_stride) are not written; offsets are 64-bit).  dot(i, j) = the fp32 fmaf chain over k = 0 .. d - 1 in ascending
+ * order from 0, on the exact f32-input matrix instruction;
+ *   inv_norm = NULL (metric "dot"):   s = dot(i, j)
+ *   else (metric "cosine"):           s = (dot(i, j) * inv_norm[min(i, j)]) * inv_norm[max(i, j)], each product rounded to fp32.
+ * So s(i, j) and s(j, i) have THE SAME BITS, the bits of s(i, j) depend on rows i and j alone -- not on n, the order of the queries or how
+ * the catalogue is cut into calls --, and a NaN in row j reaches exactly the scores of row j and column j.  The table is read in place: the
+ * query rows are gathered through `queries`, nothing is copied or normalised.  A query id outside [0, n_items) is never dereferenced:
+ * its row of scores is NaN.  One launch, stream-ordered, no allocation, no wait, no atomic: the same inputs give the same bits.
+ * Covered: 1 <= d <= PMGT_ITEM_SIM_MAX_D, 1 <= n_items <= 2^31 - 2, 1 <= n <= PMGT_NCF_MAX_USERS per call, row_stride >= n_items.  Refused
+ * (-2) before anything is launched, writing nothing: a size outside these limits, an eps that is not a positive finite number, a NULL or
+ * misaligned buffer (inv_norm may be NULL), more workgroups than a grid holds.
+ * Added without a bump of pmgt_abi_version(): two entries, nothing existing moved. */
+#define PMGT_ITEM_SIM_MAX_D 1024
+int pmgt_item_sim_norms(const float* table, int64_t n_items, int d, float eps, float* inv_norm, void* stream);
+int pmgt_item_sim_score(const float* table, const float* inv_norm, const int64_t* queries, int64_t n, int64_t n_items, int d, float* scores,
+                        int64_t row_stride, void* stream);
+
 /* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
  * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
  * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and

@@ -15,6 +15,7 @@ from .pair_train import pair_schedule_steps, sgd_step_host  # noqa: F401
 from .catalogue_eval import (CatalogueMetrics, HeldoutRanks, catalogue_metrics_host, evaluate_catalogue, heldout_csr,  # noqa: F401
                              heldout_ranks_host)
 from .item_graph import ItemGraph, build_item_graph, item_graph_host, synthetic_interactions  # noqa: F401
+from .similar import ItemSimScorer, edges_csr, evaluate_neighbours, holdout_edges, item_sim_host, similar_items  # noqa: F401
 
 __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_grad_host", "ng_sample", "NcfHeadTrainer", "fit_ncf",
            "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks", "DCN", "DcnGrad", "DcnTrainer", "evaluate_ctr", "fit_dcn",
@@ -22,4 +23,5 @@ __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_gr
            "check_ncf_model_covered", "ncf_model_grad_host", "ncf_model_layout", "NcfModelGrad", "NcfModelTrainer", "fit_ncf_model",
            "ncf_model_scores_host", "NcfModelScorer", "dcn_scores_host", "DcnScorer", "evaluate_catalogue", "heldout_ranks_host",
            "catalogue_metrics_host", "heldout_csr", "HeldoutRanks", "CatalogueMetrics", "sgd_step_host", "pair_schedule_steps",
-           "ItemGraph", "build_item_graph", "item_graph_host", "synthetic_interactions"]
+           "ItemGraph", "build_item_graph", "item_graph_host", "synthetic_interactions",
+           "ItemSimScorer", "edges_csr", "evaluate_neighbours", "holdout_edges", "item_sim_host", "similar_items"]
