@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import NCF_MAX_USERS, RANK_HELDOUT_CHUNK, RANK_HELDOUT_FLAG_EXCLUDED, RANK_HELDOUT_HEADER_BYTES, TOPK_FLAG_NAN  # noqa: F401
 from .evaluation import score_key
 from .metrics import RANK_MAX_KS      # PMGT_RANK_MAX_KS: the header holds that many sums a quantity
-from .recommend import ModelDispatch, check_csr, default_batch_users, exclusion_csr
+from .recommend import ModelDispatch, check_batch, check_csr, check_impl, default_batch_users, exclusion_csr, refuse_nan  # noqa: F401
 
 SUM_THREADS = 256             # the threads of the fixed summation tree
 
@@ -44,6 +44,20 @@ def count_common_pairs(a_csr, b_csr, item_num: int) -> int:
         owner = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
         ids.append(np.unique(owner * np.int64(item_num) + np.asarray(items, dtype=np.int64)))
     return int(len(np.intersect1d(ids[0], ids[1], assume_unique=True)))
+
+
+def heldout_queries(who: str, heldout, build_exclusion, n_items: int):
+    """The held-out prelude of evaluate_catalogue and evaluate_neighbours, in their order of refusals: an empty held-out CSR `heldout` is
+    refused, then build_exclusion() builds (and validates) the exclusion CSR, then a held-out pair that is also excluded is refused
+    -> (the exclusion CSR, the evaluated ids: those with at least one held-out item, ascending)."""
+    n_pairs = len(heldout[1])
+    if n_pairs < 1:
+        raise ValueError(f"{who}: the held-out set is empty")
+    exclusion = build_exclusion()
+    n_both = count_common_pairs(heldout, exclusion, n_items)
+    if n_both:
+        raise ValueError(f"{who}: {n_both} of {n_pairs} held-out pairs are also excluded")
+    return exclusion, np.nonzero(np.diff(heldout[0]) > 0)[0].astype(np.int64)
 
 
 def heldout_ranks_host(scores, users, heldout_csr, exclusion_csr=None):
@@ -133,6 +147,21 @@ def catalogue_metrics_host(ranks, indptr, ks=(10, 20)) -> dict:
     out["sums"] = dict(ndcg={k: tree_sum_host(out["ndcg"][k]) for k in ks}, recall={k: tree_sum_host(out["recall"][k]) for k in ks},
                        hit={k: tree_sum_host(out["hit"][k]) for k in ks}, rr=tree_sum_host(out["rr"]))
     return out
+
+
+def rank_host(score_rows, ids, batch: int, heldout, exclusion, ks):
+    """The yardstick of rank_device: score_rows(ids) -> numpy [m, I] on batches of `ids`, heldout_ranks_host, then catalogue_metrics_host;
+    rank_device's result with the records always there."""
+    ranks = np.zeros(len(heldout[1]), dtype=np.int32)
+    flags = np.zeros(len(ids), dtype=np.uint32)
+    for lo in range(0, len(ids), batch):
+        q = ids[lo: lo + batch]
+        r, flags[lo: lo + batch] = heldout_ranks_host(score_rows(q), q, heldout, exclusion)
+        ranks = np.maximum(ranks, r)                         # (a call fills the places of its own ids, the others stay 0)
+    records = catalogue_metrics_host(ranks, heldout[0], ks)
+    sums = records.pop("sums")
+    sums["n_nan"] = int(np.count_nonzero(flags & TOPK_FLAG_NAN))
+    return sums, records, ranks
 
 
 def summarize_catalogue(sums: dict, n_users: int, n_pairs: int, ks) -> dict:
@@ -252,6 +281,32 @@ class CatalogueMetrics:
                     hit={k: rec[2 * nk + i].copy() for i, k in enumerate(self.ks)}, rr=rec[3 * nk].copy())
 
 
+def rank_device(scorer, ids, batch: int, heldout, exclusion, id_num: int, ks, records: bool = False):
+    """The ranking pass on the device: per batch of `ids` (int64 numpy, ascending, checked by the caller) scorer.score then
+    HeldoutRanks.rank, with the held-out and the exclusion CSR over `id_num` ids, then one reduce.  Everything is uploaded and built
+    before the first score; nothing is copied to the host and nothing waits up to statistic(), the one small copy out.
+    -> (sums: CatalogueMetrics.statistic(), with n_nan; records: users, n_pos, ndcg[k], recall[k], hit[k], rr per id, or None unless
+    `records`; ranks int32 aligned with the held-out CSR, or None)."""
+    import torch
+    dev, n, n_items = scorer.device, len(ids), scorer.n_items
+    ranker = HeldoutRanks(dev, n_items, heldout[0], heldout[1], id_num, exclusion[0], exclusion[1])
+    reducer = CatalogueMetrics(dev, n, ks)
+    ids_d = torch.from_numpy(ids).to(dev)
+    flags_d = torch.zeros(n, dtype=torch.int32, device=dev)
+    work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
+    for lo in range(0, n, batch):
+        hi = min(lo + batch, n)
+        scorer.score(ids_d[lo:hi], out=work)
+        ranker.rank(work[: hi - lo], ids_d[lo:hi], flags_d[lo:hi])
+    reducer.reduce(ranker, ids_d, flags_d)
+    sums = reducer.statistic()                               # the one small copy out: after the loop
+    if not records:
+        return sums, None, None
+    rec = reducer.per_user()
+    rec.update(users=ids, n_pos=np.diff(heldout[0])[ids])
+    return sums, rec, ranker.ranks.cpu().numpy()
+
+
 def evaluate_catalogue(model, sampler, heldout, exclude=None, ks=(10, 20), batch_users: int = None, impl: str = "device", table=None,
                        threads: int = 8, seed: int = 0, per_user: bool = False):
     """Whole-catalogue ranking quality of `model` on the held-out (user, item) pairs -> {"n<k>", "r<k>", "hr<k>" for k in ks, "mrr",
@@ -262,72 +317,34 @@ def evaluate_catalogue(model, sampler, heldout, exclude=None, ks=(10, 20), batch
       interactions; None excludes nothing).  Held-out duplicates are dropped.  The evaluated users are those with at least one held-out
       item, in ascending id order.
     model, sampler, table, batch_users and the eval-mode handling are recommend()'s, for a PMGT_NCF, the stand-alone NCF class and a DCN.
-    impl="device": per batch the class's fused scorer, then pmgt_rank_heldout; nothing is copied to the host and nothing waits inside the
-      loop; after it one reduce and one small copy.  The ranks are exact for the scorer's scores whatever `batch_users` is.
-    impl="host": the yardstick -- host_scores / dcn_host_scores, heldout_ranks_host, catalogue_metrics_host; needs no GPU on a CPU model.
+    impl="device": rank_device with the class's fused scorer; the ranks are exact for the scorer's scores whatever `batch_users` is.
+    impl="host": the yardstick -- rank_host over host_scores / dcn_host_scores; needs no GPU on a CPU model.
     per_user=True: returns (result, dict) with users, n_pos, ndcg[k], recall[k], hit[k], rr per evaluated user, and ranks with the
       held-out CSR (indptr, items) they align with.
     Raises ValueError for ids outside the model's tables, a held-out pair that is also excluded (naming how many), a user with a NaN score
     among their eligible items (naming how many users), an empty held-out set, and -- impl="device" only -- a head shape the kernels do
     not cover."""
     from .metrics import check_ks
-    if impl not in ("host", "device"):
-        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    check_impl(impl)
     ks = check_ks(ks)
     user_num, n_items = model.user_num, model.item_num
-    h_indptr, h_items = heldout_csr(heldout, user_num, n_items)
-    n_pairs = len(h_items)
-    if n_pairs < 1:
-        raise ValueError("evaluate_catalogue: the held-out set is empty")
-    indptr, excl = exclusion_csr(exclude, user_num, n_items)
-    n_both = count_common_pairs((h_indptr, h_items), (indptr, excl), n_items)
-    if n_both:
-        raise ValueError(f"evaluate_catalogue: {n_both} of {n_pairs} held-out pairs are also excluded")
-    users = np.nonzero(np.diff(h_indptr) > 0)[0].astype(np.int64)
+    held = heldout_csr(heldout, user_num, n_items)
+    exclusion, users = heldout_queries("evaluate_catalogue", held, lambda: exclusion_csr(exclude, user_num, n_items), n_items)
     dispatch = ModelDispatch(model, "evaluate_catalogue")
     if impl == "device":
         dispatch.check_covered()
-    if batch_users is not None and (not isinstance(batch_users, (int, np.integer)) or batch_users < 1):
-        raise ValueError(f"evaluate_catalogue: batch_users = {batch_users!r} must be a positive integer or None")
-    n_users = len(users)
-    batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
+    batch = check_batch(batch_users, len(users), n_items, "evaluate_catalogue")
     dispatch.resolve_table(sampler, table, threads, seed)
-    dev = dispatch.dev
-    was_training, set_mode = model.training, dispatch.sets_mode(impl)
-    if set_mode:
-        model.eval()
-    try:
+    with dispatch.eval_mode(impl):
         if impl == "host":
-            ranks, flags = heldout_ranks_host(dispatch.host_scores(users), users, (h_indptr, h_items), (indptr, excl))
-            pu = catalogue_metrics_host(ranks, h_indptr, ks)
-            sums, n_nan = pu.pop("sums"), int(np.count_nonzero(flags & TOPK_FLAG_NAN))
+            sums, pu, ranks = rank_host(dispatch.host_scores, users, batch, held, exclusion, ks)
         else:
             import torch
             with torch.no_grad():
-                scorer = dispatch.scorer()
-                ranker = HeldoutRanks(dev, n_items, h_indptr, h_items, user_num, indptr, excl)
-                reducer = CatalogueMetrics(dev, n_users, ks)
-                users_d = torch.from_numpy(users).to(dev)
-                flags_d = torch.zeros(n_users, dtype=torch.int32, device=dev)
-                work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
-                for lo in range(0, n_users, batch):
-                    hi = min(lo + batch, n_users)
-                    scorer.score(users_d[lo:hi], out=work)
-                    ranker.rank(work[: hi - lo], users_d[lo:hi], flags_d[lo:hi])
-                reducer.reduce(ranker, users_d, flags_d)
-                sums = reducer.statistic()                   # the one small copy out: after the loop
-            n_nan = sums["n_nan"]
-            if per_user:
-                pu = reducer.per_user()
-                pu.update(users=users, n_pos=np.diff(h_indptr)[users])
-                ranks = ranker.ranks.cpu().numpy()
-    finally:
-        if set_mode:
-            model.train(was_training)
-    if n_nan:
-        raise ValueError(f"evaluate_catalogue: {n_nan} of {n_users} users have a NaN score among their eligible items")
-    result = summarize_catalogue(sums, n_users, n_pairs, ks)
+                sums, pu, ranks = rank_device(dispatch.scorer(), users, batch, held, exclusion, user_num, ks, per_user)
+    refuse_nan("evaluate_catalogue", sums["n_nan"], len(users), "users")
+    result = summarize_catalogue(sums, len(users), len(held[1]), ks)
     if not per_user:
         return result
-    pu.update(ranks=ranks, indptr=h_indptr, items=h_items)
+    pu.update(ranks=ranks, indptr=held[0], items=held[1])
     return result, pu

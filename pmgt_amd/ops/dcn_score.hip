@@ -5,11 +5,9 @@
 //
 // THE DEEP NET is the NCF MLP tower with factor' = 2 F, layers' = L, d' = E: every layer is Linear -> LayerNorm -> ReLU (or Linear -> ReLU),
 // the widths run 2 E -> E -> ... -> 2 F, and layer 0 splits into a per-user and a per-item half that the caller computes (Pu [n][E],
-// Pi [I][E] with b_0 folded in).  The tile is ncf_score.hip's (its header states the design: 32 items x 4 UW users a workgroup of 4 waves,
-// every layer transposed on the exact f32-input 32x32x2 MFMA, the activations of a pair chained in the registers of its lane, the weights
-// streamed through LDS in chunks of 32 k-columns by ncf_score_tile.h); the LayerNorm is ncf_model_score.hip's (two passes, biased variance,
-// 1 / sqrt(var + eps), one exchange with lane ^ 32).  The kernel is a template on LayerNorm on / off: both need the cross epilogue.  The last
-// deep width is 2 F, up to 128: four 32-feature blocks in the output dot.
+// Pi [I][E] with b_0 folded in).  The tower, with and without LayerNorm, is ncf_score_tile.h's, whose header states the design; this file
+// adds the row scalars in LDS and the output layer with the cross net as the tower's final store.  The last deep width is 2 F, up to 128:
+// four 32-feature blocks in the output dot.
 //
 // THE CROSS NET COLLAPSES (dcn_head.py's header): the reference's layer adds x0, not x^(c), so every cross state is a scalar multiple of x0
 // (no LayerNorm) or an affine image of the centred x0 (LayerNorm), and every s_c and the output dot split into one scalar per user row plus
@@ -80,86 +78,6 @@ template <bool LN> __device__ __forceinline__ float dcs_cross(const float* ur, c
     }
 }
 
-// acc = relu(LN(acc)) over the M true features of every pair (ncf_model_score.hip's nms_ln_relu), or relu(acc)
-template <bool LN, int UW, int NB>
-__device__ __forceinline__ void dcs_norm_relu(f32x16 (&acc)[UW][NB], const float* __restrict__ gamma, const float* __restrict__ beta, int M, float eps,
-                                              int h) {
-    if constexpr (!LN) {
-#pragma unroll
-        for (int u = 0; u < UW; ++u)
-#pragma unroll
-            for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-                for (int g = 0; g < 16; ++g) acc[u][mb][g] = relu_keep_nan(acc[u][mb][g]);
-    } else {
-        const float inv = 1.f / (float)M;                    // (M is a power of two: the product is the quotient)
-        float mean[UW], rstd[UW];
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-            float s = 0.f;
-#pragma unroll
-            for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-                for (int g = 0; g < 16; ++g)
-                    if (mb * 32 + rho(g) + 4 * h < M) s += acc[u][mb][g];
-            s += __shfl_xor(s, 32, 64);
-            mean[u] = s * inv;
-            float q = 0.f;
-#pragma unroll
-            for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-                for (int g = 0; g < 16; ++g)
-                    if (mb * 32 + rho(g) + 4 * h < M) {
-                        const float c = acc[u][mb][g] - mean[u];
-                        q += c * c;
-                    }
-            q += __shfl_xor(q, 32, 64);
-            rstd[u] = 1.f / sqrtf(q * inv + eps);
-        }
-#pragma unroll
-        for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int f = mb * 32 + rho(g) + 4 * h;
-                const bool live = f < M;
-                const float ga = live ? gamma[f] : 0.f, be = live ? beta[f] : 0.f;
-#pragma unroll
-                for (int u = 0; u < UW; ++u) acc[u][mb][g] = live ? relu_keep_nan(((acc[u][mb][g] - mean[u]) * rstd[u]) * ga + be) : 0.f;
-            }
-    }
-}
-
-// Y = relu([LN](W X + bias)) for a layer whose input X sits in the accumulators of the previous one: K true inputs (X is zero past them), M outputs
-template <bool LN, int UW, int NBI, int NBO>
-__device__ __forceinline__ void dcs_layer_from_acc(const f32x16 (&X)[UW][NBI], f32x16 (&Y)[UW][NBO], const DcsArgs& a, int layer, float* ws, int tid) {
-    const int lane = tid & 63, p = lane & 31, h = lane >> 5;
-    const int M = a.d >> layer, K = a.d >> (layer - 1);
-    const float* __restrict__ W = a.w[layer];
-    bias_init<UW, NBO>(Y, a.b[layer], M, h);
-    float st[NBO * 4];
-    chunk_fetch<NBO>(st, W, M, K, 0, tid);
-#pragma unroll
-    for (int b = 0; b < NBI; ++b) {
-        if (b * 32 >= K) break;                      // (uniform)
-        __syncthreads();                             // every wave is done with the previous chunk
-        chunk_store<NBO>(st, ws, tid);
-        __syncthreads();
-        if ((b + 1) * 32 < K && b + 1 < NBI) chunk_fetch<NBO>(st, W, M, K, (b + 1) * 32, tid);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            if (b * 32 + rho(g) >= K) continue;      // (uniform) k-steps wholly past the true width
-            float wa[NBO];
-#pragma unroll
-            for (int mb = 0; mb < NBO; ++mb) wa[mb] = ws[(mb * 32 + p) * NCF_CHUNK_STRIDE + rho(g) + 4 * h];
-#pragma unroll
-            for (int u = 0; u < UW; ++u)
-#pragma unroll
-                for (int mb = 0; mb < NBO; ++mb) Y[u][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[mb], X[u][b][g], Y[u][mb], 0, 0, 0);
-        }
-    }
-    dcs_norm_relu<LN, UW, NBO>(Y, a.gamma[layer], a.beta[layer], M, a.eps, h);
-}
-
 // the output layer on the last activations (features 32 b + rho(g) + 4 h of pair p in X[u][b][g]) plus the cross net; one store per pair
 template <bool LN, int UW, int NB>
 __device__ __forceinline__ void dcs_output_store(const f32x16 (&X)[UW][NB], const DcsArgs& a, const DcsTile& t) {
@@ -188,45 +106,15 @@ __device__ __forceinline__ void dcs_output_store(const f32x16 (&X)[UW][NB], cons
     }
 }
 
-// the layers behind `layer - 1`, halving the block count while it is above one, then the output layer
-template <bool LN, int UW, int NBI>
-__device__ __forceinline__ void dcs_run_tail(f32x16 (&X)[UW][NBI], int layer, const DcsArgs& a, const DcsTile& t, float* ws, int tid) {
-    if constexpr (NBI > 1) {
-        if (layer < a.num_layers) {
-            f32x16 Y[UW][NBI / 2];
-            dcs_layer_from_acc<LN, UW, NBI, NBI / 2>(X, Y, a, layer, ws, tid);
-            dcs_run_tail<LN, UW, NBI / 2>(Y, layer + 1, a, t, ws, tid);
-        } else {
-            dcs_output_store<LN, UW, NBI>(X, a, t);
-        }
-    } else {
-        for (; layer < a.num_layers; ++layer) {
-            f32x16 Y[UW][1];
-            dcs_layer_from_acc<LN, UW, 1, 1>(X, Y, a, layer, ws, tid);
-#pragma unroll
-            for (int u = 0; u < UW; ++u) X[u][0] = Y[u][0];
-        }
-        dcs_output_store<LN, UW, 1>(X, a, t);
-    }
-}
-
-// floats of dynamic LDS: Pi tile | Pu tile | item scalars | user scalars | gamma0 | beta0 | weight chunk
-static size_t dcs_smem_floats(int d, int TU, int NB) {
-    return (size_t)NCF_ITEMS * (d + 1) + (size_t)TU * d + (size_t)(NCF_ITEMS + TU) * DCS_RS + (size_t)2 * d + (size_t)32 * NB * NCF_CHUNK_STRIDE;
-}
-
-// L >= 2.  NB = 32-row blocks of layer 1's output (E / 2 rounded up to 32)
+// L >= 2.  NB = 32-row blocks of layer 1's output (E / 2 rounded up to 32).  The file's own LDS tiles are the row scalars: item
+// [32][DCS_RS] | user [TU][DCS_RS]; gamma0 / beta0 are reserved with and without LayerNorm
 template <bool LN, int UW, int NB> __global__ __launch_bounds__(NCF_THREADS) void dcn_score_kernel(DcsArgs a) {
     extern __shared__ __align__(16) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5;
     const int d = a.d, TU = NCF_WAVES * UW;
-    float* pi_s = smem;                                      // [32][d + 1]
-    float* pu_s = pi_s + NCF_ITEMS * (d + 1);                // [TU][d]
-    float* ir_s = pu_s + TU * d;                             // [32][DCS_RS]
+    const TowerLds s = tower_lds(smem, d, TU, (NCF_ITEMS + TU) * DCS_RS, true);
+    float* ir_s = s.own;                                     // [32][DCS_RS]
     float* ur_s = ir_s + NCF_ITEMS * DCS_RS;                 // [TU][DCS_RS]
-    float* g0_s = ur_s + TU * DCS_RS;                        // [d]
-    float* b0_s = g0_s + d;                                  // [d]
-    float* ws = b0_s + d;                                    // [32 NB][33]
     DcsTile t;
     t.j0 = (int)(blockIdx.x % (unsigned)a.item_tiles) * NCF_ITEMS;
     t.r0 = (int)(blockIdx.x / (unsigned)a.item_tiles) * TU;
@@ -234,15 +122,7 @@ template <bool LN, int UW, int NB> __global__ __launch_bounds__(NCF_THREADS) voi
     t.lane = lane;
     t.ur_s = ur_s;
     t.ir_s = ir_s;
-    // rows outside the batch / the catalogue are zeros: computed, never stored
-    for (int e = tid; e < NCF_ITEMS * d; e += NCF_THREADS) {
-        const int row = e / d, c = e - row * d, j = t.j0 + row;
-        pi_s[row * (d + 1) + c] = j < a.n_items ? a.pi[(int64_t)j * d + c] : 0.f;
-    }
-    for (int e = tid; e < TU * d; e += NCF_THREADS) {
-        const int row = e / d, c = e - row * d, r = t.r0 + row;
-        pu_s[e] = r < a.n ? a.pu[(int64_t)r * d + c] : 0.f;
-    }
+    tower_load_tiles<LN, UW>(a, s, t.r0, t.j0, tid);
     for (int e = tid; e < NCF_ITEMS * DCS_RS; e += NCF_THREADS) {
         const int row = e / DCS_RS, c = e - row * DCS_RS, j = t.j0 + row;
         ir_s[e] = j < a.n_items ? a.ir[(int64_t)j * DCS_RS + c] : 0.f;
@@ -251,83 +131,14 @@ template <bool LN, int UW, int NB> __global__ __launch_bounds__(NCF_THREADS) voi
         const int row = e / DCS_RS, c = e - row * DCS_RS, r = t.r0 + row;
         ur_s[e] = r < a.n ? a.ur[(int64_t)r * DCS_RS + c] : 0.f;
     }
-    if constexpr (LN)
-        for (int e = tid; e < d; e += NCF_THREADS) g0_s[e] = a.gamma[0][e], b0_s[e] = a.beta[0][e];
     __syncthreads();                                         // the tiles are written
-    const float* pu_w = pu_s + wave * UW * d;
-    const float* pi_row = pi_s + p * (d + 1);
+    const float* pu_w = s.pu_s + wave * UW * d;
+    const float* pi_row = s.pi_s + p * (d + 1);
     float mean[UW], rstd[UW];
-    if constexpr (LN) {
-        // the statistics of layer 0's row y = Pu[r] + Pi[j] of every pair of the lane: each half sums its half of the features, one exchange
-        const int half = d >> 1, f0 = h * half;
-        const float inv = 1.f / (float)d;                    // (d is a power of two)
-        float s[UW];
-#pragma unroll
-        for (int u = 0; u < UW; ++u) s[u] = 0.f;
-        for (int k = f0; k < f0 + half; k += 4) {            // (half is a multiple of 8; the Pu rows are 16-byte aligned in LDS)
-            const float pv[4] = {pi_row[k], pi_row[k + 1], pi_row[k + 2], pi_row[k + 3]};
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const float4 uv = *reinterpret_cast<const float4*>(pu_w + u * d + k);
-                s[u] += uv.x + pv[0], s[u] += uv.y + pv[1], s[u] += uv.z + pv[2], s[u] += uv.w + pv[3];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-            s[u] += __shfl_xor(s[u], 32, 64);
-            mean[u] = s[u] * inv;
-            s[u] = 0.f;
-        }
-        for (int k = f0; k < f0 + half; k += 4) {
-            const float pv[4] = {pi_row[k], pi_row[k + 1], pi_row[k + 2], pi_row[k + 3]};
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const float4 uv = *reinterpret_cast<const float4*>(pu_w + u * d + k);
-                const float c0 = (uv.x + pv[0]) - mean[u], c1 = (uv.y + pv[1]) - mean[u], c2 = (uv.z + pv[2]) - mean[u], c3 = (uv.w + pv[3]) - mean[u];
-                s[u] += c0 * c0, s[u] += c1 * c1, s[u] += c2 * c2, s[u] += c3 * c3;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-            s[u] += __shfl_xor(s[u], 32, 64);
-            rstd[u] = 1.f / sqrtf(s[u] * inv + a.eps);
-        }
-    }
-    // layer 1: K = d inputs formed on the fly, M = d / 2 outputs
-    const int K = d, M = d >> 1;
-    const float* __restrict__ W = a.w[1];
+    if constexpr (LN) tower_row_stats<UW>(pu_w, pi_row, d, a.eps, h, mean, rstd);
     f32x16 acc[UW][NB];
-    bias_init<UW, NB>(acc, a.b[1], M, h);
-    float st[NB * 4];
-    chunk_fetch<NB>(st, W, M, K, 0, tid);
-    for (int k0 = 0; k0 < K; k0 += NCF_CHUNK) {
-        __syncthreads();                                     // every wave is done with the previous chunk
-        chunk_store<NB>(st, ws, tid);
-        __syncthreads();
-        if (k0 + NCF_CHUNK < K) chunk_fetch<NB>(st, W, M, K, k0 + NCF_CHUNK, tid);
-        const int kc = min(NCF_CHUNK, K - k0);               // (K >= 32 here: always 32)
-        for (int s0 = 0; s0 < kc; s0 += 8)
-#pragma unroll
-        for (int s = s0; s < s0 + 8; s += 2) {
-            const int k = s + h;
-            const float piv = pi_row[k0 + k];
-            float ga = 0.f, be = 0.f;
-            if constexpr (LN) ga = g0_s[k0 + k], be = b0_s[k0 + k];
-            float wa[NB];
-#pragma unroll
-            for (int mb = 0; mb < NB; ++mb) wa[mb] = ws[(mb * 32 + p) * NCF_CHUNK_STRIDE + k];
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                float hv = pu_w[u * d + k0 + k] + piv;
-                if constexpr (LN) hv = ((hv - mean[u]) * rstd[u]) * ga + be;
-                hv = relu_keep_nan(hv);
-#pragma unroll
-                for (int mb = 0; mb < NB; ++mb) acc[u][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[mb], hv, acc[u][mb], 0, 0, 0);
-            }
-        }
-    }
-    dcs_norm_relu<LN, UW, NB>(acc, a.gamma[1], a.beta[1], M, a.eps, h);
-    dcs_run_tail<LN, UW, NB>(acc, 2, a, t, ws, tid);
+    tower_first_layer<LN, UW, NB>(acc, a, s, pu_w, pi_row, mean, rstd, tid);
+    tower_run_tail<LN, UW, NB>(acc, 2, a, s.ws, tid, [&](const auto& X) { dcs_output_store<LN>(X, a, t); });
 }
 
 // L = 1: z = wo_deep . relu([LN_0](Pu[r] + Pi[j])) + z_cross + bo over E = 2 F <= 128 features; one pair a thread, items on the lanes
@@ -440,12 +251,9 @@ static int dcs_shape(const pmgt_dcn_head* head, const char* who) {
 
 template <bool LN, int UW, int NB> static int dcs_launch(const DcsArgs& a, hipStream_t st) {
     const int TU = NCF_WAVES * UW;
-    const size_t smem = sizeof(float) * dcs_smem_floats(a.d, TU, NB);
-    const int64_t grid = (int64_t)a.item_tiles * ((a.n + TU - 1) / TU);
-    PMGT_CHECK(grid <= 0x7FFFFFFF, -2, "pmgt_dcn_score: %lld workgroups exceed the grid limit; split the users", (long long)grid);
-    PMGT_SMEM_ATTR(((const void*)dcn_score_kernel<LN, UW, NB>), 65536);      // (the largest tile, E = 256, takes 61 952 bytes)
-    hipLaunchKernelGGL((dcn_score_kernel<LN, UW, NB>), dim3((unsigned)grid), dim3(NCF_THREADS), smem, st, a);
-    return 0;
+    const size_t smem = sizeof(float) * tower_lds_floats(a.d, TU, NB, (NCF_ITEMS + TU) * DCS_RS, true);
+    // (the largest tile, E = 256, takes 61 952 bytes)
+    return tower_launch<DcsArgs, dcn_score_kernel<LN, UW, NB>>("pmgt_dcn_score", a, TU, smem, 65536, st);
 }
 
 template <bool LN> static int dcs_dispatch(const DcsArgs& a, int L, int64_t n, int64_t n_items, hipStream_t st) {

@@ -4,23 +4,12 @@
 //
 // WHICH CASES RUN HERE.  A model WITHOUT LayerNorm of kind MLP / NeuMF-end / NeuMF-pre is the head ncf_score.hip scores: the entry hands it
 // to pmgt_ncf_score, so those bits are that file's.  The kernels below cover the LayerNorm layer  h_(l+1) = relu(LN_l(W_l h_l + b_l))  and
-// kind GMF.  The MLP tower keeps ncf_score.hip's design (its header: layer 0 split into Pu [n][d] and Pi [I][d] by the caller, every layer
-// transposed on the exact f32-input 32x32x2 MFMA, the activations of a pair chained in the registers of its lane, the weights streamed
-// through LDS in chunks of 32 k-columns, 32 items x 4 UW users a workgroup) and shares ncf_score_tile.h with it: the chunk transfers, the
-// bias and the predict layer.  What is new:
-//   LAYER 0.   The pre-norm row of a pair is y = Pu[r] + Pi[j], formed on the fly from the LDS tiles.  Before the k-loop every lane computes
-//              its pair's mean and rstd over the d features: lane half h sums the features [h d / 2, (h + 1) d / 2) in order, the halves
-//              exchange once (a + b and b + a are the same float, so both halves hold the same bits), then the same for the squared
-//              deviations.  The k-loop feeds relu(((y - mean) rstd) gamma0[k] + beta0[k]); gamma0 / beta0 sit in LDS.
-//   LAYER l.   The M = d >> l outputs of a pair sit in the 16 registers x NB blocks of its lane and of the lane of the other half: the
-//              statistics are a register sum plus one exchange, before the ReLU.  The blocks are zero-padded to 32 features; features past
-//              M take no part in either sum, the divisor is M, and they are written back as 0.
-//   NUMERICS.  ncf_model_train.hip's: two passes (the mean, then the sum of squared deviations), biased variance, rstd = 1 / sqrt(var +
-//              eps), the file compiled without contraction.  The products keep ONE accumulation chain: K is at most 256 here (that
-//              file's K = 512 needed four): the k-ordered chain emulated on the host stays within 1.5 x the fp32 formula's error at d = 256,
-//              dealing the steps onto two or four accumulators gains nothing there, and the device gives 1.62 x at most (the bound is 4 x).
-//   NaN.       A pair's values live on the two lanes of its item only (the MFMA's B column, the one exchange with lane ^ 32), and the ReLU
-//              keeps a NaN: a NaN in a row of Pi reaches every score of that item and no other.
+// kind GMF.  The MLP tower, its LayerNorm (layer 0's row statistics from the LDS tiles, layer l's from the registers; the numerics are
+// ncf_model_train.hip's: two passes, biased variance, rstd = 1 / sqrt(var + eps), no contraction) and the tile kernel are
+// ncf_score_tile.h's, whose header states the design: the tile kernel here is its LN = true instance.  The products keep ONE accumulation
+// chain: K is at most 256 here (ncf_model_train.hip's K = 512 needed four): the k-ordered chain emulated on the host stays within 1.5 x the
+// fp32 formula's error at d = 256, dealing the steps onto two or four accumulators gains nothing there, and the device gives 1.62 x at most
+// (the bound is 4 x).
 //   L = 1.     One pair a thread (ncf_score.hip's VALU kernel) with the LayerNorm over the F features in front of the predict dot.
 //   GMF.       scores[r][j] = sum_f wp[f] (gu[users[r]][f] gi[j][f]) + bp: one item a thread, its gi row in registers, 8 users a workgroup
 //              (their gu rows are uniform loads), the dot dealt onto four sums joined as (a + b) + (c + d).  No MLP tensor is read.
@@ -34,225 +23,8 @@ namespace pmgt {
 
 static constexpr int NMS_GMF_USERS = 8;                                     // users a workgroup of the GMF kernel
 
-struct NmsArgs {
-    const float* w[NCF_MAX_LAYERS];      // [i]: W_i [d >> i][d >> (i - 1)]; [0] is never read (the caller's split)
-    const float* b[NCF_MAX_LAYERS];
-    const float* gamma[NCF_MAX_LAYERS];  // LayerNorm of layer i over d >> i features
-    const float* beta[NCF_MAX_LAYERS];
-    const float* wp;                     // predict_layer.weight [factor] or, with both branches, [2 factor] = [gmf | mlp]
-    const float* bp;
-    const float* gu;                     // embed_user_GMF.weight [user_num][factor] or NULL
-    const float* gi;                     // embed_item_GMF.weight [I][factor] or NULL
-    const float* pu;                     // [n][d]
-    const float* pi;                     // [I][d]
-    const int64_t* users;                // [n]
-    float* scores;                       // [n][row_stride]
-    int64_t row_stride, user_num;
-    float eps;
-    int n, n_items, d, factor, num_layers, item_tiles;
-};
-
-// acc = relu(LN(acc)) over the M true features of every pair (feature 32 mb + rho(g) + 4 h of pair p in acc[u][mb][g], the other half of the
-// features on lane ^ 32); features past M come out as 0
-template <int UW, int NB>
-__device__ __forceinline__ void nms_ln_relu(f32x16 (&acc)[UW][NB], const float* __restrict__ gamma, const float* __restrict__ beta, int M, float eps,
-                                            int h) {
-    const float inv = 1.f / (float)M;                        // (M is a power of two: the product is the quotient)
-    float mean[UW], rstd[UW];
-#pragma unroll
-    for (int u = 0; u < UW; ++u) {
-        float s = 0.f;
-#pragma unroll
-        for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-            for (int g = 0; g < 16; ++g)
-                if (mb * 32 + rho(g) + 4 * h < M) s += acc[u][mb][g];
-        s += __shfl_xor(s, 32, 64);
-        mean[u] = s * inv;
-        float q = 0.f;
-#pragma unroll
-        for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-            for (int g = 0; g < 16; ++g)
-                if (mb * 32 + rho(g) + 4 * h < M) {
-                    const float c = acc[u][mb][g] - mean[u];
-                    q += c * c;
-                }
-        q += __shfl_xor(q, 32, 64);
-        rstd[u] = 1.f / sqrtf(q * inv + eps);
-    }
-#pragma unroll
-    for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int f = mb * 32 + rho(g) + 4 * h;
-            const bool live = f < M;
-            const float ga = live ? gamma[f] : 0.f, be = live ? beta[f] : 0.f;
-#pragma unroll
-            for (int u = 0; u < UW; ++u) acc[u][mb][g] = live ? relu_keep_nan(((acc[u][mb][g] - mean[u]) * rstd[u]) * ga + be) : 0.f;
-        }
-}
-
-// Y = relu(LN(W X + bias)) for a layer whose input X sits in the accumulators of the previous one: K true inputs (X is zero past them), M outputs
-template <int UW, int NBI, int NBO>
-__device__ __forceinline__ void nms_layer_from_acc(const f32x16 (&X)[UW][NBI], f32x16 (&Y)[UW][NBO], const NmsArgs& a, int layer, float* ws, int tid) {
-    const int lane = tid & 63, p = lane & 31, h = lane >> 5;
-    const int M = a.d >> layer, K = a.d >> (layer - 1);
-    const float* __restrict__ W = a.w[layer];
-    bias_init<UW, NBO>(Y, a.b[layer], M, h);
-    float st[NBO * 4];
-    chunk_fetch<NBO>(st, W, M, K, 0, tid);
-#pragma unroll
-    for (int b = 0; b < NBI; ++b) {
-        if (b * 32 >= K) break;                      // (uniform)
-        __syncthreads();                             // every wave is done with the previous chunk
-        chunk_store<NBO>(st, ws, tid);
-        __syncthreads();
-        if ((b + 1) * 32 < K && b + 1 < NBI) chunk_fetch<NBO>(st, W, M, K, (b + 1) * 32, tid);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            if (b * 32 + rho(g) >= K) continue;      // (uniform) k-steps wholly past the true width
-            float wa[NBO];
-#pragma unroll
-            for (int mb = 0; mb < NBO; ++mb) wa[mb] = ws[(mb * 32 + p) * NCF_CHUNK_STRIDE + rho(g) + 4 * h];
-#pragma unroll
-            for (int u = 0; u < UW; ++u)
-#pragma unroll
-                for (int mb = 0; mb < NBO; ++mb) Y[u][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[mb], X[u][b][g], Y[u][mb], 0, 0, 0);
-        }
-    }
-    nms_ln_relu<UW, NBO>(Y, a.gamma[layer], a.beta[layer], M, a.eps, h);
-}
-
-// the layers behind `layer - 1`, halving the block count while it is above one, then the predict layer
-template <int UW, int NBI>
-__device__ __forceinline__ void nms_run_tail(f32x16 (&X)[UW][NBI], int layer, const NmsArgs& a, const NcfTile& t, float* ws, int tid) {
-    if constexpr (NBI > 1) {
-        if (layer < a.num_layers) {
-            f32x16 Y[UW][NBI / 2];
-            nms_layer_from_acc<UW, NBI, NBI / 2>(X, Y, a, layer, ws, tid);
-            nms_run_tail<UW, NBI / 2>(Y, layer + 1, a, t, ws, tid);
-        } else {
-            predict_store<UW, NBI>(X, a, t);
-        }
-    } else {
-        for (; layer < a.num_layers; ++layer) {
-            f32x16 Y[UW][1];
-            nms_layer_from_acc<UW, 1, 1>(X, Y, a, layer, ws, tid);
-#pragma unroll
-            for (int u = 0; u < UW; ++u) X[u][0] = Y[u][0];
-        }
-        predict_store<UW, 1>(X, a, t);
-    }
-}
-
-// NB = 32-row blocks of layer 1's output (d / 2 rounded up to 32); dynamic LDS: Pi tile | Pu tile | GMF item tile | gamma0 | beta0 | weight chunk
-template <int UW, int NB> __global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_kernel(NmsArgs a) {
-    extern __shared__ __align__(16) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5;
-    const int d = a.d, F = a.factor, TU = NCF_WAVES * UW;
-    float* pi_s = smem;                                      // [32][d + 1]
-    float* pu_s = pi_s + NCF_ITEMS * (d + 1);                // [TU][d]
-    float* gi_s = pu_s + TU * d;                             // [32][F + 1]
-    float* g0_s = gi_s + NCF_ITEMS * (F + 1);                // [d]
-    float* b0_s = g0_s + d;                                  // [d]
-    float* ws = b0_s + d;                                    // [32 NB][33]
-    NcfTile t;
-    t.j0 = (int)(blockIdx.x % (unsigned)a.item_tiles) * NCF_ITEMS;
-    t.r0 = (int)(blockIdx.x / (unsigned)a.item_tiles) * TU;
-    t.wave = wave;
-    t.lane = lane;
-    t.gi_s = gi_s;
-    // rows outside the batch / the catalogue are zeros: computed, never stored
-    for (int e = tid; e < NCF_ITEMS * d; e += NCF_THREADS) {
-        const int row = e / d, c = e - row * d, j = t.j0 + row;
-        pi_s[row * (d + 1) + c] = j < a.n_items ? a.pi[(int64_t)j * d + c] : 0.f;
-    }
-    for (int e = tid; e < TU * d; e += NCF_THREADS) {
-        const int row = e / d, c = e - row * d, r = t.r0 + row;
-        pu_s[e] = r < a.n ? a.pu[(int64_t)r * d + c] : 0.f;
-    }
-    if (a.gi)
-        for (int e = tid; e < NCF_ITEMS * F; e += NCF_THREADS) {
-            const int row = e / F, c = e - row * F, j = t.j0 + row;
-            gi_s[row * (F + 1) + c] = j < a.n_items ? a.gi[(int64_t)j * F + c] : 0.f;
-        }
-    for (int e = tid; e < d; e += NCF_THREADS) g0_s[e] = a.gamma[0][e], b0_s[e] = a.beta[0][e];
-    __syncthreads();                                         // the tiles are written
-    // the statistics of layer 0's row y = Pu[r] + Pi[j] of every pair of the lane: each half sums its half of the features, one exchange
-    const float* pu_w = pu_s + wave * UW * d;
-    const float* pi_row = pi_s + p * (d + 1);
-    const int half = d >> 1, f0 = h * half;
-    const float inv = 1.f / (float)d;                        // (d is a power of two)
-    float mean[UW], rstd[UW];
-    {
-        float s[UW];
-#pragma unroll
-        for (int u = 0; u < UW; ++u) s[u] = 0.f;
-        for (int k = f0; k < f0 + half; k += 4) {            // (half is a multiple of 8; the Pu rows are 16-byte aligned in LDS)
-            const float pv[4] = {pi_row[k], pi_row[k + 1], pi_row[k + 2], pi_row[k + 3]};
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const float4 uv = *reinterpret_cast<const float4*>(pu_w + u * d + k);
-                s[u] += uv.x + pv[0], s[u] += uv.y + pv[1], s[u] += uv.z + pv[2], s[u] += uv.w + pv[3];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-            s[u] += __shfl_xor(s[u], 32, 64);
-            mean[u] = s[u] * inv;
-            s[u] = 0.f;
-        }
-        for (int k = f0; k < f0 + half; k += 4) {
-            const float pv[4] = {pi_row[k], pi_row[k + 1], pi_row[k + 2], pi_row[k + 3]};
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const float4 uv = *reinterpret_cast<const float4*>(pu_w + u * d + k);
-                const float c0 = (uv.x + pv[0]) - mean[u], c1 = (uv.y + pv[1]) - mean[u], c2 = (uv.z + pv[2]) - mean[u], c3 = (uv.w + pv[3]) - mean[u];
-                s[u] += c0 * c0, s[u] += c1 * c1, s[u] += c2 * c2, s[u] += c3 * c3;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-            s[u] += __shfl_xor(s[u], 32, 64);
-            rstd[u] = 1.f / sqrtf(s[u] * inv + a.eps);
-        }
-    }
-    // layer 1: K = d inputs formed on the fly, M = d / 2 outputs
-    const int K = d, M = d >> 1;
-    const float* __restrict__ W = a.w[1];
-    f32x16 acc[UW][NB];
-    bias_init<UW, NB>(acc, a.b[1], M, h);
-    float st[NB * 4];
-    chunk_fetch<NB>(st, W, M, K, 0, tid);
-    for (int k0 = 0; k0 < K; k0 += NCF_CHUNK) {
-        __syncthreads();                                     // every wave is done with the previous chunk
-        chunk_store<NB>(st, ws, tid);
-        __syncthreads();
-        if (k0 + NCF_CHUNK < K) chunk_fetch<NB>(st, W, M, K, k0 + NCF_CHUNK, tid);
-        const int kc = min(NCF_CHUNK, K - k0);
-        for (int s0 = 0; s0 < kc; s0 += 8)                   // (kc is 16 or 32)
-#pragma unroll
-        for (int s = s0; s < s0 + 8; s += 2) {
-            const int k = s + h;
-            const float piv = pi_row[k0 + k], ga = g0_s[k0 + k], be = b0_s[k0 + k];
-            float wa[NB];
-#pragma unroll
-            for (int mb = 0; mb < NB; ++mb) wa[mb] = ws[(mb * 32 + p) * NCF_CHUNK_STRIDE + k];
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const float hv = relu_keep_nan((((pu_w[u * d + k0 + k] + piv) - mean[u]) * rstd[u]) * ga + be);
-#pragma unroll
-                for (int mb = 0; mb < NB; ++mb) acc[u][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[mb], hv, acc[u][mb], 0, 0, 0);
-            }
-        }
-    }
-    nms_ln_relu<UW, NB>(acc, a.gamma[1], a.beta[1], M, a.eps, h);
-    nms_run_tail<UW, NB>(acc, 2, a, t, ws, tid);
-}
-
 // num_layers = 1: logit = predict(relu(LN(Pu[r] + Pi[j]))) (+ GMF), d = factor <= 64; one pair a thread, items on the lanes
-__global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_l1_kernel(NmsArgs a) {
+__global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_l1_kernel(NcfArgs a) {
     const int64_t j = (int64_t)(blockIdx.x % (unsigned)a.item_tiles) * NCF_THREADS + threadIdx.x;
     const int r = (int)(blockIdx.x / (unsigned)a.item_tiles);
     if (j >= a.n_items || r >= a.n) return;
@@ -288,7 +60,7 @@ __global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_l1_kernel(NmsArgs
 }
 
 // kind GMF: one item a thread with its gi row in registers, NMS_GMF_USERS users a workgroup
-template <int F> __global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_gmf_kernel(NmsArgs a) {
+template <int F> __global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_gmf_kernel(NcfArgs a) {
     const int64_t j = (int64_t)(blockIdx.x % (unsigned)a.item_tiles) * NCF_THREADS + threadIdx.x;
     const int r0 = (int)(blockIdx.x / (unsigned)a.item_tiles) * NMS_GMF_USERS;
     if (j >= a.n_items) return;
@@ -312,17 +84,6 @@ template <int F> __global__ __launch_bounds__(NCF_THREADS) void ncf_model_score_
         }
         a.scores[(int64_t)r * a.row_stride + j] = s;
     }
-}
-
-template <int UW, int NB> static int nms_launch(const NmsArgs& a, hipStream_t st) {
-    const int TU = NCF_WAVES * UW;
-    const size_t smem = sizeof(float) * ((size_t)NCF_ITEMS * (a.d + 1) + (size_t)TU * a.d + (size_t)NCF_ITEMS * (a.factor + 1) + (size_t)2 * a.d +
-                                         (size_t)32 * NB * NCF_CHUNK_STRIDE);
-    const int64_t grid = (int64_t)a.item_tiles * ((a.n + TU - 1) / TU);
-    PMGT_CHECK(grid <= 0x7FFFFFFF, -2, "pmgt_ncf_model_score: %lld workgroups exceed the grid limit; split the users", (long long)grid);
-    PMGT_SMEM_ATTR(((const void*)ncf_model_score_kernel<UW, NB>), (int)smem);
-    hipLaunchKernelGGL((ncf_model_score_kernel<UW, NB>), dim3((unsigned)grid), dim3(NCF_THREADS), smem, st, a);
-    return 0;
 }
 
 }  // namespace pmgt
@@ -372,7 +133,7 @@ extern "C" int pmgt_ncf_model_score(const pmgt_ncf_model_head* head, const float
         hd.user_num = head->user_num;
         return pmgt_ncf_score(&hd, pu, pi, users, n, n_items, scores, row_stride, stream);
     }
-    NmsArgs a = {};
+    NcfArgs a = {};
     for (int i = 0; mlp && i < L; ++i) {
         a.w[i] = head->weight[i], a.b[i] = head->bias[i];
         a.gamma[i] = head->gamma[i], a.beta[i] = head->beta[i];
@@ -408,14 +169,8 @@ extern "C" int pmgt_ncf_model_score(const pmgt_ncf_model_head* head, const float
         const int64_t grid = (int64_t)a.item_tiles * n;
         PMGT_CHECK(grid <= 0x7FFFFFFF, -2, "%s: %lld workgroups exceed the grid limit; split the users", who, (long long)grid);
         hipLaunchKernelGGL(ncf_model_score_l1_kernel, dim3((unsigned)grid), dim3(NCF_THREADS), 0, st, a);
-    } else {
-        a.item_tiles = (int)((n_items + NCF_ITEMS - 1) / NCF_ITEMS);
-        int rc;
-        // blocks of layer 1's output; users per wave: two at the widest layer (128 accumulator registers), four below
-        if (d > 128) rc = nms_launch<2, 4>(a, st);
-        else if (d > 64) rc = nms_launch<4, 2>(a, st);
-        else rc = nms_launch<4, 1>(a, st);
-        if (rc) return rc;
+    } else if (int rc = ncf_tile_launch<true>(who, a, st)) {
+        return rc;
     }
     PMGT_LAUNCH_OK();
     return 0;

@@ -6,6 +6,7 @@ materialising pair rows (pmgt_ncf_score), and a second kernel selects per row (p
 THE ORDER is that of the ranking metrics: descending `score_key`, and among equal keys THE LOWER ITEM INDEX FIRST.
 
 The pure-numpy part (topk_host, exclusion_csr) needs no GPU; the head (its shape, the covered heads, ncf_head_host) is stated in ncf_head.py."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -91,12 +92,60 @@ def topk_host(scores, k: int, indptr=None, items=None, users=None):
     return out_items, out_scores, flags
 
 
+# ---- the checks the whole-catalogue drivers share (recommend, evaluate_catalogue, similar_items, evaluate_neighbours) -------------------------
+def check_impl(impl) -> str:
+    if impl not in ("host", "device"):
+        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    return impl
+
+
+def check_batch(batch, n_ids: int, n_items: int, who: str, name: str = "batch_users") -> int:
+    """The ids per launch from the caller's `batch_users` / `batch_items` (`name`): None picks default_batch_users."""
+    if batch is not None and (not isinstance(batch, (int, np.integer)) or isinstance(batch, bool) or batch < 1):
+        raise ValueError(f"{who}: {name} = {batch!r} must be a positive integer or None")
+    return default_batch_users(n_ids, n_items) if batch is None else int(min(batch, n_ids, NCF_MAX_USERS))
+
+
+def refuse_nan(who: str, n_nan: int, n_ids: int, what: str) -> None:
+    """`what`: "users" or "items", the ids that were scored."""
+    if n_nan:
+        raise ValueError(f"{who}: {n_nan} of {n_ids} {what} have a NaN score among their eligible items")
+
+
 # ---- device side ------------------------------------------------------------------------------------------------------------------------------
-class NcfScorer:
+class CatalogueScorer:
+    """What select_device and catalogue_eval.rank_device need of a scorer: `device`, `n_items` (set by the subclass's constructor) and
+    score(ids, out=None): ids int64 [n] on the device (the caller checks their range on the host) -> scores fp32 [n, row_stride] with the
+    score of (ids[r], item j) at [r, j]; `out` (fp32, contiguous, [>= n, row_stride >= I]) is written in place and entries [r, I ..) are
+    left.  A subclass names its entry (`entry`, the prefix of the messages) and its ids (`ids_name`) and launches in
+    _launch(ids, n, out).  `max_ids`: the upper bound on n that is refused here; None leaves it to the entry (RuntimeError)."""
+    entry = None
+    ids_name = "users"
+    place = "the table's device"
+    max_ids = None
+
+    def score(self, ids, out=None):
+        import torch
+        n = int(ids.shape[0])
+        if ids.dtype != torch.int64 or ids.dim() != 1 or ids.device != self.device or not ids.is_contiguous() or n < 1 \
+                or (self.max_ids is not None and n > self.max_ids):
+            span = "n >= 1" if self.max_ids is None else f"1 .. {self.max_ids}"
+            raise ValueError(f"{self.entry}: {self.ids_name} must be a contiguous int64 tensor [{span}] on {self.place}")
+        if out is None:
+            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
+                or out.device != self.device:
+            raise ValueError(f"{self.entry}: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on {self.place}")
+        self._launch(ids, n, out)
+        return out
+
+
+class NcfScorer(CatalogueScorer):
     """The fused head over one item table: NcfScorer(weights, table) splits layer 0 and computes the per-item half Pi = table W0e^T + b0
     once; score(users) computes the per-user half Pu = U_mlp[users] W0u^T (a torch matmul: plumbing) and launches pmgt_ncf_score.
     `weights`: the head's parameters as contiguous fp32 DEVICE tensors keyed like the state_dict (a PMGT_NCF's own state_dict serves);
     `table` [I, d] fp32 on the same device.  Nothing in here copies to the host or waits for the device."""
+    entry = "ncf_score"
 
     def __init__(self, weights: dict, table):
         import torch
@@ -113,7 +162,7 @@ class NcfScorer:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != table.device:
                 raise ValueError(f"ncf_score: {key} must be an fp32 tensor on the table's device")
             self.w[key] = t.detach().contiguous()
-        self.n_items = int(table.shape[0])
+        self.device, self.n_items = table.device, int(table.shape[0])
         self.user_num = int(self.w["mlp_user_embeddings.weight"].shape[0])
         w0 = self.w["mlp_layers.0.linear.weight"]
         if tuple(w0.shape) != (self.d, 2 * self.d):
@@ -132,30 +181,19 @@ class NcfScorer:
             h.gmf_user, h.gmf_item = self.w["gmf_user_embeddings.weight"].data_ptr(), self.w["gmf_item_embeddings.weight"].data_ptr()
         self._head = h
 
-    def score(self, users, out=None):
-        """users int64 [n] on the device (ids in [0, user_num): the caller checks them on the host) -> scores fp32 [n, row_stride] with the logit
-        of (users[r], item j) at [r, j]; `out` (fp32, contiguous, [>= n, row_stride >= I]) is written in place and entries [r, I ..) are left."""
-        import torch
-        n = int(users.shape[0])
-        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.pi.device or not users.is_contiguous() or n < 1:
-            raise ValueError("ncf_score: users must be a contiguous int64 tensor [n >= 1] on the table's device")
-        if out is None:
-            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.pi.device)
-        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
-                or out.device != self.pi.device:
-            raise ValueError(f"ncf_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
+    def _launch(self, users, n, out):
         pu = self.w["mlp_user_embeddings.weight"].index_select(0, users) @ self._w0u_t
         _lib.check(self.lib.pmgt_ncf_score(C.byref(self._head), pu.data_ptr(), self.pi.data_ptr(), users.data_ptr(), n, self.n_items,
                                            out.data_ptr(), int(out.shape[1]), _lib.stream()))
-        return out
 
 
-class NcfModelScorer:
+class NcfModelScorer(CatalogueScorer):
     """NcfScorer for the reference's stand-alone NCF class (ncf.py): the fused eval-mode head with or without LayerNorm, kinds MLP, GMF,
     NeuMF-end and NeuMF-pre (scored as NeuMF-end), by pmgt_ncf_model_score.  `weights`: the model's parameters as fp32 DEVICE tensors keyed
     like its state_dict (a whole state_dict serves: pass kind=, which a state_dict alone does not tell); `table` [I, d] fp32 on the same
     device stands in for embed_item_MLP.weight (None: that tensor).  Pi = table W0e^T + b0 is computed once; score(users) computes Pu and
     launches.  Kind GMF has no Pi / Pu and refuses a `table`.  Nothing in here copies to the host or waits for the device."""
+    entry = "ncf_model_score"
 
     def __init__(self, weights: dict, table=None, kind: str = None, layer_norm_eps: float = 1e-12):
         import torch
@@ -215,25 +253,14 @@ class NcfModelScorer:
         self._user_mlp = self.w[M.USER_MLP] if mlp else None
         self._head = h
 
-    def score(self, users, out=None):
-        """NcfScorer.score's contract: users int64 [n] on the device -> scores fp32 [n, row_stride]; `out` is written in place."""
-        import torch
-        n = int(users.shape[0])
-        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.device or not users.is_contiguous() or n < 1:
-            raise ValueError("ncf_model_score: users must be a contiguous int64 tensor [n >= 1] on the table's device")
-        if out is None:
-            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
-        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
-                or out.device != self.device:
-            raise ValueError(f"ncf_model_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
+    def _launch(self, users, n, out):
         pu = self._user_mlp.index_select(0, users) @ self._w0u_t if self.pi is not None else None
         _lib.check(self.lib.pmgt_ncf_model_score(C.byref(self._head), pu.data_ptr() if pu is not None else 0,
                                                  self.pi.data_ptr() if pu is not None else 0, users.data_ptr(), n, self.n_items,
                                                  out.data_ptr(), int(out.shape[1]), _lib.stream()))
-        return out
 
 
-class DcnScorer:
+class DcnScorer(CatalogueScorer):
     """NcfModelScorer for the Deep & Cross Network (dcn.py): the fused eval-mode model by pmgt_dcn_score, the deep tower on the NCF scoring
     tile and the collapsed cross net (dcn_head.py's header) in its epilogue.  `weights_or_flat`: the model's parameters as fp32 DEVICE
     tensors keyed like its state_dict (a whole state_dict serves; they are gathered into one flat buffer of dcn_layout once), or a pair
@@ -242,6 +269,7 @@ class DcnScorer:
     item_embeddings.weight (None: that tensor).  Built once: Pi = table W0i^T + b0, the item rows' scalars (pmgt_dcn_score_rows) and the 2 C
     constants K_c, B_c (torch: plumbing); they are a snapshot of the parameters at construction.  score(users) gathers the user rows,
     computes Pu and their scalars and launches.  Nothing in here copies to the host or waits for the device."""
+    entry, place = "dcn_score", "the parameters' device"
 
     def __init__(self, weights_or_flat, table=None, layer_norm_eps: float = 1e-12):
         import torch
@@ -310,24 +338,13 @@ class DcnScorer:
         _lib.check(self.lib.pmgt_dcn_score_rows(C.byref(self._head), table.data_ptr(), int(table.shape[0]), half, out.data_ptr(), _lib.stream()))
         return out
 
-    def score(self, users, out=None):
-        """NcfScorer.score's contract: users int64 [n] on the device -> scores fp32 [n, row_stride]; `out` is written in place."""
-        import torch
-        n = int(users.shape[0])
-        if users.dtype != torch.int64 or users.dim() != 1 or users.device != self.device or not users.is_contiguous() or n < 1:
-            raise ValueError("dcn_score: users must be a contiguous int64 tensor [n >= 1] on the parameters' device")
-        if out is None:
-            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
-        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
-                or out.device != self.device:
-            raise ValueError(f"dcn_score: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the parameters' device")
+    def _launch(self, users, n, out):
         rows = self._user_table.index_select(0, users)
         pu = rows @ self._w0u_t
         user_rows = self.rows(rows, 0)
         _lib.check(self.lib.pmgt_dcn_score(C.byref(self._head), pu.data_ptr(), self.pi.data_ptr(), user_rows.data_ptr(), self.item_rows.data_ptr(),
                                            self._consts.data_ptr(), users.data_ptr(), n, self.n_items, out.data_ptr(), int(out.shape[1]),
                                            _lib.stream()))
-        return out
 
 
 class TopkRows:
@@ -369,6 +386,31 @@ class TopkRows:
                                            self.user_num if excl else 0, len(self._items) if excl else 0, self._ws.data_ptr(),
                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _lib.stream()))
         return out
+
+
+def select_device(scorer: CatalogueScorer, ids, batch: int, k: int, indptr, excl, id_num: int):
+    """The selection pass on the device: per batch of `ids` (int64 numpy, checked by the caller) scorer.score then TopkRows.select, with the
+    exclusion CSR (indptr, excl) over `id_num` ids.  Everything is uploaded and built before the first score; nothing is copied to the host
+    and nothing waits inside the loop; one copy at the end fetches -> (items int32 [n, k], scores fp32 [n, k], flags uint32 [n]) as numpy."""
+    import torch
+    dev, n, n_items = scorer.device, len(ids), scorer.n_items
+    picker = TopkRows(dev, batch, n_items, k, indptr, excl, id_num)
+    ids_d = torch.from_numpy(ids).to(dev)
+    out = (torch.empty(n, k, dtype=torch.int32, device=dev), torch.empty(n, k, dtype=torch.float32, device=dev),
+           torch.empty(n, dtype=torch.int32, device=dev))
+    work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
+    for lo in range(0, n, batch):
+        hi = min(lo + batch, n)
+        scorer.score(ids_d[lo:hi], out=work)
+        picker.select(work[: hi - lo], ids_d[lo:hi], out=tuple(t[lo:hi] for t in out))
+    items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
+    return items, scores, flags.view(np.uint32)
+
+
+def select_host(score_rows, ids, batch: int, k: int, indptr, excl):
+    """The yardstick of select_device: score_rows(ids) -> numpy [m, I] on batches of `ids`, then topk_host; select_device's result."""
+    parts = [topk_host(score_rows(ids[lo: lo + batch]), k, indptr, excl, ids[lo: lo + batch]) for lo in range(0, len(ids), batch)]
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
 
 def default_batch_users(n_users: int, n_items: int) -> int:
@@ -422,8 +464,8 @@ def dcn_host_scores(model, table, users, pair_chunk: int = 1 << 18) -> np.ndarra
 class ModelDispatch:
     """What recommend() and evaluate_catalogue() need to know of the model class, stated once: a PMGT_NCF (encoder + head over an encoded
     catalogue table), the reference's stand-alone NCF class (ncf.py) or a dcn.DCN.  In the caller's order: check_covered() (impl="device":
-    the existing check_*_covered of the class), resolve_table() (the default table, check_item_table; sets .dev and .table), then inside the
-    caller's eval-mode block host_scores(users) or scorer().  `who` names the caller in the messages."""
+    the existing check_*_covered of the class), resolve_table() (the default table, check_item_table; sets .dev and .table), then inside
+    `with eval_mode(impl):` host_scores(users) or scorer().  `who` names the caller in the messages."""
 
     def __init__(self, model, who: str):
         from .ncf import NCF
@@ -461,19 +503,25 @@ class ModelDispatch:
         else:
             if table is None:
                 from .evaluation import encode_catalogue
-                was_training = model.training
-                model.eval()
-                try:
+                with self.eval_mode("host"):
                     table = encode_catalogue(model, sampler, threads=threads, seed=seed)
-                finally:
-                    model.train(was_training)
             dev = model.engine.device
             check_item_table(table, n_items, model.config.hidden_size, dev, who)
         self.dev, self.table = dev, table
 
-    def sets_mode(self, impl: str) -> bool:
-        """Whether the caller puts the model into eval mode around the scoring (and restores the mode it had)."""
-        return impl == "host" or self.standalone
+    @contextlib.contextmanager
+    def eval_mode(self, impl: str):
+        """The model in eval mode around the scoring, the mode it had restored behind it (impl="device" on a PMGT_NCF reads the weights
+        only: its mode is left alone)."""
+        model = self.model
+        was_training, set_mode = model.training, impl == "host" or self.standalone
+        if set_mode:
+            model.eval()
+        try:
+            yield
+        finally:
+            if set_mode:
+                model.train(was_training)
 
     def host_scores(self, users) -> np.ndarray:
         """impl="host": the full score rows [U, I] of `users` as numpy."""
@@ -503,9 +551,8 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     A user with FEWER THAN k eligible items gets item -1 and score -inf in the slots past them; that is not an error.
     table: a catalogue table of encode_catalogue to reuse; None encodes it once, in eval mode, and restores the caller's train / eval mode.
     batch_users: users per launch; None picks the largest batch whose [batch, I] fp32 score rows stay within 256 MiB.
-    impl="device": pmgt_ncf_score then pmgt_topk_rows per batch; nothing is copied to the host and nothing waits inside the loop, one copy
-      at the end fetches items, scores and flags.  impl="host": the yardstick -- `model.head` on chunks of pair rows, the full score rows
-      copied out, topk_host.
+    impl="device": select_device with the class's fused scorer (pmgt_ncf_score then pmgt_topk_rows per batch).  impl="host": the
+      yardstick -- select_host over `model.head` on chunks of pair rows.
     model may also be the reference's stand-alone NCF class (ncf.py; any kind, with or without LayerNorm): `sampler` is then unused (pass
       None), the device is that of the parameters, `table` defaults to model.embed_item_MLP.weight (a trainer's table serves, no copy; kind
       GMF reads none and refuses one), impl="device" is NcfModelScorer + TopkRows in the same loop, and impl="host" on a CPU model needs no GPU.
@@ -515,8 +562,7 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
       impl="host" is model.forward on chunks of pair rows + topk_host and needs no GPU on a CPU model.
     Raises ValueError for users or excluded ids outside the model's tables, k outside [1, 1024], a user with a NaN score among their
     eligible items (naming how many users), and -- impl="device" only -- a head shape the kernel does not cover."""
-    if impl not in ("host", "device"):
-        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    check_impl(impl)
     k = check_k(k)
     users = np.ascontiguousarray(users, dtype=np.int64)
     if users.ndim != 1 or len(users) < 1:
@@ -527,36 +573,13 @@ def recommend(model, sampler, users, k: int = 20, exclude=None, batch_users: int
     dispatch = ModelDispatch(model, "recommend")
     if impl == "device":
         dispatch.check_covered()
-    if batch_users is not None and (not isinstance(batch_users, (int, np.integer)) or batch_users < 1):
-        raise ValueError(f"recommend: batch_users = {batch_users!r} must be a positive integer or None")
-    n_users, n_items = len(users), model.item_num
-    batch = default_batch_users(n_users, n_items) if batch_users is None else int(min(batch_users, n_users, NCF_MAX_USERS))
+    batch = check_batch(batch_users, len(users), model.item_num, "recommend")
     dispatch.resolve_table(sampler, table, threads, seed)
-    dev = dispatch.dev
-    was_training, set_mode = model.training, dispatch.sets_mode(impl)
-    if set_mode:
-        model.eval()
-    try:
+    with dispatch.eval_mode(impl):
         if impl == "host":
-            items, scores, flags = topk_host(dispatch.host_scores(users), k, indptr, excl, users)
+            items, scores, flags = select_host(dispatch.host_scores, users, batch, k, indptr, excl)
         else:
             with torch.no_grad():
-                scorer = dispatch.scorer()
-                picker = TopkRows(dev, batch, n_items, k, indptr, excl, model.user_num)
-                users_d = torch.from_numpy(users).to(dev)
-                out = (torch.empty(n_users, k, dtype=torch.int32, device=dev), torch.empty(n_users, k, dtype=torch.float32, device=dev),
-                       torch.empty(n_users, dtype=torch.int32, device=dev))
-                work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
-                for lo in range(0, n_users, batch):
-                    hi = min(lo + batch, n_users)
-                    scorer.score(users_d[lo:hi], out=work)
-                    picker.select(work[: hi - lo], users_d[lo:hi], out=tuple(t[lo:hi] for t in out))
-                items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
-            flags = flags.view(np.uint32)
-    finally:
-        if set_mode:
-            model.train(was_training)
-    n_nan = int(np.count_nonzero(flags & TOPK_FLAG_NAN))
-    if n_nan:
-        raise ValueError(f"recommend: {n_nan} of {n_users} users have a NaN score among their eligible items")
+                items, scores, flags = select_device(dispatch.scorer(), users, batch, k, indptr, excl, model.user_num)
+    refuse_nan("recommend", int(np.count_nonzero(flags & TOPK_FLAG_NAN)), len(users), "users")
     return items.astype(np.int64), scores

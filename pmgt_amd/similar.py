@@ -14,11 +14,12 @@ import numpy as np
 
 from . import _lib
 from ._lib import ITEM_SIM_MAX_D, NCF_MAX_USERS, TOPK_FLAG_NAN
-from .catalogue_eval import (CatalogueMetrics, HeldoutRanks, catalogue_metrics_host, count_common_pairs, heldout_ranks_host,
-                             summarize_catalogue)
+from .catalogue_eval import (CatalogueMetrics, HeldoutRanks, catalogue_metrics_host, count_common_pairs, heldout_queries,  # noqa: F401
+                             heldout_ranks_host, rank_device, rank_host, summarize_catalogue)
 from .graph import CSRGraph
 from .pair_train import check_ids
-from .recommend import TopkRows, check_k, default_batch_users, exclusion_csr, topk_host
+from .recommend import (CatalogueScorer, TopkRows, check_batch, check_impl, check_k, default_batch_users, exclusion_csr,  # noqa: F401
+                        refuse_nan, select_device, select_host, topk_host)
 
 METRICS = ("cosine", "dot")
 
@@ -163,9 +164,10 @@ def device_table(table, who: str):
     return table.detach().contiguous()
 
 
-class ItemSimScorer:
+class ItemSimScorer(CatalogueScorer):
     """pmgt_item_sim_score over one table [I, d] (fp32, contiguous, on a GPU), read in place: ItemSimScorer(table) computes the inverse norms
     once (pmgt_item_sim_norms; metric "dot" has none); score(queries) launches.  Nothing in here copies to the host or waits for the device."""
+    entry, ids_name, max_ids = "item_sim", "queries", NCF_MAX_USERS
 
     def __init__(self, table, metric: str = "cosine", eps: float = 1e-12):
         import torch
@@ -185,29 +187,9 @@ class ItemSimScorer:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.pmgt_item_sim_norms(self.table.data_ptr(), self.n_items, self.d, eps, self.inv_norm.data_ptr(), _lib.stream()))
 
-    def score(self, queries, out=None):
-        """NcfScorer.score's contract: queries int64 [n] on the device (ids in [0, I): the caller checks them on the host) -> scores fp32
-        [n, row_stride] with s(queries[r], j) at [r, j]; `out` (fp32, contiguous, [>= n, row_stride >= I]) is written in place and entries
-        [r, I ..) are left."""
-        import torch
-        n = int(queries.shape[0])
-        if queries.dtype != torch.int64 or queries.dim() != 1 or queries.device != self.device or not queries.is_contiguous() \
-                or not 1 <= n <= NCF_MAX_USERS:
-            raise ValueError(f"item_sim: queries must be a contiguous int64 tensor [1 .. {NCF_MAX_USERS}] on the table's device")
-        if out is None:
-            out = torch.empty(n, self.n_items, dtype=torch.float32, device=self.device)
-        if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < n or out.shape[1] < self.n_items \
-                or out.device != self.device:
-            raise ValueError(f"item_sim: out must be a contiguous fp32 tensor [>= {n}, >= {self.n_items}] on the table's device")
+    def _launch(self, queries, n, out):
         _lib.check(self.lib.pmgt_item_sim_score(self.table.data_ptr(), 0 if self.inv_norm is None else self.inv_norm.data_ptr(), queries.data_ptr(),
                                                 n, self.n_items, self.d, out.data_ptr(), int(out.shape[1]), _lib.stream()))
-        return out
-
-
-def _batch(batch_items, n_queries: int, n_items: int, who: str) -> int:
-    if batch_items is not None and (not isinstance(batch_items, (int, np.integer)) or isinstance(batch_items, bool) or batch_items < 1):
-        raise ValueError(f"{who}: batch_items = {batch_items!r} must be a positive integer or None")
-    return default_batch_users(n_queries, n_items) if batch_items is None else int(min(batch_items, n_queries, NCF_MAX_USERS))
 
 
 def similar_items(table, items=None, k: int = 20, metric: str = "cosine", exclude=None, exclude_self: bool = True, batch_items: int = None,
@@ -221,12 +203,10 @@ def similar_items(table, items=None, k: int = 20, metric: str = "cosine", exclud
       id v = row v - 2); built into the CSR once.  exclude_self adds (i, i) for every item.
     A query with FEWER THAN k eligible items gets item -1 and score -inf in the slots past them; that is not an error.
     batch_items: queries per launch; None picks the largest batch whose [batch, I] fp32 score rows stay within 256 MiB.
-    impl="device": ItemSimScorer.score then TopkRows.select per batch; nothing is copied to the host and nothing waits inside the loop, one
-      copy at the end fetches items, scores and flags.  impl="host": the yardstick -- item_sim_host + topk_host; needs no GPU.
+    impl="device": recommend.select_device with an ItemSimScorer.  impl="host": the yardstick -- select_host over item_sim_host; needs no GPU.
     Raises ValueError for ids outside the table, k outside [1, 1024], d outside [1, 1024], an unknown metric or impl, and a query with a
     NaN score among its eligible items (naming how many)."""
-    if impl not in ("host", "device"):
-        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    check_impl(impl)
     check_metric(metric)
     k = check_k(k)
     n_items, _ = check_table(table, "similar_items")
@@ -235,32 +215,16 @@ def similar_items(table, items=None, k: int = 20, metric: str = "cosine", exclud
         raise ValueError(f"similar_items: items {items.shape} must be [Q >= 1]")
     check_ids("items", items, n_items, "similar_items")
     indptr, excl = item_exclusion_csr(exclude, n_items, exclude_self)
-    n_q = len(items)
-    batch = _batch(batch_items, n_q, n_items, "similar_items")
+    batch = check_batch(batch_items, len(items), n_items, "similar_items", "batch_items")
     if impl == "host":
         t = host_table(table)
-        parts = [topk_host(item_sim_host(t, items[lo: lo + batch], metric), k, indptr, excl, items[lo: lo + batch]) for lo in range(0, n_q, batch)]
-        found, scores, flags = (np.concatenate([p[i] for p in parts]) for i in range(3))
+        found, scores, flags = select_host(lambda q: item_sim_host(t, q, metric), items, batch, k, indptr, excl)
     else:
         import torch
         table_d = device_table(table, "similar_items")
-        dev = table_d.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            scorer = ItemSimScorer(table_d, metric)
-            picker = TopkRows(dev, batch, n_items, k, indptr, excl, n_items)
-            items_d = torch.from_numpy(items).to(dev)
-            out = (torch.empty(n_q, k, dtype=torch.int32, device=dev), torch.empty(n_q, k, dtype=torch.float32, device=dev),
-                   torch.empty(n_q, dtype=torch.int32, device=dev))
-            work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
-            for lo in range(0, n_q, batch):
-                hi = min(lo + batch, n_q)
-                scorer.score(items_d[lo:hi], out=work)
-                picker.select(work[: hi - lo], items_d[lo:hi], out=tuple(t[lo:hi] for t in out))
-            found, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
-        flags = flags.view(np.uint32)
-    n_nan = int(np.count_nonzero(flags & TOPK_FLAG_NAN))
-    if n_nan:
-        raise ValueError(f"similar_items: {n_nan} of {n_q} items have a NaN score among their eligible items")
+        with torch.no_grad(), torch.cuda.device(table_d.device):
+            found, scores, flags = select_device(ItemSimScorer(table_d, metric), items, batch, k, indptr, excl, n_items)
+    refuse_nan("similar_items", int(np.count_nonzero(flags & TOPK_FLAG_NAN)), len(items), "items")
     return found.astype(np.int64), scores
 
 
@@ -274,68 +238,33 @@ def evaluate_neighbours(table, heldout, exclude=None, ks=(10, 20), metric: str =
       query a and a a held-out item of query b; duplicates are dropped.  The evaluated items are those with at least one, ascending.
     exclude: typically the training graph -- a CSRGraph (node id v = row v - 2), (query item, item) pairs or a ready (indptr, items) CSR pair
       over item ids; None excludes nothing.  exclude_self adds (i, i) for every item.
-    table, metric, batch_items, impl: similar_items'.  impl="device": per batch ItemSimScorer.score then HeldoutRanks.rank; nothing is
-      copied to the host and nothing waits inside the loop; after it one reduce and one small copy.  impl="host": the yardstick --
-      item_sim_host, heldout_ranks_host, catalogue_metrics_host; needs no GPU.
+    table, metric, batch_items, impl: similar_items'.  impl="device": catalogue_eval.rank_device with an ItemSimScorer.  impl="host": the
+      yardstick -- rank_host over item_sim_host; needs no GPU.
     per_item=True: returns (result, dict) with items (the evaluated queries), n_pos, ndcg[k], recall[k], hit[k], rr per evaluated item, and
       ranks with the held-out CSR (indptr, heldout) they align with.
     Raises ValueError for ids outside the table, a held-out pair that is also excluded (naming how many), a query with a NaN score among
     its eligible items (naming how many), an empty held-out set, d outside [1, 1024] and an unknown metric or impl."""
     from .metrics import check_ks
-    if impl not in ("host", "device"):
-        raise ValueError(f"impl={impl!r}: expected 'host' or 'device'")
+    check_impl(impl)
     check_metric(metric)
     ks = check_ks(ks)
     n_items, _ = check_table(table, "evaluate_neighbours")
-    h_indptr, h_items = edges_csr(heldout, n_items, True, "heldout")
-    n_pairs = len(h_items)
-    if n_pairs < 1:
-        raise ValueError("evaluate_neighbours: the held-out set is empty")
-    indptr, excl = item_exclusion_csr(exclude, n_items, exclude_self)
-    n_both = count_common_pairs((h_indptr, h_items), (indptr, excl), n_items)
-    if n_both:
-        raise ValueError(f"evaluate_neighbours: {n_both} of {n_pairs} held-out pairs are also excluded")
-    items = np.nonzero(np.diff(h_indptr) > 0)[0].astype(np.int64)
-    n_q = len(items)
-    batch = _batch(batch_items, n_q, n_items, "evaluate_neighbours")
+    held = edges_csr(heldout, n_items, True, "heldout")
+    exclusion, items = heldout_queries("evaluate_neighbours", held, lambda: item_exclusion_csr(exclude, n_items, exclude_self), n_items)
+    batch = check_batch(batch_items, len(items), n_items, "evaluate_neighbours", "batch_items")
     if impl == "host":
         t = host_table(table)
-        ranks = np.zeros(n_pairs, dtype=np.int32)
-        flags = np.zeros(n_q, dtype=np.uint32)
-        for lo in range(0, n_q, batch):
-            q = items[lo: lo + batch]
-            r, flags[lo: lo + batch] = heldout_ranks_host(item_sim_host(t, q, metric), q, (h_indptr, h_items), (indptr, excl))
-            ranks = np.maximum(ranks, r)                     # (a call fills the places of its own queries, the others stay 0)
-        rec = catalogue_metrics_host(ranks, h_indptr, ks)
-        sums, n_nan = rec.pop("sums"), int(np.count_nonzero(flags & TOPK_FLAG_NAN))
-        rec.pop("users")
+        sums, rec, ranks = rank_host(lambda q: item_sim_host(t, q, metric), items, batch, held, exclusion, ks)
     else:
         import torch
         table_d = device_table(table, "evaluate_neighbours")
-        dev = table_d.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            scorer = ItemSimScorer(table_d, metric)
-            ranker = HeldoutRanks(dev, n_items, h_indptr, h_items, n_items, indptr, excl)
-            reducer = CatalogueMetrics(dev, n_q, ks)
-            items_d = torch.from_numpy(items).to(dev)
-            flags_d = torch.zeros(n_q, dtype=torch.int32, device=dev)
-            work = torch.empty(batch, n_items, dtype=torch.float32, device=dev)
-            for lo in range(0, n_q, batch):
-                hi = min(lo + batch, n_q)
-                scorer.score(items_d[lo:hi], out=work)
-                ranker.rank(work[: hi - lo], items_d[lo:hi], flags_d[lo:hi])
-            reducer.reduce(ranker, items_d, flags_d)
-            sums = reducer.statistic()                       # the one small copy out: after the loop
-            n_nan = sums["n_nan"]
-            if per_item:
-                rec = reducer.per_user()
-                rec["n_pos"] = np.diff(h_indptr)[items]
-                ranks = ranker.ranks.cpu().numpy()
-    if n_nan:
-        raise ValueError(f"evaluate_neighbours: {n_nan} of {n_q} items have a NaN score among their eligible items")
-    result = summarize_catalogue(sums, n_q, n_pairs, ks)
+        with torch.no_grad(), torch.cuda.device(table_d.device):
+            sums, rec, ranks = rank_device(ItemSimScorer(table_d, metric), items, batch, held, exclusion, n_items, ks, per_item)
+    refuse_nan("evaluate_neighbours", sums["n_nan"], len(items), "items")
+    result = summarize_catalogue(sums, len(items), len(held[1]), ks)
     result = {("items" if key == "users" else key): v for key, v in result.items()}
     if not per_item:
         return result
-    rec.update(items=items, ranks=ranks, indptr=h_indptr, heldout=h_items)
+    rec.pop("users")
+    rec.update(items=items, ranks=ranks, indptr=held[0], heldout=held[1])
     return result, rec
