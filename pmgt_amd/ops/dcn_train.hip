@@ -1,10 +1,10 @@
 // The Deep & Cross Network of the reference's click-through experiment (pmgt/dcn/models.py; pmgt_dcn_forward and pmgt_dcn_train_grad of
 // include/pmgt_capi.h, where the formulae stand): logits, or loss, logits and the gradient of the mean BCE-with-logits loss with respect to
 // every trained parameter, both embedding tables included, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for
-// ncf_train.hip's reason: the measured step launches nothing of this.  fp32 end to end; the Linear layers and their gradients run on the exact
-// f32-input MFMA (v_mfma_f32_32x32x2_f32) in the pair-major forms of ncf_train.hip (forward Y^T = W X^T, data dX^T = W^T dY^T, weight
-// dW = dY^T X), everything else is ROW WORK: one wave owns one pair's row (up to D = 512 floats, 8 a lane as two 16-byte pieces) and
-// reduces over it with a shuffle butterfly.
+// ncf_train.hip's reason: the measured step launches nothing of this.  The Linear layers and their gradients are the pair-major products of
+// pair_train_tile.h, which also states the roles rank / zero / weight / rows and the chain policies: Chain::ONE without dropout,
+// Chain::BLOCK in the DROP instantiations, no activation in the epilogue, one row source and no input mask.  Everything else is ROW WORK:
+// one wave owns one pair's row (up to D = 512 floats, 8 a lane as two 16-byte pieces) and reduces over it with a shuffle butterfly.
 //
 // EVERYTHING IS PAIR-MAJOR in the caller's workspace: x0 [n][D], the deep net's y_l = W_l h_l + b_l, h_(l+1), g_l = d loss / d LN_l's
 // output behind the ReLU and dy_l = d loss / d y_l, each [n][D >> (l + 1)]; the cross net's final x^(C) [n][D] and, with LayerNorm, G_c = d loss
@@ -12,21 +12,17 @@
 // states x^(c) themselves are NOT stored: x^(c+1) = ((x0 s_c + x0) - mean) rstd gamma + beta is recomputed from x0 and the statistics by
 // the same sequence of operations wherever it is needed (the file is compiled without contraction, so the bits agree).
 //
-// LAUNCH 1, dcn_pairs_kernel, three roles by block index (the forward entry launches the tiles only, instantiated without the backward):
-//   tile   32 pairs a workgroup of 4 waves.  Gathers x0; deep forward: per layer the MFMA product (the waves share out the 32-feature
-//          blocks) then, per pair row, LayerNorm and ReLU; cross forward per pair row, wave w taking pairs 8 w .. 8 w + 7: the dot with w_c,
-//          x0 s + x0, LayerNorm; the output layer, the loss and dz.  Then back: per deep layer the row pass (ReLU mask, LayerNorm
-//          backward) and the MFMA data gradient, down to d x0's deep part; per pair row the cross chain from layer C - 1 to 0, which adds
-//          its terms in that order, then d x^(0), then the deep part.  A workgroup reads only what it wrote itself, behind a barrier.
-//   rank   the position of every pair in the STABLE order by user id and by item id, counted (n <= 65 536), as ncf_train.hip does.
-//   zero   the gradient rows of the two embedding tables, whole.
-// LAUNCH 2, dcn_grads_kernel, three roles:
-//   weight one workgroup per 32 x 32 block of a layer's dW = dy^T h, 32-pair chunks dealt to the 4 waves in order, added as (w0 + w1) +
-//          (w2 + w3); one more block column against the constant column (1, 0, ..) gives the bias gradient.  The output layer is the
-//          pseudo-layer with dy = [dz, loss of the pair] against [x^(C) ; h_L]: row 0 its weight and bias gradient, row 1 the loss sum.
-//   cols   64 columns a workgroup: gamma, beta and w_c gradients, wave a summing the pairs a, a + 4, .. in order, added the same way.
-//   rows   one wave per position of a stable order; the wave at the start of a run of equal ids adds the run's d x0 halves in pair order.
-// DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+// LAUNCH 1, dcn_pairs_kernel (the forward entry launches the tiles only, instantiated without the backward): the roles rank and zero (the
+// gradient rows of the two embedding tables), and
+//   tile   32 pairs a workgroup of 4 waves.  Gathers x0; deep forward: per layer the MFMA product then, per pair row, LayerNorm and ReLU;
+//          cross forward per pair row, wave w taking pairs 8 w .. 8 w + 7: the dot with w_c, x0 s + x0, LayerNorm; the output layer, the
+//          loss and dz.  Then back: per deep layer the row pass (ReLU mask, LayerNorm backward) and the MFMA data gradient, down to d x0's
+//          deep part; per pair row the cross chain from layer C - 1 to 0, which adds its terms in that order, then d x^(0), then the deep
+//          part.  A workgroup reads only what it wrote itself, behind a barrier.
+// LAUNCH 2, dcn_grads_kernel: the roles weight (the output layer is the pseudo-layer against [x^(C) ; h_L]) and rows (the two halves of
+// d x0), and
+//   cols   64 columns a workgroup: gamma, beta and w_c gradients, wave a summing the pairs a, a + 4, .. in order, added as (w0 + w1) +
+//          (w2 + w3).
 //
 // DROPOUT (pmgt_dcn_train_grad_dropout; the DROP instantiations, which alone read the second kernel argument): the model in training
 // mode, every mask m = 0 or 1 / (1 - p) drawn by the counter-based RNG of csrc/common.h at (site, row = the pair, column = the feature):
@@ -37,19 +33,15 @@
 // kept elements and the factor 1 / (1 - p_l) suffices), ds_c = sum_j g_j m_cj x0_j, d x0 += g (m_c s_c) + g, and the final d x0 is
 // multiplied by m_e before the store.  A site with p = 0 draws nothing; launch 2 runs its DROP instantiation only when a p_cross is > 0.
 // ARITHMETIC OF THE DROP INSTANTIATIONS of launch 1: the row reductions (s_c, the LayerNorm statistics and the sums of its backward, ds_c,
-// the output layer's dots) add exact products in fp64 and round to fp32 once, and an MFMA chain sums each block of 32 k from 0 and adds
-// the blocks (K / 32 + 16 additions deep instead of K / 2).  With ONE pair in a call nothing averages over pairs and the yardstick's
-// fp32 error is that of single BLAS dot products; the in-order sums of the entries without dropout, whose bits are kept, sit at up to
-// 3.8 x that on their own cases and passed 4 x on 7 of 3 936 cases under the masks.  Statistics are stored and only READ by the second
-// launch, so what it recomputes from them agrees as before.
-#include "ncf_head.h"
+// the output layer's dots) add exact products in fp64 and round to fp32 once, for Chain::BLOCK's reason.  Statistics are stored and only
+// READ by the second launch, so what it recomputes from them agrees as before.
+#include "pair_train_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace pmgt {
 
-static constexpr int DC_THREADS = 256, DC_WAVES = 4, DC_TILE = 32, DC_PER_WAVE = DC_TILE / DC_WAVES;
-static constexpr int DC_MAX_DEEP = PMGT_DCN_MAX_DEEP, DC_MAX_CROSS = PMGT_DCN_MAX_CROSS, DC_ZERO_BLOCKS = 1024;
+static constexpr int DC_PER_WAVE = PAIR_TILE / PAIR_WAVES, DC_MAX_DEEP = PMGT_DCN_MAX_DEEP, DC_MAX_CROSS = PMGT_DCN_MAX_CROSS;
 static constexpr int DC_MAX_TASKS = DC_MAX_DEEP + 1, DC_MAX_JOBS = 2 * DC_MAX_DEEP + 3 * DC_MAX_CROSS, DC_MAX_E = 256;
 
 struct DcDeep {
@@ -78,13 +70,6 @@ struct DcPairsArgs {
     int n, E, D, F, L, C, tiles, rank_blocks, zero_blocks;
 };
 
-struct DcTask {
-    const float* a;                         // dy [n][m]
-    const float *b1, *b2;                   // the layer's input [n][w1 + w2] from one or two pair-major sources
-    float *gw, *gb;
-    int m, w1, w2, col_blocks, first, predict;
-};
-
 enum { DC_JOB_SUM = 0, DC_JOB_DEEP_GAMMA = 1, DC_JOB_CROSS_GAMMA = 2, DC_JOB_CROSS_W = 3 };
 
 struct DcJob {
@@ -97,7 +82,7 @@ struct DcJob {
 };
 
 struct DcGradsArgs {
-    DcTask task[DC_MAX_TASKS];
+    PairTask task[DC_MAX_TASKS];
     DcJob job[DC_MAX_JOBS];
     const int64_t *users, *items;
     const int *order_u, *order_i;
@@ -111,17 +96,6 @@ struct DcDrop {
     pmgt_dcn_dropout d;
     signed char job_cross[DC_MAX_JOBS];      // launch 2, per cols job: the cross layer whose mask its recomputation draws again, -1: none
 };
-
-__device__ __forceinline__ float4 dc_ld4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-__device__ __forceinline__ float dc_elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-__device__ __forceinline__ int dc_wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-__device__ __forceinline__ float dc_wave_sum(float x) {      // a butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 // ---- a row of W <= 512 floats (W a multiple of 8) on a wave: lane holds the pieces lane and lane + 64, elements k = 4 j + e ----------
 struct DcRow {
@@ -137,7 +111,7 @@ __device__ __forceinline__ DcRow dc_row(int W, int lane) {
 __device__ __forceinline__ void dc_row_ld(float (&e)[8], const float* p, const DcRow& r) {      // elements outside the row are 0
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const float4 v = dc_ld4(p + r.col[j], r.ok[j]);
+        const float4 v = pair_ld4(p + r.col[j], r.ok[j]);
         e[4 * j] = v.x, e[4 * j + 1] = v.y, e[4 * j + 2] = v.z, e[4 * j + 3] = v.w;
     }
 }
@@ -164,7 +138,7 @@ __device__ __forceinline__ float dc_row_dot(const float (&a)[8], const float (&b
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += a[k] * b[k];
-    return dc_wave_sum(s);
+    return pair_wave_sum(s);
 }
 template <bool HI = false>
 __device__ __forceinline__ float dc_row_sum(const float (&a)[8]) {
@@ -177,7 +151,7 @@ __device__ __forceinline__ float dc_row_sum(const float (&a)[8]) {
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += a[k];
-    return dc_wave_sum(s);
+    return pair_wave_sum(s);
 }
 // u -> (u - mean) rstd, the statistics out
 template <bool HI = false>
@@ -219,7 +193,6 @@ __device__ __forceinline__ void dc_cross_u(float (&u)[8], const float (&x0)[8], 
 }
 
 // ---- dropout (the DROP instantiations only) ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ DropKey dc_drop_off() { return DropKey{0u, 0u, 0u, 1.f, false}; }
 // the mask of a site on the lane's 8 elements of row `pair`: the pieces lane and lane + 64 are the column groups lane and lane + 64
 __device__ __forceinline__ void dc_row_mask(float (&m)[8], const DropKey& k, int pair, int lane) {
 #pragma unroll
@@ -236,154 +209,36 @@ __device__ __forceinline__ void dc_cross_u_drop(float (&u)[8], const float (&x0)
     for (int k = 0; k < 8; ++k) u[k] = (x0[k] * s) * m[k] + x0[k];
 }
 
-// y[pair][0 .. M) = W [M][K] x + bias, x the lane's own pair row (forward_layer of ncf_train.hip without its ReLU; K a multiple of 32)
-// DROP: the result is multiplied by the mask of key ky before the store (row = the pair)
-template <bool DROP>
-__device__ __forceinline__ void dc_linear(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* xrow, bool valid,
-                                          float* yrow, int wave, int lane, const DropKey& ky, int pair) {
-    const int p = lane & 31, h = lane >> 5;
-    for (int mb = wave; mb * 32 < M; mb += DC_WAVES) {
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int f = mb * 32 + rho(g) + 4 * h;
-            acc[g] = f < M ? bias[f] : 0.f;
-        }
-        const int m = mb * 32 + p;
-        const float* wrow = W + (int64_t)m * K;
-        for (int k0 = 0; k0 < K; k0 += 32) {
-            float4 a[4], x[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = k0 + 16 * h + 4 * j;
-                a[j] = dc_ld4(wrow + k, m < M && k < K);
-                x[j] = dc_ld4(xrow + k, valid && k < K);
-            }
-            if constexpr (DROP) {                            // a block of 32 k sums from 0 and is added whole: K / 32 + 16 additions deep, not K / 2
-                f32x16 blk;
-#pragma unroll
-                for (int g = 0; g < 16; ++g) blk[g] = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) blk = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), blk, 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < 16; ++g) acc[g] = acc[g] + blk[g];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dc_elem(a[j], e), dc_elem(x[j], e), acc, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int f = mb * 32 + 8 * q + 4 * h;
-            if constexpr (DROP) {
-                float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-                if (ky.on) {
-                    float mk[4];
-                    drop_mul4(ky, (uint32_t)pair, (uint32_t)(f >> 2), mk);
-                    v.x *= mk[0], v.y *= mk[1], v.z *= mk[2], v.w *= mk[3];
-                }
-                if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = v;
-            } else {
-                if (valid && f < M) *reinterpret_cast<float4*>(yrow + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-            }
-        }
-    }
-}
-
-// dx[pair][c] = sum_o W[o][c] dy[pair][o] for c in [0, K), W [M][K]
-// DROP: per block of 32 o, as dc_linear
-template <bool DROP>
-__device__ __forceinline__ void dc_linear_bwd(const float* __restrict__ W, int M, int K, const float* dy_row, bool valid, float* dx_row, int wave,
-                                              int lane) {
-    const int p = lane & 31, h = lane >> 5;
-    for (int cb = wave; cb * 32 < K; cb += DC_WAVES) {
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-        const int c = cb * 32 + p;
-        for (int o0 = 0; o0 < M; o0 += 32) {
-            float4 z[4];
-            float a[16];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = dc_ld4(dy_row + o0 + 16 * h + 4 * j, valid && o0 + 16 * h + 4 * j < M);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const int o = o0 + 16 * h + s;
-                a[s] = (c < K && o < M) ? W[(int64_t)o * K + c] : 0.f;
-            }
-            if constexpr (DROP) {
-                f32x16 blk;
-#pragma unroll
-                for (int g = 0; g < 16; ++g) blk[g] = 0.f;
-#pragma unroll
-                for (int s = 0; s < 16; ++s) blk = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), blk, 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < 16; ++g) acc[g] = acc[g] + blk[g];
-            } else {
-#pragma unroll
-                for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], dc_elem(z[s >> 2], s & 3), acc, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int f = cb * 32 + 8 * q + 4 * h;
-            if (valid && f < K) *reinterpret_cast<float4*>(dx_row + f) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-        }
-    }
-}
-
 // TRAIN: the gradient entry (the forward entry is the same forward code without the stores and the phases only the backward needs)
 // LN: use_layer_norm
 // DROP: dropout is on at one site or more (without it the kernel's instructions are those it had: `dr` is not read)
 template <bool TRAIN, bool LN, bool DROP>
-__global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, DcDrop dr) {
-    __shared__ float s_dl[DC_TILE];
-    __shared__ int64_t s_ids[DC_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
-    int bid = blockIdx.x;
+__global__ __launch_bounds__(PAIR_THREADS) void dcn_pairs_kernel(DcPairsArgs a, DcDrop dr) {
+    __shared__ float s_dl[PAIR_TILE];
+    __shared__ int64_t s_ids[PAIR_THREADS];
+    constexpr Chain DC_CHAIN = DROP ? Chain::BLOCK : Chain::ONE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = pair_wave_index(), n = a.n;
+    const int bid = blockIdx.x;
     if constexpr (TRAIN) {
         if (bid >= a.tiles + 2 * a.rank_blocks) {            // ---- zero: the gradients of the two embedding tables, whole
-            float4* z = reinterpret_cast<float4*>(a.zero_base);
-            for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * DC_THREADS + tid; i < a.zero_vec4; i += (int64_t)a.zero_blocks * DC_THREADS)
-                z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            pair_zero<false>(bid - a.tiles - 2 * a.rank_blocks, a.zero_blocks, a.zero_base, a.zero_vec4, nullptr, 0, tid);
             return;
         }
         if (bid >= a.tiles) {                                // ---- rank: the stable order by id, counted
-            bid -= a.tiles;
-            const int kind = bid / a.rank_blocks;
-            const int64_t* ids = kind ? a.items : a.users;
-            int* order = kind ? a.order_i : a.order_u;
-            const int p = (bid - kind * a.rank_blocks) * DC_THREADS + tid;
-            const int64_t mine = p < n ? ids[p] : 0;
-            int rank = 0;
-            for (int q0 = 0; q0 < n; q0 += DC_THREADS) {
-                __syncthreads();
-                s_ids[tid] = q0 + tid < n ? ids[q0 + tid] : 0;
-                __syncthreads();
-                const int cnt = min(DC_THREADS, n - q0);
-                for (int j = 0; j < cnt; ++j) {
-                    const int64_t v = s_ids[j];
-                    rank += (v < mine || (v == mine && q0 + j < p)) ? 1 : 0;
-                }
-            }
-            if (p < n) order[rank] = p;
+            pair_rank(bid - a.tiles, a.rank_blocks, n, a.users, a.items, a.order_u, a.order_i, s_ids, tid);
             return;
         }
     }
     // ---- tile: 32 pairs
     const int D = a.D, E = a.E, L = a.L, C = a.C;
-    const int mpair = bid * DC_TILE + (lane & 31);           // the lane's pair in the MFMA phases
+    const int mpair = bid * PAIR_TILE + (lane & 31);           // the lane's pair in the MFMA phases
     const bool mvalid = mpair < n;
     const DcRow rD = dc_row(D, lane);
-    DropKey kemb = dc_drop_off();
+    DropKey kemb = pair_drop_off();
     if constexpr (DROP) kemb = make_drop_key(DropCfg{dr.d.rng, dr.d.p_emb, DCN_SITE_EMB});
     // x0 = [users_t[u] ; items_t[i]]: a piece lies in one half (E is a multiple of 4)
     for (int i = 0; i < DC_PER_WAVE; ++i) {
-        const int pair = bid * DC_TILE + wave * DC_PER_WAVE + i;
+        const int pair = bid * PAIR_TILE + wave * DC_PER_WAVE + i;
         if (pair >= n) break;                                // (uniform per wave)
         const float* urow = a.users_t + a.users[pair] * E;
         const float* irow = a.items_t + a.items[pair] * E;
@@ -409,13 +264,14 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
     for (int l = 0; l < L; ++l) {
         const DcDeep& dl = a.deep[l];
         const float* xin = l == 0 ? a.x0 : a.deep[l - 1].h;
-        DropKey kdeep = dc_drop_off();                       // DROP: the stored y_l is the dropped one, and the row pass normalises that
+        DropKey kdeep = pair_drop_off();                       // DROP: the stored y_l is the dropped one, and the row pass normalises that
         if constexpr (DROP) kdeep = make_drop_key(DropCfg{dr.d.rng, dr.d.p_deep[l], DCN_SITE_DEEP + (uint32_t)l});
-        dc_linear<DROP>(dl.w, dl.b, dl.out, dl.in, xin + (int64_t)mpair * dl.in, mvalid, dl.y + (int64_t)mpair * dl.out, wave, lane, kdeep, mpair);
+        pair_linear<DC_CHAIN, false, DROP>(dl.w, dl.b, dl.out, dl.in, xin + (int64_t)mpair * dl.in, dl.in, nullptr, mvalid,
+                                           dl.y + (int64_t)mpair * dl.out, wave, lane, pair_drop_off(), kdeep, mpair);
         __syncthreads();
         const DcRow r = dc_row(dl.out, lane);
         for (int i = 0; i < DC_PER_WAVE; ++i) {
-            const int pair = bid * DC_TILE + wave * DC_PER_WAVE + i;
+            const int pair = bid * PAIR_TILE + wave * DC_PER_WAVE + i;
             if (pair >= n) break;
             float v[8];
             dc_row_ld(v, dl.y + (int64_t)pair * dl.out, r);
@@ -437,7 +293,7 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
     const int HW = a.deep[L - 1].out;                        // 2 F
     const DcRow rH = dc_row(HW, lane);
     for (int i = 0; i < DC_PER_WAVE; ++i) {
-        const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+        const int pl = wave * DC_PER_WAVE + i, pair = bid * PAIR_TILE + pl;
         if (pair >= n) {
             if (TRAIN && lane == 0) s_dl[pl] = 0.f;
             continue;
@@ -483,12 +339,10 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
         if (lane == 0) {
             if (a.logits) a.logits[pair] = z;
             if constexpr (TRAIN) {
-                const float y = a.labels[pair];
-                const float e = expf(-fabsf(z));
-                const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-                const float dz = (sig - y) / (float)n;
+                float dz, loss;
+                pair_bce<false>(z, a.labels[pair], n, dz, loss);
                 a.pz[(int64_t)pair * 2] = dz;
-                a.pz[(int64_t)pair * 2 + 1] = (fmaxf(z, 0.f) - z * y) + log1pf(e);
+                a.pz[(int64_t)pair * 2 + 1] = loss;
                 s_dl[pl] = dz;
             }
         }
@@ -499,10 +353,10 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
     for (int l = L - 1; l >= 0; --l) {
         const DcDeep& dl = a.deep[l];
         const DcRow r = dc_row(dl.out, lane);
-        DropKey kdeep = dc_drop_off();
+        DropKey kdeep = pair_drop_off();
         if constexpr (DROP) kdeep = make_drop_key(DropCfg{dr.d.rng, dr.d.p_deep[l], DCN_SITE_DEEP + (uint32_t)l});
         for (int i = 0; i < DC_PER_WAVE; ++i) {
-            const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+            const int pl = wave * DC_PER_WAVE + i, pair = bid * PAIR_TILE + pl;
             if (pair >= n) break;
             float g[8], hv[8];
             if (l == L - 1) {
@@ -538,12 +392,13 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
         }
         __syncthreads();
         float* dst = l == 0 ? a.dx0 : a.deep[l - 1].dy;
-        dc_linear_bwd<DROP>(dl.w, dl.out, dl.in, dl.dy + (int64_t)mpair * dl.out, mvalid, dst + (int64_t)mpair * dl.in, wave, lane);
+        pair_linear_bwd<DC_CHAIN, DROP>(dl.w, dl.out, dl.in, dl.in, dl.dy + (int64_t)mpair * dl.out, nullptr, mvalid, dst + (int64_t)mpair * dl.in,
+                                        wave, lane, 1.f, pair_drop_off(), mpair);
         __syncthreads();
     }
     // cross backward and d x0
     for (int i = 0; i < DC_PER_WAVE; ++i) {
-        const int pl = wave * DC_PER_WAVE + i, pair = bid * DC_TILE + pl;
+        const int pl = wave * DC_PER_WAVE + i, pair = bid * PAIR_TILE + pl;
         if (pair >= n) break;
         float e0[8], g[8], acc[8], t[8];
         dc_row_ld(e0, a.x0 + (int64_t)pair * D, rD);
@@ -608,38 +463,20 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_pairs_kernel(DcPairsArgs a, Dc
     }
 }
 
-__device__ __forceinline__ float dc_src_at(const DcTask& t, int pair, int c) {
-    return c < t.w1 ? t.b1[(int64_t)pair * t.w1 + c] : t.b2[(int64_t)pair * t.w2 + (c - t.w1)];
-}
-
 // DROP: a cross layer's mask is on: the cols role draws it again where it recomputes x^(c) / xhat (the weight and rows roles read stored,
 // already dropped operands and need nothing)
 template <bool LN, bool DROP>
-__global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a, DcDrop dr) {
-    __shared__ float s_acc[DC_WAVES][16][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = dc_wave_index(), n = a.n;
+__global__ __launch_bounds__(PAIR_THREADS) void dcn_grads_kernel(DcGradsArgs a, DcDrop dr) {
+    __shared__ float s_acc[PAIR_WAVES][16][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = pair_wave_index(), n = a.n;
     int bid = blockIdx.x;
     if (bid >= a.weight_blocks + a.col_blocks) {             // ---- rows: segment sums of d x0's halves in pair order
-        bid -= a.weight_blocks + a.col_blocks;
-        const int kind = bid / a.row_blocks;
-        const int s = (bid - kind * a.row_blocks) * DC_WAVES + wave;
-        if (s >= n) return;
-        const int64_t* ids = kind ? a.items : a.users;
-        const int* order = kind ? a.order_i : a.order_u;
-        const int64_t id = ids[order[s]];
-        if (s > 0 && ids[order[s - 1]] == id) return;        // (uniform per wave) not the start of a run
+        const PairRun r = pair_run(bid - a.weight_blocks - a.col_blocks, a.row_blocks, wave, n, a.users, a.items, a.order_u, a.order_i);
+        if (!r.start) return;
         const int E = a.E;
-        const float* src = a.dx0 + (kind ? E : 0);
-        float* dst = (kind ? a.g_items : a.g_users) + id * E;
-        for (int c = lane; c < E; c += 64) {
-            float sum = 0.f;
-            for (int t = s; t < n; ++t) {
-                const int pr = order[t];
-                if (ids[pr] != id) break;
-                sum += src[(int64_t)pr * 2 * E + c];
-            }
-            dst[c] = sum;
-        }
+        const float* src = a.dx0 + (r.kind ? E : 0);
+        float* dst = (r.kind ? a.g_items : a.g_users) + r.id * E;
+        for (int c = lane; c < E; c += 64) dst[c] = pair_run_sum(r, n, src, 2 * E, c);
         return;
     }
     if (bid >= a.weight_blocks) {                            // ---- cols: sums over the pairs of 64 columns
@@ -652,13 +489,13 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a, Dc
         const bool ok = col < W;
         float gam = 0.f, bet = 0.f;
         if (LN && jb.kind == DC_JOB_CROSS_W && jb.st && ok) gam = jb.gamma[col], bet = jb.beta[col];
-        DropKey kc = dc_drop_off();
+        DropKey kc = pair_drop_off();
         if constexpr (DROP) {
             const int mc = dr.job_cross[ji];
             if (mc >= 0) kc = make_drop_key(DropCfg{dr.d.rng, dr.d.p_cross[mc], DCN_SITE_CROSS + (uint32_t)mc});
         }
         float sum = 0.f;
-        for (int p = wave; p < n; p += DC_WAVES) {
+        for (int p = wave; p < n; p += PAIR_WAVES) {
             if (!ok) break;
             const int64_t at = (int64_t)p * W + col;
             float v;
@@ -690,50 +527,7 @@ __global__ __launch_bounds__(DC_THREADS) void dcn_grads_kernel(DcGradsArgs a, Dc
         return;
     }
     // ---- weight: one 32 x 32 block of dW = dy^T x, the pairs in order
-    int ti = 0;
-    for (int i = 1; i < a.ntasks; ++i)
-        if (bid >= a.task[i].first) ti = i;
-    const DcTask& t = a.task[ti];
-    const int local = bid - t.first, M = t.m, K = t.w1 + t.w2;
-    const int mb = local / t.col_blocks, nb = local - mb * t.col_blocks;
-    const bool ones = nb == t.col_blocks - 1;
-    const int p = lane & 31, h = lane >> 5, m = mb * 32 + p, c = nb * 32 + p;
-    f32x16 acc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-    for (int ch = wave; ch * 32 < n; ch += DC_WAVES) {
-        float av[16], bv[16];
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int pair = ch * 32 + 16 * h + s;
-            const bool ok = pair < n;
-            av[s] = (ok && m < M) ? t.a[(int64_t)pair * M + m] : 0.f;
-            bv[s] = ones ? (p == 0 ? 1.f : 0.f) : ((ok && c < K) ? dc_src_at(t, pair, c) : 0.f);
-        }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int g = 0; g < 16; ++g) s_acc[wave][g][lane] = acc[g];
-    __syncthreads();
-    const int gq = tid >> 6;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-        const int g = gq * 4 + gg;
-        const float v = (s_acc[0][g][lane] + s_acc[1][g][lane]) + (s_acc[2][g][lane] + s_acc[3][g][lane]);
-        const int mo = mb * 32 + rho(g) + 4 * h;
-        if (t.predict) {
-            if (mo == 0) {
-                if (ones) { if (p == 0) t.gb[0] = v; }
-                else if (c < K) t.gw[c] = v;
-            } else if (mo == 1 && ones && p == 0) {
-                a.loss[0] = v / (float)n;
-            }
-        } else if (mo < M) {
-            if (ones) { if (p == 0) t.gb[mo] = v; }
-            else if (c < K) t.gw[(int64_t)mo * K + c] = v;
-        }
-    }
+    pair_weight_block<false, false>(a.task, a.ntasks, bid, n, a.loss, DropCfg{}, s_acc, tid, lane, wave);
 }
 
 struct DcShape {
@@ -747,8 +541,7 @@ static int dc_shape(int F, int L, int C, int ln, int64_t user_num, int64_t item_
     PMGT_CHECK((F << L) <= DC_MAX_E, -2, "%s: E = factor_num * 2^deep_layers = %d above %d", who, F << L, DC_MAX_E);
     PMGT_CHECK(C >= 1 && C <= DC_MAX_CROSS, -2, "%s: cross_layers = %d outside [1, %d]", who, C, DC_MAX_CROSS);
     PMGT_CHECK(ln == 0 || ln == 1, -2, "%s: use_layer_norm = %d, expected 0 or 1", who, ln);
-    PMGT_CHECK(user_num >= 1 && user_num <= 0x7FFFFFFELL, -2, "%s: user_num = %lld outside [1, 2^31 - 2]", who, (long long)user_num);
-    PMGT_CHECK(item_num >= 1 && item_num <= 0x7FFFFFFELL, -2, "%s: item_num = %lld outside [1, 2^31 - 2]", who, (long long)item_num);
+    if (int rc = pair_check_rows(who, user_num, item_num)) return rc;
     *s = DcShape{F, L, C, ln, F << L, 2 * (F << L), user_num, item_num};
     return 0;
 }
@@ -792,34 +585,30 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     DcShape s;
     if (int rc = dc_shape(head->factor_num, head->deep_layers, head->cross_layers, head->use_layer_norm, head->user_num, head->item_num, who, &s))
         return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_DCN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_DCN_MAX_PAIRS);
+    if (int rc = pair_check_n(who, n, PMGT_DCN_MAX_PAIRS)) return rc;
     PMGT_CHECK(head->layer_norm_eps >= 0.f, -2, "%s: layer_norm_eps = %g is NaN or negative", who, (double)head->layer_norm_eps);      // (a NaN fails)
     PMGT_CHECK(head->params && users && items && workspace, -2, "%s: NULL buffer", who);
     PMGT_CHECK(train ? (head->grads && labels && loss) : logits != nullptr, -2, "%s: NULL buffer", who);
     PMGT_CHECK((((uintptr_t)head->params | (uintptr_t)(train ? head->grads : nullptr) | (uintptr_t)workspace) & 15) == 0, -2,
                "%s: the parameters, the gradients and the workspace must be 16-byte aligned", who);
-    PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
-               "%s: misaligned buffer", who);
+    if (int rc = pair_check_small(who, users, items, labels, loss, logits)) return rc;
     const int64_t need = dc_workspace_floats(s, n) * (int64_t)sizeof(float);
     PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
     DcDrop dr = {};
     bool drop_on = false, cross_on = false;                  // every p 0: the instantiations without dropout
     if (drop) {
         dr.d.rng = drop->rng, dr.d.p_emb = drop->p_emb;
-        PMGT_CHECK(dr.d.p_emb >= 0.f && dr.d.p_emb < 1.f, -2, "%s: p_emb = %g outside [0, 1)", who, (double)dr.d.p_emb);      // (a NaN fails both)
-        drop_on = dr.d.p_emb > 0.f;
+        if (int rc = pair_check_p(who, "p_emb", -1, dr.d.p_emb, &drop_on)) return rc;
         for (int l = 0; l < s.L; ++l) {
             dr.d.p_deep[l] = drop->p_deep[l];
-            PMGT_CHECK(dr.d.p_deep[l] >= 0.f && dr.d.p_deep[l] < 1.f, -2, "%s: p_deep[%d] = %g outside [0, 1)", who, l, (double)dr.d.p_deep[l]);
-            drop_on = drop_on || dr.d.p_deep[l] > 0.f;
+            if (int rc = pair_check_p(who, "p_deep", l, dr.d.p_deep[l], &drop_on)) return rc;
         }
         for (int c = 0; c < s.C; ++c) {
             dr.d.p_cross[c] = drop->p_cross[c];
-            PMGT_CHECK(dr.d.p_cross[c] >= 0.f && dr.d.p_cross[c] < 1.f, -2, "%s: p_cross[%d] = %g outside [0, 1)", who, c, (double)dr.d.p_cross[c]);
-            cross_on = cross_on || dr.d.p_cross[c] > 0.f;
+            if (int rc = pair_check_p(who, "p_cross", c, dr.d.p_cross[c], &cross_on)) return rc;
         }
         drop_on = drop_on || cross_on;
-        PMGT_CHECK(!drop_on || (dr.d.rng && ((uintptr_t)dr.d.rng & 7) == 0), -2, "%s: dropout needs the device {seed, step} pair, 8-byte aligned", who);
+        if (int rc = pair_check_rng(who, drop_on, dr.d.rng)) return rc;
     }
     int64_t off[PMGT_DCN_TENSORS];
     dc_layout(s, off);
@@ -862,46 +651,23 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     pa.zero_vec4 = off[2] / 4;                               // the two tables come first; E is a multiple of 8
     pa.eps = head->layer_norm_eps;
     pa.n = (int)n, pa.E = s.E, pa.D = D, pa.F = s.F, pa.L = L, pa.C = C;
-    pa.tiles = (int)cdiv64(n, DC_TILE);
-    pa.rank_blocks = (int)cdiv64(n, DC_THREADS);
-    pa.zero_blocks = (int)std::min<int64_t>(DC_ZERO_BLOCKS, cdiv64(pa.zero_vec4, DC_THREADS));
+    pa.tiles = (int)cdiv64(n, PAIR_TILE);
+    pa.rank_blocks = (int)cdiv64(n, PAIR_THREADS);
+    pa.zero_blocks = (int)std::min<int64_t>(PAIR_ZERO_BLOCKS, cdiv64(pa.zero_vec4, PAIR_THREADS));
     hipStream_t st = (hipStream_t)stream;
     if (!train) {
-        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<false, true, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa, dr);
-        else hipLaunchKernelGGL((dcn_pairs_kernel<false, false, false>), dim3((unsigned)pa.tiles), dim3(DC_THREADS), 0, st, pa, dr);
+        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<false, true, false>), dim3((unsigned)pa.tiles), dim3(PAIR_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((dcn_pairs_kernel<false, false, false>), dim3((unsigned)pa.tiles), dim3(PAIR_THREADS), 0, st, pa, dr);
         PMGT_LAUNCH_OK();
         return 0;
     }
 
     DcGradsArgs ga = {};
     int first = 0;
-    for (int l = 0; l < L; ++l) {
-        DcTask& t = ga.task[l];
-        t.a = pa.deep[l].dy;
-        t.m = pa.deep[l].out;
-        t.b1 = l == 0 ? pa.x0 : pa.deep[l - 1].h, t.w1 = pa.deep[l].in;
-        t.b2 = nullptr, t.w2 = 0;
-        t.gw = G + off[2 + 4 * l];
-        t.gb = G + off[3 + 4 * l];
-        t.col_blocks = (t.w1 + 31) / 32 + 1;
-        t.first = first;
-        t.predict = 0;
-        first += (t.m + 31) / 32 * t.col_blocks;
-    }
-    {
-        DcTask& t = ga.task[L];
-        t.a = pa.pz;
-        t.m = 2;
-        t.b1 = pa.xC, t.w1 = D;
-        t.b2 = pa.deep[L - 1].h, t.w2 = 2 * s.F;
-        t.gw = G + off[36];
-        t.gb = G + off[37];
-        t.col_blocks = (D + 2 * s.F + 31) / 32 + 1;
-        t.first = first;
-        t.predict = 1;
-        first += t.col_blocks;
-    }
-    ga.ntasks = L + 1;
+    for (int l = 0; l < L; ++l)
+        pair_add_task(ga.task, &ga.ntasks, &first, pa.deep[l].dy, pa.deep[l].out,
+                      PairSrc{l == 0 ? pa.x0 : pa.deep[l - 1].h, nullptr, pa.deep[l].in, nullptr, nullptr, 0}, G + off[2 + 4 * l], G + off[3 + 4 * l], false);
+    pair_add_task(ga.task, &ga.ntasks, &first, pa.pz, 2, PairSrc{pa.xC, nullptr, D, pa.deep[L - 1].h, nullptr, 2 * s.F}, G + off[36], G + off[37], true);
     ga.weight_blocks = first;
     int nj = 0, cfirst = 0;
     auto add_job = [&](int kind, const float* a, const float* x, const float* stp, int stride, const float* gm, const float* bt, float* out, int W,
@@ -926,7 +692,7 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
     }
     ga.njobs = nj;
     ga.col_blocks = cfirst;
-    ga.row_blocks = (int)cdiv64(n, DC_WAVES);
+    ga.row_blocks = (int)cdiv64(n, PAIR_WAVES);
     ga.users = users, ga.items = items;
     ga.order_u = pa.order_u, ga.order_i = pa.order_i;
     ga.dx0 = pa.dx0;
@@ -936,19 +702,19 @@ static int dc_run(const char* who, bool train, const pmgt_dcn_head* head, const 
 
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
     if (drop_on) {
-        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
-        else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, true>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
+        if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, true>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, true>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
     }
-    else if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
-    else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, false>), dim3(grid1), dim3(DC_THREADS), 0, st, pa, dr);
+    else if (s.ln) hipLaunchKernelGGL((dcn_pairs_kernel<true, true, false>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
+    else hipLaunchKernelGGL((dcn_pairs_kernel<true, false, false>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
     PMGT_LAUNCH_OK();
     const unsigned grid2 = (unsigned)(ga.weight_blocks + ga.col_blocks + 2 * ga.row_blocks);
     if (cross_on) {                                          // (launch 2 draws cross masks only)
-        if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
-        else hipLaunchKernelGGL((dcn_grads_kernel<false, true>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
+        if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, true>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
+        else hipLaunchKernelGGL((dcn_grads_kernel<false, true>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
     }
-    else if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
-    else hipLaunchKernelGGL((dcn_grads_kernel<false, false>), dim3(grid2), dim3(DC_THREADS), 0, st, ga, dr);
+    else if (s.ln) hipLaunchKernelGGL((dcn_grads_kernel<true, false>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
+    else hipLaunchKernelGGL((dcn_grads_kernel<false, false>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
     PMGT_LAUNCH_OK();
     return 0;
 }
@@ -974,7 +740,7 @@ int64_t pmgt_dcn_workspace_bytes(int factor_num, int deep_layers, int cross_laye
     const char* who = "pmgt_dcn_workspace_bytes";
     DcShape s;
     if (int rc = dc_shape(factor_num, deep_layers, cross_layers, use_layer_norm, 1, 1, who, &s)) return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_DCN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_DCN_MAX_PAIRS);
+    if (int rc = pair_check_n(who, n, PMGT_DCN_MAX_PAIRS)) return rc;
     return dc_workspace_floats(s, n) * (int64_t)sizeof(float);
 }
 

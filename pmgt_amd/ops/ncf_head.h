@@ -1,5 +1,7 @@
-// What ncf_score.hip and ncf_train.hip share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU, the covered heads, the
-// dropout sites of the trained head; dcn_train.hip takes the block order, the ReLU and its own dropout sites from here.
+// What the scoring and the training kernels of the pair heads share: the accumulator and register order of the 32 x 32 MFMA block, the ReLU,
+// the covered heads, the dropout sites of the trained head and of the DCN.  Included through ncf_score_tile.h (the scoring tower of
+// ncf_score.hip, ncf_model_score.hip, dcn_score.hip) and pair_train_tile.h (the pair-major training tile of ncf_train.hip,
+// ncf_model_train.hip, dcn_train.hip); item_sim.hip takes the block order alone.
 #pragma once
 #include "../csrc/common.h"
 #include "../../include/pmgt_capi.h"

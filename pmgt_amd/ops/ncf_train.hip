@@ -1,37 +1,20 @@
 // Training of the head of PMGT_NCF over an item table, FROZEN (pmgt_ncf_train_grad of include/pmgt_capi.h) or TRAINED WITH THE HEAD
 // (pmgt_ncf_train_grad_table; the head: pmgt/pmgt_ncf/models.py:91-105, the step it serves: pmgt/ncf/trainer.py:183-200, the table's
 // requires_grad_: pmgt/ncf/trainer.py:168-179): loss, logits and the gradient of the mean BCE-with-logits loss with respect to every
-// parameter of the head -- and, for the second entry, to the table --, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for ncf_score.hip's reason: the measured step
-// launches nothing of this.  fp32 end to end; every matrix product runs on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32).
+// parameter of the head -- and, for the second entry, to the table --, for n (user, item, label) pairs, in TWO launches.  Kept out of csrc/ for
+// ncf_score.hip's reason: the measured step launches nothing of this.  The pair-major product forms, the roles rank / zero / weight / rows
+// and the chain policies are stated in pair_train_tile.h; this file's products are Chain::ONE with the ReLU in the epilogue, and its loss
+// line is the FUSED form of pair_bce (the file is compiled with the compiler's default contraction).
 //
-// EVERYTHING IS PAIR-MAJOR.  Activations act_l [n][out_l], pre-activation gradients dz_l [n][out_l] and the per-pair embedding gradients sit in
-// the caller's workspace as plain row-major matrices, one row per pair.  The three products are then
-//   forward   Y^T [out, pair] = W [out, in] X^T          A = W[m][k]: 16 contiguous k per lane (4 x 16-byte loads), B = X[pair][k]: the same
-//   data      dX^T [in, pair] = W^T [in, out] dZ^T       A = W[k][m]: one coalesced row segment per k-step,          B = dZ[pair][k]: 16 per lane
-//   weight    dW [out, in]    = dZ^T [out, pair] X       A = dZ[pair][m], B = X[pair][c]: both one coalesced row segment per k-step
-// with the PAIR on the lane in the first two (result register g of lane half h = feature rho(g) + 4 h, so a lane stores four 16-byte pieces
-// of its pair's row) and the pairs as the contraction index of the third.  A 32-wide chunk of k is split 16 | 16 between the lane halves:
-// k-step s multiplies k0 + s (half 0) and k0 + 16 + s (half 1).  Widths below 32 are zero-padded by the guards of the loads.
-//
-// LAUNCH 1, ncf_train_pairs_kernel, three roles by block index:
-//   tile   32 pairs a workgroup of 4 waves (the waves share out the 32-feature blocks of a layer): gathers [U_mlp[u] ; table[i]] on the fly,
-//          runs the layers, the GMF product and the predict layer, the stable loss max(z, 0) - z y + log1p(exp(-|z|)) and
-//          dlogit = (sigmoid(z) - y) / n, then walks back: dz_l = (W_(l+1)^T dz_(l+1)) * (act_l > 0) down to the user half of layer 0's input
-//          (frozen table: dx [n][d]) or to all of it (trained table: dx [n][2 d], the item half behind the user half; a column block is
-//          computed on its own, so the user half has the same bits either way).
-//          Between layers the rows go through the workspace; a workgroup reads only what it wrote itself, behind a barrier.
-//   rank   the position of every pair in the STABLE order by user id (and, NeuMF-end, by item id): rank = the number of pairs with a smaller
-//          (id, pair index); counted, not sorted: n <= 65 536 and the ids of a block of 256 pairs go through LDS once per 256 ranks.
-//   zero   the gradient rows of the embedding tables, whole (the optimizer is dense), and as a second range the table's gradient.
-// LAUNCH 2, ncf_train_grads_kernel, two roles:
-//   weight one workgroup per 32 x 32 block of a layer's dW; its 4 waves take the 32-pair chunks c = w, w + 4, ... IN ORDER and the four
-//          accumulators are added as (w0 + w1) + (w2 + w3).  A layer has one more block column whose B operand is the constant column
-//          (1, 0, ..., 0): its column 0 is the bias gradient.  The predict layer is the pseudo-layer with dz = [dlogit, loss_pair]: row 0 gives
-//          d predict_layer.weight and .bias, row 1 of the constant column the loss sum.
-//   rows   one wave per position of the stable order; the wave at the start of a run of equal ids adds the run's per-pair rows in pair order
-//          and stores the table row.  Rows no pair touches keep the +0.0 of launch 1.  The item kind sums the GMF item rows (NeuMF-end)
-//          and, for a trained table, the item half of dx by the same rule.
-// DETERMINISM: no atomic anywhere; every sum has one fixed order, so the same inputs give the same bits.
+// LAUNCH 1, ncf_train_pairs_kernel: the roles rank (by user id and, NeuMF-end, by item id) and zero (the embedding gradients and, as a
+// second range, the table's gradient), and
+//   tile   32 pairs a workgroup: gathers [U_mlp[u] ; table[i]] on the fly, runs the layers, the GMF product and the predict layer, the loss
+//          and dlogit, then walks back: dz_l = (W_(l+1)^T dz_(l+1)) * (act_l > 0) down to the user half of layer 0's input (frozen table:
+//          dx [n][d]) or to all of it (trained table: dx [n][2 d], the item half behind the user half; a column block is computed on its
+//          own, so the user half has the same bits either way).  Between layers the rows go through the workspace; a workgroup reads only
+//          what it wrote itself, behind a barrier.
+// LAUNCH 2, ncf_train_grads_kernel: the roles weight and rows.  The user kind of rows sums dx's user half and the GMF user rows, the item
+// kind the GMF item rows (NeuMF-end) and, for a trained table, the item half of dx.
 //
 // DROPOUT (pmgt_ncf_train_grad_dropout; the DROP instantiations, the others are the kernels as they were): PMGT_NCF.head in training mode,
 // the masks m = 0 or 1 / (1 - p) drawn by the counter-based RNG of csrc/common.h from the caller's device {seed, step} pair, indexed by
@@ -46,18 +29,17 @@
 //
 // PER-PAIR ITEM ROWS (pmgt_ncf_train_grad_rows: the head on top of an encoder that is trained with it, every pair with a context and so an
 // item embedding of its own), still TWO launches: the TABLE instantiations with two run-time differences.  Launch 1 reads the item half of
-// layer 0's input from row `pair` of x_item [n][d] instead of table[items[pair]], and the weight task of layer 0 reads the same rows (NtSrc
+// layer 0's input from row `pair` of x_item [n][d] instead of table[items[pair]], and the weight task of layer 0 reads the same rows (PairSrc
 // by the pair index).  Launch 2 sums no table rows; its extra role
 //   item   copies the item half of dx [n][2 d] into the caller's d_item [n][d], 16 bytes a thread: one row per pair, nothing summed
 // so two pairs on one item keep their own gradient rows.  The other entries launch no block of this role and keep their bits.
 #include <climits>
 
-#include "ncf_head.h"
+#include "pair_train_tile.h"
 
 namespace pmgt {
 
-static constexpr int NT_THREADS = 256, NT_WAVES = 4, NT_TILE = 32, NT_MAX_LAYERS = PMGT_NCF_MAX_LAYERS;
-static constexpr int NT_ZERO_BLOCKS = 1024, NT_MAX_TASKS = NT_MAX_LAYERS + 1;
+static constexpr int NT_MAX_LAYERS = PMGT_NCF_MAX_LAYERS, NT_MAX_TASKS = NT_MAX_LAYERS + 1;
 
 struct NtLayer {
     const float* w;      // [out][2 out]
@@ -83,28 +65,10 @@ struct NtPairsArgs {
     int n, d, factor, num_layers, neumf, tiles, rank_blocks, zero_blocks;
 };
 
-// a matrix [n][w1 + w2] given by one or two row sources, each read by the pair index itself (idx NULL) or through an id list
-struct NtSrc {
-    const float* p1;
-    const int64_t* idx1;
-    int w1;
-    const float* p2;
-    const int64_t* idx2;
-    int w2;
-};
-
-struct NtTask {
-    const float* a;      // dz [n][m]
-    NtSrc b;             // the layer's input [n][k]
-    float* gw;           // [m][k]
-    float* gb;           // [m]
-    int m, col_blocks, first, predict;      // col_blocks counts the constant column's block
-};
-
 typedef pmgt_ncf_dropout NtDrop;      // the second kernel argument; only the DROP instantiations read it
 
 struct NtGradsArgs {
-    NtTask task[NT_MAX_TASKS];
+    PairTask task[NT_MAX_TASKS];
     const int64_t *users, *items;
     const int *order_u, *order_i;
     const float *dx, *ggu, *ggi;
@@ -114,180 +78,44 @@ struct NtGradsArgs {
     int item_first, item_blocks;                                     // rows entry: the first block and the count of the `item` role; else (INT_MAX, 0)
 };
 
-__device__ __forceinline__ float4 ld4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-__device__ __forceinline__ float elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }      // provably uniform
-__device__ __forceinline__ DropKey drop_off() { return DropKey{0u, 0u, 0u, 1.f, false}; }
-__device__ __forceinline__ void mul4(float4& v, const float (&m)[4]) { v.x *= m[0], v.y *= m[1], v.z *= m[2], v.w *= m[3]; }
-
-// act[pair][0 .. M) = relu(W [M][K] x + bias); x = [r1[0 .. w1) ; r2[0 .. K - w1)], the lane's own pair row(s)
-// DROP: x is multiplied by the mask of key kx as it is loaded and the result by the mask of ky before the store (row = the pair)
-template <bool DROP>
-__device__ __forceinline__ void forward_layer(const float* __restrict__ W, const float* __restrict__ bias, int M, int K, const float* r1, int w1,
-                                              const float* r2, bool valid, float* act_row, int wave, int lane, const DropKey& kx,
-                                              const DropKey& ky, int pair) {
-    const int p = lane & 31, h = lane >> 5;
-    for (int mb = wave; mb * 32 < M; mb += NT_WAVES) {
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int f = mb * 32 + rho(g) + 4 * h;
-            acc[g] = f < M ? bias[f] : 0.f;
-        }
-        const int m = mb * 32 + p;
-        const float* wrow = W + (int64_t)m * K;
-        for (int k0 = 0; k0 < K; k0 += 32) {
-            float4 a[4], x[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = k0 + 16 * h + 4 * j;
-                a[j] = ld4(wrow + k, m < M && k < K);
-                x[j] = ld4(k < w1 ? r1 + k : r2 + (k - w1), valid && k < K);
-                if constexpr (DROP) {
-                    if (kx.on) {
-                        float mk[4];
-                        drop_mul4(kx, (uint32_t)pair, (uint32_t)(k >> 2), mk);
-                        mul4(x[j], mk);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(elem(a[j], e), elem(x[j], e), acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int f = mb * 32 + 8 * q + 4 * h;
-            float4 v;
-            v.x = relu_keep_nan(acc[4 * q]);
-            v.y = relu_keep_nan(acc[4 * q + 1]);
-            v.z = relu_keep_nan(acc[4 * q + 2]);
-            v.w = relu_keep_nan(acc[4 * q + 3]);
-            if constexpr (DROP) {
-                if (ky.on) {
-                    float mk[4];
-                    drop_mul4(ky, (uint32_t)pair, (uint32_t)(f >> 2), mk);
-                    mul4(v, mk);
-                }
-            }
-            if (valid && f < M) *reinterpret_cast<float4*>(act_row + f) = v;
-        }
-    }
-}
-
-// dx[pair][c] = sum_o W[o][c] dz[pair][o] for c in [0, C), W [M][K] with C <= K; times (mask_row[c] > 0) when mask_row
-// DROP: a gradient that passes mask_row is multiplied by gscale (the scale of the layer that wrote mask_row), and the result by the mask of kx
-template <bool DROP>
-__device__ __forceinline__ void backward_layer(const float* __restrict__ W, int M, int K, int C, const float* dz_row, const float* mask_row,
-                                               bool valid, float* dx_row, int wave, int lane, float gscale, const DropKey& kx, int pair) {
-    const int p = lane & 31, h = lane >> 5;
-    for (int cb = wave; cb * 32 < C; cb += NT_WAVES) {
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-        const int c = cb * 32 + p;
-        for (int o0 = 0; o0 < M; o0 += 32) {
-            float4 z[4];
-            float a[16];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = ld4(dz_row + o0 + 16 * h + 4 * j, valid && o0 + 16 * h + 4 * j < M);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const int o = o0 + 16 * h + s;
-                a[s] = (c < C && o < M) ? W[(int64_t)o * K + c] : 0.f;
-            }
-#pragma unroll
-            for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], elem(z[s >> 2], s & 3), acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int f = cb * 32 + 8 * q + 4 * h;
-            const bool ok = valid && f < C;
-            float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-            if (mask_row) {
-                const float4 hm = ld4(mask_row + f, ok);
-                v.x = hm.x > 0.f ? v.x : 0.f;
-                v.y = hm.y > 0.f ? v.y : 0.f;
-                v.z = hm.z > 0.f ? v.z : 0.f;
-                v.w = hm.w > 0.f ? v.w : 0.f;
-                if constexpr (DROP) v.x *= gscale, v.y *= gscale, v.z *= gscale, v.w *= gscale;
-            }
-            if constexpr (DROP) {
-                if (kx.on) {
-                    float mk[4];
-                    drop_mul4(kx, (uint32_t)pair, (uint32_t)(f >> 2), mk);
-                    mul4(v, mk);
-                }
-            }
-            if (ok) *reinterpret_cast<float4*>(dx_row + f) = v;
-        }
-    }
-}
-
 // TABLE: the item table is trained (the frozen instantiation is the kernel as it was: the widths below fold to d)
 // DROP: dropout is on at one site or more (without it the kernel's instructions are those it had: `dr` is not read)
 template <bool TABLE, bool DROP>
-__global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a, NtDrop dr) {
-    __shared__ float s_dl[NT_TILE];
-    __shared__ int64_t s_ids[NT_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
+__global__ __launch_bounds__(PAIR_THREADS) void ncf_train_pairs_kernel(NtPairsArgs a, NtDrop dr) {
+    __shared__ float s_dl[PAIR_TILE];
+    __shared__ int64_t s_ids[PAIR_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = pair_wave_index(), n = a.n;
     int bid = blockIdx.x;
-    if (bid >= a.tiles + 2 * a.rank_blocks) {                // ---- zero: the embedding gradients, whole
-        float4* z = reinterpret_cast<float4*>(a.zero_base);
-        float4* z2 = reinterpret_cast<float4*>(a.zero2_base);
-        const int64_t total = a.zero_vec4 + (TABLE ? a.zero2_vec4 : 0);
-        for (int64_t i = (int64_t)(bid - a.tiles - 2 * a.rank_blocks) * NT_THREADS + tid; i < total; i += (int64_t)a.zero_blocks * NT_THREADS) {
-            if (!TABLE || i < a.zero_vec4) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            else z2[i - a.zero_vec4] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+    if (bid >= a.tiles + 2 * a.rank_blocks) {                // ---- zero: the embedding gradients, whole, and the table's
+        pair_zero<TABLE>(bid - a.tiles - 2 * a.rank_blocks, a.zero_blocks, a.zero_base, a.zero_vec4, a.zero2_base, a.zero2_vec4, tid);
         return;
     }
     if (bid >= a.tiles) {                                    // ---- rank: the stable order by id, counted
-        bid -= a.tiles;
-        const int kind = bid / a.rank_blocks;
-        const int64_t* ids = kind ? a.items : a.users;
-        int* order = kind ? a.order_i : a.order_u;
-        const int p = (bid - kind * a.rank_blocks) * NT_THREADS + tid;
-        const int64_t mine = p < n ? ids[p] : 0;
-        int rank = 0;
-        for (int q0 = 0; q0 < n; q0 += NT_THREADS) {
-            __syncthreads();
-            s_ids[tid] = q0 + tid < n ? ids[q0 + tid] : 0;
-            __syncthreads();
-            const int cnt = min(NT_THREADS, n - q0);
-            for (int j = 0; j < cnt; ++j) {
-                const int64_t v = s_ids[j];
-                rank += (v < mine || (v == mine && q0 + j < p)) ? 1 : 0;
-            }
-        }
-        if (p < n) order[rank] = p;
+        pair_rank(bid - a.tiles, a.rank_blocks, n, a.users, a.items, a.order_u, a.order_i, s_ids, tid);
         return;
     }
     // ---- tile: forward and data gradient of 32 pairs
     const int d = a.d, F = a.factor, L = a.num_layers;
     const int pl = lane & 31, h = lane >> 5;
-    const int pair = bid * NT_TILE + pl;
+    const int pair = bid * PAIR_TILE + pl;
     const bool valid = pair < n;
     const int64_t uid = valid ? a.users[pair] : 0, iid = valid ? a.items[pair] : 0;
     const float* urow = a.u_mlp + uid * d;
     const float* irow = a.x_item ? a.x_item + (int64_t)pair * d : a.table + iid * d;
-    DropKey kemb = drop_off(), kgmf = drop_off(), klay = drop_off();
+    DropKey kemb = pair_drop_off(), kgmf = pair_drop_off(), klay = pair_drop_off();
     if constexpr (DROP) {
         kemb = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB});
         if (a.neumf) kgmf = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_GMF});
         klay = make_drop_key(DropCfg{dr.rng, dr.p_layer[0], NCF_SITE_LAYER});
     }
-    forward_layer<DROP>(a.layer[0].w, a.layer[0].b, d, 2 * d, urow, d, irow, valid, a.layer[0].act + (int64_t)pair * d, wave, lane, kemb, klay,
-                        pair);
+    pair_linear<Chain::ONE, true, DROP>(a.layer[0].w, a.layer[0].b, d, 2 * d, urow, d, irow, valid, a.layer[0].act + (int64_t)pair * d, wave, lane,
+                                        kemb, klay, pair);
     __syncthreads();
     for (int l = 1; l < L; ++l) {
         const int M = a.layer[l].out;
         if constexpr (DROP) klay = make_drop_key(DropCfg{dr.rng, dr.p_layer[l], NCF_SITE_LAYER + (uint32_t)l});
-        forward_layer<DROP>(a.layer[l].w, a.layer[l].b, M, 2 * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, 2 * M, nullptr, valid,
-                            a.layer[l].act + (int64_t)pair * M, wave, lane, drop_off(), klay, pair);
+        pair_linear<Chain::ONE, true, DROP>(a.layer[l].w, a.layer[l].b, M, 2 * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, 2 * M, nullptr, valid,
+                                            a.layer[l].act + (int64_t)pair * M, wave, lane, pair_drop_off(), klay, pair);
         __syncthreads();
     }
     const float* feat = a.layer[L - 1].act;                  // [n][F]
@@ -325,13 +153,12 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
         if (h == 0) {
             float dl = 0.f;
             if (valid) {
-                const float z = s + a.bp[0], y = a.labels[pair];
-                const float e = expf(-fabsf(z));
-                const float sig = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-                dl = (sig - y) / (float)n;
+                const float z = s + a.bp[0];
+                float loss;
+                pair_bce<true>(z, a.labels[pair], n, dl, loss);
                 if (a.logits) a.logits[pair] = z;
                 a.pz[(int64_t)pair * 2] = dl;
-                a.pz[(int64_t)pair * 2 + 1] = fmaxf(z, 0.f) - z * y + log1pf(e);
+                a.pz[(int64_t)pair * 2 + 1] = loss;
             }
             s_dl[pl] = dl;
         }
@@ -339,8 +166,8 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     __syncthreads();
     float gscale = 1.f;                                      // DROP: 1 / (1 - p) of the layer whose activation masks the gradient
     if constexpr (DROP) gscale = klay.scale;                 // (klay is the last layer's key)
-    for (int e = tid; e < NT_TILE * F; e += NT_THREADS) {    // dz of the last layer and the per-pair GMF gradients
-        const int pp = e / F, f = e - pp * F, pr = bid * NT_TILE + pp;
+    for (int e = tid; e < PAIR_TILE * F; e += PAIR_THREADS) {    // dz of the last layer and the per-pair GMF gradients
+        const int pp = e / F, f = e - pp * F, pr = bid * PAIR_TILE + pp;
         if (pr >= n) continue;
         const float dl = s_dl[pp];
         const int64_t at = (int64_t)pr * F + f;
@@ -359,49 +186,38 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_pairs_kernel(NtPairsArgs
     for (int l = L - 1; l >= 1; --l) {
         const int M = a.layer[l].out;
         if constexpr (DROP) gscale = make_drop_key(DropCfg{dr.rng, dr.p_layer[l - 1], NCF_SITE_LAYER + (uint32_t)(l - 1)}).scale;
-        backward_layer<DROP>(a.layer[l].w, M, 2 * M, 2 * M, a.layer[l].dz + (int64_t)pair * M, a.layer[l - 1].act + (int64_t)pair * 2 * M, valid,
-                             a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane, gscale, drop_off(), pair);
+        pair_linear_bwd<Chain::ONE, DROP>(a.layer[l].w, M, 2 * M, 2 * M, a.layer[l].dz + (int64_t)pair * M,
+                                          a.layer[l - 1].act + (int64_t)pair * 2 * M, valid, a.layer[l - 1].dz + (int64_t)pair * 2 * M, wave, lane,
+                                          gscale, pair_drop_off(), pair);
         __syncthreads();
     }
     const int dxw = TABLE ? 2 * d : d;                       // the columns of layer 0's input that dx covers
-    backward_layer<DROP>(a.layer[0].w, d, 2 * d, dxw, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.dx + (int64_t)pair * dxw, wave, lane,
-                         1.f, kemb, pair);
-}
-
-__device__ __forceinline__ float src_at(const NtSrc& s, int pair, int c) {
-    if (c < s.w1) {
-        const int64_t row = s.idx1 ? s.idx1[pair] : pair;
-        return s.p1[row * s.w1 + c];
-    }
-    const int64_t row = s.idx2 ? s.idx2[pair] : pair;
-    return s.p2[row * s.w2 + (c - s.w1)];
+    pair_linear_bwd<Chain::ONE, DROP>(a.layer[0].w, d, 2 * d, dxw, a.layer[0].dz + (int64_t)pair * d, nullptr, valid, a.dx + (int64_t)pair * dxw,
+                                      wave, lane, 1.f, kemb, pair);
 }
 
 // DROP: the weight task of layer 0 gathers its B operand from the tables and applies the emb mask to it, drawn again per element
 template <bool TABLE, bool DROP>
-__global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs a, NtDrop dr) {
-    __shared__ float s_acc[NT_WAVES][16][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(), n = a.n;
+// 7 waves a SIMD (72 VGPRs), the occupancy of the DROP instantiations before the weight role was shared (68 VGPRs; the plain ones had 80 and 6
+// waves): unbounded, the DROP instantiations take 73, one over; the plain ones need 67 either way
+__global__ __launch_bounds__(PAIR_THREADS, 7) void ncf_train_grads_kernel(NtGradsArgs a, NtDrop dr) {
+    __shared__ float s_acc[PAIR_WAVES][16][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = pair_wave_index(), n = a.n;
     int bid = blockIdx.x;
     if (bid >= a.item_first) {                               // ---- item (rows entry): d_item [n][d] = the item half of dx [n][2 d], 16 bytes a thread
         const int q = a.d >> 2;                              // (d is a multiple of 8)
         const float4* src = reinterpret_cast<const float4*>(a.dx);
         float4* dst = reinterpret_cast<float4*>(a.d_item);
-        for (int64_t i = (int64_t)(bid - a.item_first) * NT_THREADS + tid; i < (int64_t)n * q; i += (int64_t)a.item_blocks * NT_THREADS) {
+        for (int64_t i = (int64_t)(bid - a.item_first) * PAIR_THREADS + tid; i < (int64_t)n * q; i += (int64_t)a.item_blocks * PAIR_THREADS) {
             const int64_t pr = i / q;
             dst[i] = src[pr * 2 * q + q + (i - pr * q)];
         }
         return;
     }
     if (bid >= a.weight_blocks) {                            // ---- rows: segment sums of the per-pair embedding gradients in pair order
-        bid -= a.weight_blocks;
-        const int kind = bid / a.row_blocks;
-        const int s = (bid - kind * a.row_blocks) * NT_WAVES + wave;
-        if (s >= n) return;
-        const int64_t* ids = kind ? a.items : a.users;
-        const int* order = kind ? a.order_i : a.order_u;
-        const int64_t id = ids[order[s]];
-        if (s > 0 && ids[order[s - 1]] == id) return;        // (uniform per wave) not the start of a run
+        const PairRun r = pair_run(bid - a.weight_blocks, a.row_blocks, wave, n, a.users, a.items, a.order_u, a.order_i);
+        if (!r.start) return;
+        const int kind = r.kind;
         const int d = a.d, F = a.factor;
         const int Fg = a.neumf ? F : 0;                      // the GMF rows of this kind
         const int dxw = TABLE ? 2 * d : d;
@@ -416,68 +232,12 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_train_grads_kernel(NtGradsArgs
             }
             else if (c < d) { src = a.dx; dst = a.g_u_mlp; sw = dxw; w = d; cc = c; }
             else { src = a.ggu; dst = a.g_gu; sw = w = F; cc = c - d; }
-            float sum = 0.f;
-            for (int t = s; t < n; ++t) {
-                const int pr = order[t];
-                if (ids[pr] != id) break;
-                sum += src[(int64_t)pr * sw + cc];
-            }
-            dst[id * w + cc] = sum;
+            dst[r.id * w + cc] = pair_run_sum(r, n, src, sw, cc);
         }
         return;
     }
     // ---- weight: one 32 x 32 block of dW = dz^T x, the pairs in order
-    int ti = 0;
-    for (int i = 1; i < a.ntasks; ++i)
-        if (bid >= a.task[i].first) ti = i;
-    const NtTask& t = a.task[ti];
-    const int local = bid - t.first, M = t.m, K = t.b.w1 + t.b.w2;
-    const int mb = local / t.col_blocks, nb = local - mb * t.col_blocks;
-    const bool ones = nb == t.col_blocks - 1;
-    const int p = lane & 31, h = lane >> 5, m = mb * 32 + p, c = nb * 32 + p;
-    DropKey kemb = drop_off();
-    if constexpr (DROP) {
-        if (ti == 0 && !ones) kemb = make_drop_key(DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB});
-    }
-    f32x16 acc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-    for (int ch = wave; ch * 32 < n; ch += NT_WAVES) {
-        float av[16], bv[16];
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int pair = ch * 32 + 16 * h + s;
-            const bool ok = pair < n;
-            av[s] = (ok && m < M) ? t.a[(int64_t)pair * M + m] : 0.f;
-            bv[s] = ones ? (p == 0 ? 1.f : 0.f) : ((ok && c < K) ? src_at(t.b, pair, c) : 0.f);
-            if constexpr (DROP) {
-                if (kemb.on) bv[s] *= drop_mul1(kemb, (uint32_t)pair, (uint32_t)c);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int g = 0; g < 16; ++g) s_acc[wave][g][lane] = acc[g];
-    __syncthreads();
-    const int gq = tid >> 6;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-        const int g = gq * 4 + gg;
-        const float v = (s_acc[0][g][lane] + s_acc[1][g][lane]) + (s_acc[2][g][lane] + s_acc[3][g][lane]);
-        const int mo = mb * 32 + rho(g) + 4 * h;
-        if (t.predict) {
-            if (mo == 0) {
-                if (ones) { if (p == 0) t.gb[0] = v; }
-                else if (c < K) t.gw[c] = v;
-            } else if (mo == 1 && ones && p == 0) {
-                a.loss[0] = v / (float)n;
-            }
-        } else if (mo < M) {
-            if (ones) { if (p == 0) t.gb[mo] = v; }
-            else if (c < K) t.gw[(int64_t)mo * K + c] = v;
-        }
-    }
+    pair_weight_block<DROP, true>(a.task, a.ntasks, bid, n, a.loss, DropCfg{dr.rng, dr.p_emb, NCF_SITE_EMB}, s_acc, tid, lane, wave);
 }
 
 struct NtShape {
@@ -488,8 +248,7 @@ struct NtShape {
 static int nt_shape(int factor_num, int num_layers, int kind, int64_t user_num, int64_t item_num, const char* who, NtShape* s) {
     int d;
     if (int rc = ncf_head_check(factor_num, num_layers, kind, who, &d)) return rc;
-    PMGT_CHECK(user_num >= 1 && user_num <= 0x7FFFFFFELL, -2, "%s: user_num = %lld outside [1, 2^31 - 2]", who, (long long)user_num);
-    PMGT_CHECK(item_num >= 1 && item_num <= 0x7FFFFFFELL, -2, "%s: item_num = %lld outside [1, 2^31 - 2]", who, (long long)item_num);
+    if (int rc = pair_check_rows(who, user_num, item_num)) return rc;
     *s = NtShape{factor_num, num_layers, d, kind == PMGT_NCF_NEUMF_END, user_num, item_num};
     return 0;
 }
@@ -547,7 +306,7 @@ namespace pmgt {
 static int64_t nt_workspace_bytes(int factor_num, int num_layers, int kind, int64_t n, bool table, const char* who) {
     NtShape s;
     if (int rc = nt_shape(factor_num, num_layers, kind, 1, 1, who, &s)) return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_NCF_TRAIN_MAX_PAIRS);
+    if (int rc = pair_check_n(who, n, PMGT_NCF_TRAIN_MAX_PAIRS)) return rc;
     return nt_workspace_floats(s, n, table) * (int64_t)sizeof(float);
 }
 
@@ -559,7 +318,7 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     PMGT_CHECK(head != nullptr, -2, "%s: NULL head", who);
     NtShape s;
     if (int rc = nt_shape(head->factor_num, head->num_layers, head->kind, head->user_num, head->item_num, who, &s)) return rc;
-    PMGT_CHECK(n >= 1 && n <= PMGT_NCF_TRAIN_MAX_PAIRS, -2, "%s: n = %lld pairs outside [1, %d]", who, (long long)n, PMGT_NCF_TRAIN_MAX_PAIRS);
+    if (int rc = pair_check_n(who, n, PMGT_NCF_TRAIN_MAX_PAIRS)) return rc;
     PMGT_CHECK((rows || head->table) && head->params && head->grads && users && items && labels && loss && workspace, -2, "%s: NULL buffer", who);
     PMGT_CHECK(!want_table || table_grad, -2, "%s: NULL table_grad", who);
     PMGT_CHECK(!rows || (x_item && d_item), -2, "%s: NULL x_item or d_item", who);
@@ -567,24 +326,13 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     PMGT_CHECK(((table_bits | (uintptr_t)head->params | (uintptr_t)head->grads | (uintptr_t)workspace | (uintptr_t)table_grad) & 15) == 0, -2,
                "%s: the table (the rows entry: x_item and d_item), the parameters, the gradients (the table's included) and the workspace must be "
                "16-byte aligned", who);
-    PMGT_CHECK((((uintptr_t)labels | (uintptr_t)loss | (uintptr_t)logits) & 3) == 0 && (((uintptr_t)users | (uintptr_t)items) & 7) == 0, -2,
-               "%s: misaligned buffer", who);
+    if (int rc = pair_check_small(who, users, items, labels, loss, logits)) return rc;
     const bool wide = want_table || rows;                    // dx covers all 2 d columns of layer 0's input
     const int64_t need = nt_workspace_floats(s, n, wide) * (int64_t)sizeof(float);
     PMGT_CHECK(workspace_bytes >= need, -2, "%s: workspace of %lld bytes below the %lld needed", who, (long long)workspace_bytes, (long long)need);
-    NtDrop dr = {};
-    bool drop_on = false;                                    // every p 0: the instantiations without dropout
-    if (drop) {
-        dr.rng = drop->rng, dr.p_emb = drop->p_emb;
-        PMGT_CHECK(dr.p_emb >= 0.f && dr.p_emb < 1.f, -2, "%s: p_emb = %g outside [0, 1)", who, (double)dr.p_emb);      // (a NaN fails both)
-        drop_on = dr.p_emb > 0.f;
-        for (int l = 0; l < s.L; ++l) {
-            dr.p_layer[l] = drop->p_layer[l];
-            PMGT_CHECK(dr.p_layer[l] >= 0.f && dr.p_layer[l] < 1.f, -2, "%s: p_layer[%d] = %g outside [0, 1)", who, l, (double)dr.p_layer[l]);
-            drop_on = drop_on || dr.p_layer[l] > 0.f;
-        }
-        PMGT_CHECK(!drop_on || (dr.rng && ((uintptr_t)dr.rng & 7) == 0), -2, "%s: dropout needs the device {seed, step} pair, 8-byte aligned", who);
-    }
+    NtDrop dr;
+    bool drop_on;                                            // every p 0: the instantiations without dropout
+    if (int rc = pair_check_ncf_dropout(who, drop, s.L, &dr, &drop_on)) return rc;
     int64_t off[PMGT_NCF_TRAIN_TENSORS];
     nt_layout(s, off);
     const float* P = head->params;
@@ -627,41 +375,22 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     pa.zero2_base = table_grad;
     pa.zero2_vec4 = want_table ? s.item_num * d / 4 : 0;     // (d is a multiple of 8)
     pa.n = (int)n, pa.d = d, pa.factor = F, pa.num_layers = L, pa.neumf = s.neumf;
-    pa.tiles = (int)cdiv64(n, NT_TILE);
-    pa.rank_blocks = (int)cdiv64(n, NT_THREADS);
-    pa.zero_blocks = (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(pa.zero_vec4 + pa.zero2_vec4, NT_THREADS));
+    pa.tiles = (int)cdiv64(n, PAIR_TILE);
+    pa.rank_blocks = (int)cdiv64(n, PAIR_THREADS);
+    pa.zero_blocks = (int)std::min<int64_t>(PAIR_ZERO_BLOCKS, cdiv64(pa.zero_vec4 + pa.zero2_vec4, PAIR_THREADS));
 
     int first = 0;
     for (int l = 0; l < L; ++l) {
         const int out = d >> l;
-        NtTask& t = ga.task[l];
-        t.a = pa.layer[l].dz;
-        t.m = out;
-        if (l == 0) t.b = rows ? NtSrc{pa.u_mlp, users, d, x_item, nullptr, d} : NtSrc{pa.u_mlp, users, d, pa.table, items, d};
-        else t.b = NtSrc{pa.layer[l - 1].act, nullptr, 2 * out, nullptr, nullptr, 0};
-        t.gw = G + off[3 + 2 * l];
-        t.gb = G + off[4 + 2 * l];
-        t.col_blocks = (2 * out + 31) / 32 + 1;
-        t.first = first;
-        t.predict = 0;
-        first += (out + 31) / 32 * t.col_blocks;
+        const PairSrc x0 = rows ? PairSrc{pa.u_mlp, users, d, x_item, nullptr, d} : PairSrc{pa.u_mlp, users, d, pa.table, items, d};
+        pair_add_task(ga.task, &ga.ntasks, &first, pa.layer[l].dz, out, l == 0 ? x0 : PairSrc{pa.layer[l - 1].act, nullptr, 2 * out, nullptr, nullptr, 0},
+                      G + off[3 + 2 * l], G + off[4 + 2 * l], false);
     }
-    {
-        NtTask& t = ga.task[L];
-        t.a = pa.pz;
-        t.m = 2;
-        if (s.neumf) t.b = NtSrc{pa.gprod, nullptr, F, pa.layer[L - 1].act, nullptr, F};
-        else t.b = NtSrc{pa.layer[L - 1].act, nullptr, F, nullptr, nullptr, 0};
-        t.gw = G + off[OFF_WP];
-        t.gb = G + off[OFF_BP];
-        t.col_blocks = ((s.neumf ? 2 * F : F) + 31) / 32 + 1;
-        t.first = first;
-        t.predict = 1;
-        first += t.col_blocks;
-    }
-    ga.ntasks = L + 1;
+    pair_add_task(ga.task, &ga.ntasks, &first, pa.pz, 2,
+                  s.neumf ? PairSrc{pa.gprod, nullptr, F, pa.layer[L - 1].act, nullptr, F} : PairSrc{pa.layer[L - 1].act, nullptr, F, nullptr, nullptr, 0},
+                  G + off[OFF_WP], G + off[OFF_BP], true);
     ga.weight_blocks = first;
-    ga.row_blocks = (int)cdiv64(n, NT_WAVES);
+    ga.row_blocks = (int)cdiv64(n, PAIR_WAVES);
     ga.users = users, ga.items = items;
     ga.order_u = pa.order_u, ga.order_i = pa.order_i;
     ga.dx = pa.dx, ga.ggu = pa.ggu, ga.ggi = pa.ggi;
@@ -676,22 +405,22 @@ static int nt_grad(const char* who, const pmgt_ncf_train* head, const int64_t* u
     const int kinds = (s.neumf || want_table) ? 2 : 1;       // MLP over a frozen table has no rows indexed by item: its item order is not read
     ga.d_item = d_item;
     ga.item_first = rows ? ga.weight_blocks + kinds * ga.row_blocks : INT_MAX;
-    ga.item_blocks = rows ? (int)std::min<int64_t>(NT_ZERO_BLOCKS, cdiv64(n * (d / 4), NT_THREADS)) : 0;
+    ga.item_blocks = rows ? (int)std::min<int64_t>(PAIR_ZERO_BLOCKS, cdiv64(n * (d / 4), PAIR_THREADS)) : 0;
     const unsigned grid1 = (unsigned)(pa.tiles + 2 * pa.rank_blocks + pa.zero_blocks);
     if (drop_on) {
-        if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
-        else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, true>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+        if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, true>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
+        else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, true>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
     }
-    else if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
-    else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, false>), dim3(grid1), dim3(NT_THREADS), 0, st, pa, dr);
+    else if (wide) hipLaunchKernelGGL((ncf_train_pairs_kernel<true, false>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
+    else hipLaunchKernelGGL((ncf_train_pairs_kernel<false, false>), dim3(grid1), dim3(PAIR_THREADS), 0, st, pa, dr);
     PMGT_LAUNCH_OK();
     const unsigned grid2 = (unsigned)(ga.weight_blocks + kinds * ga.row_blocks + ga.item_blocks);
     if (drop_on && dr.p_emb > 0.f) {                         // (launch 2 draws the emb mask only)
-        if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
-        else hipLaunchKernelGGL((ncf_train_grads_kernel<false, true>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+        if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, true>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
+        else hipLaunchKernelGGL((ncf_train_grads_kernel<false, true>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
     }
-    else if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
-    else hipLaunchKernelGGL((ncf_train_grads_kernel<false, false>), dim3(grid2), dim3(NT_THREADS), 0, st, ga, dr);
+    else if (wide) hipLaunchKernelGGL((ncf_train_grads_kernel<true, false>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
+    else hipLaunchKernelGGL((ncf_train_grads_kernel<false, false>), dim3(grid2), dim3(PAIR_THREADS), 0, st, ga, dr);
     PMGT_LAUNCH_OK();
     return 0;
 }
