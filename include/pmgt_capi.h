@@ -468,6 +468,33 @@ int pmgt_item_sim_norms(const float* table, int64_t n_items, int d, float eps, f
 int pmgt_item_sim_score(const float* table, const float* inv_norm, const int64_t* queries, int64_t n, int64_t n_items, int d, float* scores,
                         int64_t row_stride, void* stream);
 
+/* RECOMMENDING FROM A USER'S HISTORY ON THE DEVICE (item-kNN): scores[r][j] = agg over i in H(users[r]) of s(i, j) for every r in [0, n) and
+ * j in [0, n_items), where s is pmgt_item_sim_score's score over the same table and inv_norm (NULL: metric "dot") and H(u) is the list
+ * hist_items[hist_ptr[u] .. hist_ptr[u + 1]) of a CSR over user ids (hist_ptr int64 [user_num + 1], hist_items int32: item ids, every
+ * list ASCENDING WITHOUT DUPLICATES; THE CALLER CHECKS the CSR, it is read as it is).  A user the trained heads never saw is served
+ * by this, and so is an encoder that has no head yet.  The rows of scores are what pmgt_topk_rows and pmgt_rank_heldout take.
+ * One kernel: pmgt_item_sim_score's tile with a segmented reduction over the history rows in its epilogue; the [sum of |H|, n_items] block
+ * of item scores is never written, the output is [n][row_stride] fp32 (entries [r][n_items .. row_stride) are not written; offsets are 64-bit).
+ *
+ * THE SCORE.  s(i, j) has the bits of pmgt_item_sim_score.  With i_0 < i_1 < .. the items of the list in its order:
+ *   PMGT_HISTORY_MEAN:  acc = s(i_0, j); acc = acc + s(i_t, j) for t = 1 .. len - 1, every sum rounded to fp32, none contracted;
+ *                       score = acc / (float)len, one IEEE division
+ *   PMGT_HISTORY_MAX:   the largest s(i_t, j); NaN if any term is NaN; a zero result is +0.0f (the fold of the selection's key)
+ * The bits of scores[r][j] depend on H(users[r]), the rows of its items and row j alone -- not on n, the slot r, the other users of the call
+ * or how the catalogue is cut into calls: a workgroup owns whole users, and one thread folds a (user, candidate) pair from the first item
+ * of the list to the last however long the list is.  A NaN in item row x reaches column x and every score of the users whose list holds
+ * x, and nothing else.  A user id outside [0, user_num) or a user with an empty list is never dereferenced: its row of scores is NaN.  An
+ * item id outside [0, n_items) in a list is never dereferenced: its terms are NaN.
+ * One launch, stream-ordered, no allocation, no wait, no atomic: the same inputs give the same bits.
+ * Covered: 1 <= d <= PMGT_ITEM_SIM_MAX_D, 1 <= n_items <= 2^31 - 2, 1 <= n <= PMGT_NCF_MAX_USERS per call, user_num >= 1, lists of any
+ * length, row_stride >= n_items.  Refused (-2) before anything is launched, writing nothing: a size outside these limits, an unknown agg, a
+ * NULL or misaligned buffer (inv_norm may be NULL; hist_ptr and users: 8 bytes, the rest: 4), more workgroups than a grid holds.
+ * Added without a bump of pmgt_abi_version(): one entry, nothing existing moved. */
+#define PMGT_HISTORY_MEAN 0
+#define PMGT_HISTORY_MAX 1
+int pmgt_history_score(const float* table, const float* inv_norm, const int64_t* hist_ptr, const int32_t* hist_items, const int64_t* users,
+                       int64_t n, int64_t user_num, int64_t n_items, int d, int agg, float* scores, int64_t row_stride, void* stream);
+
 /* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
  * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
  * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and

@@ -16,6 +16,7 @@ from .catalogue_eval import (CatalogueMetrics, HeldoutRanks, catalogue_metrics_h
                              heldout_ranks_host)
 from .item_graph import ItemGraph, build_item_graph, item_graph_host, synthetic_interactions  # noqa: F401
 from .similar import ItemSimScorer, edges_csr, evaluate_neighbours, holdout_edges, item_sim_host, similar_items  # noqa: F401
+from .history import HistoryScorer, evaluate_history, history_scores_host, recommend_from_history  # noqa: F401
 
 __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_grad_host", "ng_sample", "NcfHeadTrainer", "fit_ncf",
            "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks", "DCN", "DcnGrad", "DcnTrainer", "evaluate_ctr", "fit_dcn",
@@ -24,4 +25,5 @@ __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_gr
            "ncf_model_scores_host", "NcfModelScorer", "dcn_scores_host", "DcnScorer", "evaluate_catalogue", "heldout_ranks_host",
            "catalogue_metrics_host", "heldout_csr", "HeldoutRanks", "CatalogueMetrics", "sgd_step_host", "pair_schedule_steps",
            "ItemGraph", "build_item_graph", "item_graph_host", "synthetic_interactions",
-           "ItemSimScorer", "edges_csr", "evaluate_neighbours", "holdout_edges", "item_sim_host", "similar_items"]
+           "ItemSimScorer", "edges_csr", "evaluate_neighbours", "holdout_edges", "item_sim_host", "similar_items",
+           "HistoryScorer", "evaluate_history", "history_scores_host", "recommend_from_history"]

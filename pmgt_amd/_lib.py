@@ -147,6 +147,7 @@ TOPK_MAX_K, TOPK_FLAG_NAN, TOPK_FLAG_SHORT = 1024, 1, 2      # PMGT_TOPK_*
 RANK_HELDOUT_CHUNK, RANK_HELDOUT_FLAG_EXCLUDED, RANK_HELDOUT_HEADER_BYTES = 1024, 4, 128      # PMGT_RANK_HELDOUT_*
 ITEM_GRAPH_MIN_SLOTS, ITEM_GRAPH_MAX_SLOTS = 16, 1024      # PMGT_ITEM_GRAPH_*_SLOTS
 ITEM_SIM_MAX_D = 1024      # PMGT_ITEM_SIM_MAX_D
+HISTORY_AGGS = ("mean", "max")      # PMGT_HISTORY_* in order
 
 AVG_MODES = ("swa", "ema")      # PMGT_AVG_* in order
 AVG_STATE_BYTES = 32            # PMGT_AVG_STATE_BYTES: int64 n_upd; 32-bit words [2] skip word, [3] w_old, [4] w_new, [5..7] reserved
@@ -174,7 +175,7 @@ HIP_SYMBOLS = [
     "pmgt_weight_average_update", "pmgt_weight_swap",
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows", "pmgt_rank_heldout", "pmgt_rank_heldout_reduce",
-    "pmgt_item_graph_default_slots", "pmgt_item_graph_count", "pmgt_item_graph_fill", "pmgt_item_sim_norms", "pmgt_item_sim_score",
+    "pmgt_item_graph_default_slots", "pmgt_item_graph_count", "pmgt_item_graph_fill", "pmgt_item_sim_norms", "pmgt_item_sim_score", "pmgt_history_score",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
@@ -349,6 +350,8 @@ def hip():
     L.pmgt_item_graph_fill.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i, vp, vp, vp, i64, vp, vp, vp, i64, vp]
     L.pmgt_item_sim_norms.argtypes = [vp, i64, i, f, vp, vp]      # (table, n_items, d, eps, inv_norm, stream)
     L.pmgt_item_sim_score.argtypes = [vp, vp, vp, i64, i64, i, vp, i64, vp]      # (table, inv_norm or NULL, queries, n, n_items, d, scores, row_stride, stream)
+    # (table, inv_norm or NULL, hist_ptr, hist_items, users, n, user_num, n_items, d, agg, scores, row_stride, stream)
+    L.pmgt_history_score.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i, i, vp, i64, vp]
     L.pmgt_ncf_train_layout.restype = i64
     L.pmgt_ncf_train_layout.argtypes = [i, i, i, i64, i64, vp]
     L.pmgt_ncf_train_workspace_bytes.restype = i64
