@@ -495,6 +495,40 @@ int pmgt_item_sim_score(const float* table, const float* inv_norm, const int64_t
 int pmgt_history_score(const float* table, const float* inv_norm, const int64_t* hist_ptr, const int32_t* hist_items, const int64_t* users,
                        int64_t n, int64_t user_num, int64_t n_items, int d, int agg, float* scores, int64_t row_stride, void* stream);
 
+/* TRUNCATED, WEIGHTED ITEM-kNN ON THE DEVICE over a precomputed neighbour index: the classic item-kNN keeps, per item, only its m most
+ * similar items and scores a candidate by the sum over the history items that LIST it.  The index is nbr int32 [n_items][idx_stride] and
+ * sim fp32 [n_items][idx_stride], of which the first m columns of every row are used (m <= idx_stride: the index of a smaller m is a prefix
+ * of the index of a larger one, so a sweep over m reads one index).  A slot holds a neighbour id or, from the first unused slot of a
+ * short row on, -1; THE LIVE IDS OF A ROW ARE PAIRWISE DISTINCT -- THE CALLER CHECKS the index, it is read as it is, and the kernel's
+ * freedom from races rests on this.  H(u) is the list hist_items[hist_ptr[u] .. hist_ptr[u + 1]) of pmgt_history_score's CSR (every list
+ * ASCENDING WITHOUT DUPLICATES, checked by the caller), hist_weights fp32 aligned with hist_items (ratings, a time decay) or NULL: every
+ * weight 1.  The rows of scores are what pmgt_topk_rows and pmgt_rank_heldout take; the output is [n][row_stride] fp32 (entries
+ * [r][n_items .. row_stride) and the rows from n on are not written; offsets are 64-bit).  Nothing of the embedding table is read: a user
+ * costs |H| m gathered entries and the n_items floats of the row, whatever d was.
+ *
+ * THE SCORE.  With i_0 < i_1 < .. the items of the list in its order and w_t the weight of entry t, for every r in [0, n), j in [0, n_items):
+ *   acc = +0.0f
+ *   for t = 0 .. len - 1, in this order:  if j is in the first m slots of row i_t, at slot c:
+ *       term = sim[i_t][c]  (hist_weights NULL)   |   w_t * sim[i_t][c] rounded once to fp32
+ *       acc  = acc + term   rounded to fp32, never contracted into an fma
+ *   scores[r][j] = acc
+ * An item that no history item lists scores +0.0f, the empty sum, and a zero result is always +0.0f.  The bits of scores[r][j] depend on
+ * H(users[r]), its weights and the index rows of its items alone -- not on n, the slot r, the other users of the call, how the catalogue is
+ * cut into tiles or the launch geometry: a workgroup keeps the accumulators of one slot and pmgt_knn_score_tile() consecutive candidates in
+ * LDS, each of its waves owns a fixed share of these columns and walks the whole list itself, first entry to last, with plain LDS reads,
+ * adds and writes.  A user id outside [0, user_num) or a user with an empty list is never dereferenced: its row of scores is NaN.  A
+ * history item outside [0, n_items) is never dereferenced: it makes the whole row NaN.  A neighbour id < 0 or >= n_items is skipped.
+ * One launch, stream-ordered, no allocation, no wait, no atomic of any kind: the same inputs give the same bits.
+ * Covered: 1 <= m <= 1024 (PMGT_TOPK_MAX_K, what the selection builds) with m <= idx_stride, 1 <= n_items <= 2^31 - 2, 1 <= n <=
+ * PMGT_NCF_MAX_USERS per call, user_num >= 1, lists of any length, row_stride >= n_items.  Refused (-2) before anything is launched, writing
+ * nothing: a size outside these limits, a NULL or misaligned buffer (hist_weights may be NULL; hist_ptr and users: 8 bytes, the rest: 4),
+ * more workgroups than a grid holds (n times the tiles of the catalogue).
+ * Added without a bump of pmgt_abi_version(): two entries, nothing existing moved. */
+int pmgt_knn_score_tile(void);      /* the candidates a workgroup owns (KNN_T of ops/knn_score.hip): where the catalogue is cut */
+int pmgt_knn_score(const int32_t* nbr, const float* sim, int64_t idx_stride, int m, const int64_t* hist_ptr, const int32_t* hist_items,
+                   const float* hist_weights /* may be NULL */, const int64_t* users, int64_t n, int64_t user_num, int64_t n_items,
+                   float* scores, int64_t row_stride, void* stream);
+
 /* Training of the head of PMGT_NCF over a FROZEN item table ON THE DEVICE (the reference's downstream step, pmgt/ncf/trainer.py:183-200 with
  * `--item-init-emb-path`: embed_item_MLP frozen, BCEWithLogitsLoss): for n (user, item, label) pairs the mean loss, the logits and the
  * gradient of that loss with respect to EVERY parameter of the head, in two launches, no sync, no allocation, no atomic: capturable, and

@@ -17,6 +17,8 @@ from .catalogue_eval import (CatalogueMetrics, HeldoutRanks, catalogue_metrics_h
 from .item_graph import ItemGraph, build_item_graph, item_graph_host, synthetic_interactions  # noqa: F401
 from .similar import ItemSimScorer, edges_csr, evaluate_neighbours, holdout_edges, item_sim_host, similar_items  # noqa: F401
 from .history import HistoryScorer, evaluate_history, history_scores_host, recommend_from_history  # noqa: F401
+from .item_knn import (ItemKnnIndex, ItemKnnScorer, build_item_knn, decay_weights, evaluate_item_knn, item_knn_scores_host,  # noqa: F401
+                       recommend_item_knn, weighted_history_csr)
 
 __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_grad_host", "ng_sample", "NcfHeadTrainer", "fit_ncf",
            "normalize_item_table", "ncf_dropout_keep", "ncf_dropout_masks", "DCN", "DcnGrad", "DcnTrainer", "evaluate_ctr", "fit_dcn",
@@ -26,4 +28,6 @@ __all__ = ["PMGTConfig", "recommend", "topk_host", "ncf_head_host", "ncf_head_gr
            "catalogue_metrics_host", "heldout_csr", "HeldoutRanks", "CatalogueMetrics", "sgd_step_host", "pair_schedule_steps",
            "ItemGraph", "build_item_graph", "item_graph_host", "synthetic_interactions",
            "ItemSimScorer", "edges_csr", "evaluate_neighbours", "holdout_edges", "item_sim_host", "similar_items",
-           "HistoryScorer", "evaluate_history", "history_scores_host", "recommend_from_history"]
+           "HistoryScorer", "evaluate_history", "history_scores_host", "recommend_from_history",
+           "ItemKnnIndex", "ItemKnnScorer", "build_item_knn", "decay_weights", "evaluate_item_knn", "item_knn_scores_host",
+           "recommend_item_knn", "weighted_history_csr"]

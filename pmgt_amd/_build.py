@@ -30,7 +30,8 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 # the several-buffer step of the fine-tune trainer under a schedule, the guard or SGD (segments_step.hip), which shares that header too;
 # the co-review counts that build the item graph from interactions (item_graph.hip), a preprocessing stage the step never launches;
 # the item-by-item dot / cosine scores from the encoder's embedding table (item_sim.hip), out of csrc/ for ncf_score.hip's reason;
-# the item-kNN scores of users from their histories over that table (history_score.hip: item_sim.hip's tile with a segmented reduction), likewise
+# the item-kNN scores of users from their histories over that table (history_score.hip: item_sim.hip's tile with a segmented reduction), likewise;
+# the truncated, weighted item-kNN scores over a precomputed neighbour index (knn_score.hip: gather, LDS accumulators, store), likewise
 OPS_SOURCES = [os.path.join(HERE, "ops", "row_ops.hip"), os.path.join(HERE, "ops", "optimizer_step.hip"),
                os.path.join(HERE, "ops", "dropout_keep.hip"), os.path.join(HERE, "ops", "eval_metrics.hip"),
                os.path.join(HERE, "ops", "weight_average.hip"), os.path.join(HERE, "ops", "ranking_metrics.hip"),
@@ -41,7 +42,7 @@ OPS_SOURCES = [os.path.join(HERE, "ops", "row_ops.hip"), os.path.join(HERE, "ops
                os.path.join(HERE, "ops", "dcn_score.hip"), os.path.join(HERE, "ops", "catalogue_rank.hip"),
                os.path.join(HERE, "ops", "sgd_step.hip"), os.path.join(HERE, "ops", "segments_step.hip"),
                os.path.join(HERE, "ops", "item_graph.hip"), os.path.join(HERE, "ops", "item_sim.hip"),
-               os.path.join(HERE, "ops", "history_score.hip")]
+               os.path.join(HERE, "ops", "history_score.hip"), os.path.join(HERE, "ops", "knn_score.hip")]
 HIP_SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_wsr.hip", "gemm_rowln.hip", "fp8.hip", "rowops.hip", "attention.hip", "attention_mfma.hip", "qkvc_attn.hip", "segsum.hip", "loss.hip", "optim.hip", "engine.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in architectural VGPRs (no v_accvgpr_read moves before every VALU

@@ -176,6 +176,7 @@ HIP_SYMBOLS = [
     "pmgt_rank_workspace_bytes", "pmgt_rank_reset", "pmgt_rank_append", "pmgt_rank_reduce",
     "pmgt_ncf_score", "pmgt_topk_workspace_bytes", "pmgt_topk_rows", "pmgt_rank_heldout", "pmgt_rank_heldout_reduce",
     "pmgt_item_graph_default_slots", "pmgt_item_graph_count", "pmgt_item_graph_fill", "pmgt_item_sim_norms", "pmgt_item_sim_score", "pmgt_history_score",
+    "pmgt_knn_score", "pmgt_knn_score_tile",
     "pmgt_ncf_train_layout", "pmgt_ncf_train_workspace_bytes", "pmgt_ncf_train_grad",
     "pmgt_ncf_train_table_workspace_bytes", "pmgt_ncf_train_grad_table", "pmgt_ncf_train_grad_dropout",
     "pmgt_ncf_train_rows_workspace_bytes", "pmgt_ncf_train_grad_rows",
@@ -352,6 +353,9 @@ def hip():
     L.pmgt_item_sim_score.argtypes = [vp, vp, vp, i64, i64, i, vp, i64, vp]      # (table, inv_norm or NULL, queries, n, n_items, d, scores, row_stride, stream)
     # (table, inv_norm or NULL, hist_ptr, hist_items, users, n, user_num, n_items, d, agg, scores, row_stride, stream)
     L.pmgt_history_score.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i, i, vp, i64, vp]
+    # (nbr, sim, idx_stride, m, hist_ptr, hist_items, hist_weights or NULL, users, n, user_num, n_items, scores, row_stride, stream)
+    L.pmgt_knn_score.argtypes = [vp, vp, i64, i, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp]
+    L.pmgt_knn_score_tile.argtypes = []      # KNN_T of ops/knn_score.hip: the candidates of a tile
     L.pmgt_ncf_train_layout.restype = i64
     L.pmgt_ncf_train_layout.argtypes = [i, i, i, i64, i64, vp]
     L.pmgt_ncf_train_workspace_bytes.restype = i64

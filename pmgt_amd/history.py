@@ -40,13 +40,9 @@ def is_csr_pair(x) -> bool:
     return isinstance(x, tuple) and len(x) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in x)
 
 
-def history_csr(histories, n_items: int, user_num: int = None, who: str = "histories"):
-    """The history CSR over user ids from (user, item) integer pairs or a ready (indptr, items) pair -> (indptr int64 [user_num + 1], items
-    int32), every list ASCENDING by item with DUPLICATES DROPPED: the order of the pairs does not matter and a pair given twice counts once.
-    user_num None: the CSR's own length, or the largest user id of the pairs plus one.  A HistoryCSR (this function's own result) over the
-    same ids is returned as it is."""
-    if isinstance(histories, HistoryCSR) and user_num in (None, len(histories[0]) - 1) and int(histories[1].max()) < n_items:
-        return histories
+def history_entries(histories, n_items: int, user_num: int = None, who: str = "histories"):
+    """The validated entries of `histories` ((user, item) integer pairs or a ready (indptr, items) pair) IN THE ORDER GIVEN
+    -> (owner int64 [P], items int64 [P], user_num); user_num None: the CSR's own length, or the largest user id of the pairs plus one."""
     if is_csr_pair(histories):
         if user_num is None:
             user_num = len(histories[0]) - 1
@@ -69,6 +65,17 @@ def history_csr(histories, n_items: int, user_num: int = None, who: str = "histo
         owner, items = pairs[:, 0], pairs[:, 1]
     if len(items) < 1:
         raise ValueError(f"{who}: no history at all")
+    return owner, items, user_num
+
+
+def history_csr(histories, n_items: int, user_num: int = None, who: str = "histories"):
+    """The history CSR over user ids from (user, item) integer pairs or a ready (indptr, items) pair -> (indptr int64 [user_num + 1], items
+    int32), every list ASCENDING by item with DUPLICATES DROPPED: the order of the pairs does not matter and a pair given twice counts once.
+    user_num None: the CSR's own length, or the largest user id of the pairs plus one.  A HistoryCSR (this function's own result) over the
+    same ids is returned as it is."""
+    if isinstance(histories, HistoryCSR) and user_num in (None, len(histories[0]) - 1) and int(histories[1].max()) < n_items:
+        return histories
+    owner, items, user_num = history_entries(histories, n_items, user_num, who)
     key = np.unique(owner * np.int64(n_items) + items)
     indptr = np.zeros(user_num + 1, dtype=np.int64)
     np.cumsum(np.bincount(key // n_items, minlength=user_num), out=indptr[1:])

@@ -388,10 +388,10 @@ class TopkRows:
         return out
 
 
-def select_device(scorer: CatalogueScorer, ids, batch: int, k: int, indptr, excl, id_num: int):
+def select_rows_device(scorer: CatalogueScorer, ids, batch: int, k: int, indptr, excl, id_num: int):
     """The selection pass on the device: per batch of `ids` (int64 numpy, checked by the caller) scorer.score then TopkRows.select, with the
     exclusion CSR (indptr, excl) over `id_num` ids.  Everything is uploaded and built before the first score; nothing is copied to the host
-    and nothing waits inside the loop; one copy at the end fetches -> (items int32 [n, k], scores fp32 [n, k], flags uint32 [n]) as numpy."""
+    and nothing waits -> (items int32 [n, k], scores fp32 [n, k], flags int32 [n]) as contiguous DEVICE tensors."""
     import torch
     dev, n, n_items = scorer.device, len(ids), scorer.n_items
     picker = TopkRows(dev, batch, n_items, k, indptr, excl, id_num)
@@ -403,7 +403,12 @@ def select_device(scorer: CatalogueScorer, ids, batch: int, k: int, indptr, excl
         hi = min(lo + batch, n)
         scorer.score(ids_d[lo:hi], out=work)
         picker.select(work[: hi - lo], ids_d[lo:hi], out=tuple(t[lo:hi] for t in out))
-    items, scores, flags = (t.cpu().numpy() for t in out)      # the copies out: after the loop
+    return out
+
+
+def select_device(scorer: CatalogueScorer, ids, batch: int, k: int, indptr, excl, id_num: int):
+    """select_rows_device, then one copy at the end fetches -> (items int32 [n, k], scores fp32 [n, k], flags uint32 [n]) as numpy."""
+    items, scores, flags = (t.cpu().numpy() for t in select_rows_device(scorer, ids, batch, k, indptr, excl, id_num))      # the copies out: after the loop
     return items, scores, flags.view(np.uint32)
 
 
